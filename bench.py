@@ -1,10 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- outer iterations/s of the MI355X inner-update engine on BASELINE.json's configurations.
 
-    python bench.py --gpus N --steps K --warmup W [--config B|C|D|E] [--no-cpu] [--no-fixed] [--no-extra]
+    python bench.py --gpus N --steps K --warmup W [--config B|C|D|E] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-fixed] [--no-extra] [--no-kernels]]
 
 One "step" = one outer iteration (nn_fac one_nmf_step / one_ntf_step semantics: every factor update + the cost) on
 synthetic dense data already resident in HBM when the timed region starts.
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (value = iterations/s, ms_per_step = one timed
+step).  --full adds everything else the line can carry (rooflines, CPU baseline, fixed-work / steady-state /
+nondeterministic legs, extra_configs of the default line); --no-cpu / --no-fixed / --no-extra / --no-kernels switch parts of
+it off again.  --dump-outputs DIR writes what the timed path returned after its last step -- the factors (U, V; NTF: F0, F1,
+F2) and the last cost -- as DIR/<name>.npy (float32 / float64 as computed; at most 64 MB in all: above that, a fixed seeded
+sample of the rows of the row-sharded factor and its row indices as <name>_rows.npy).  Inputs depend on the arguments only.
 
   B (default)  100000 x 2000 rank 50 NMF, HALS, fp32, deterministic (alpha = inf, delta = 0.01, maxiter = 100) -- configs[1],
                the configuration BASELINE.json's metric is quoted on.  N > 1: X row-sharded, one 100000 x 2000 block per
@@ -21,7 +29,7 @@ GPU, RCCL) BEFORE it touches the GPU, relays rank 0's JSON line and exits with t
 (WORLD_SIZE set) it is one of the ranks.  NNF_BENCH_BACKEND=gloo runs the ranks over gloo (ranks may then share devices:
 a rehearsal, not a measurement).
 
-The JSON line carries
+With --full the JSON line also carries
   roofline      -- the dominant streaming kernel of the configuration (B/E: nnf_xty_kernel "W^T X"; C: nnf_mu_left_kernel;
                    D: the MTTKRP kernels): algorithmic flops or bytes per launch / mean launch duration, measured live
                    with HIP events recorded by the library on the launch stream right around that kernel;
@@ -54,6 +62,7 @@ CONFIGS = {
     "E": dict(kind="nmf", rule="hals", beta=2, m=1000000, n=4000, r=100, scaling="strong", ref="configs[4]"),
 }
 E_BLOCKS = 8            # config E is generated in 8 row blocks of m/8 rows (per-shard seeds)
+DUMP_BYTES = 60000000   # --dump-outputs: at most this much data in all ranks' files (64 MB with room for the .npy headers)
 
 
 def parse_args(argv=None):
@@ -66,6 +75,11 @@ def parse_args(argv=None):
     ap.add_argument("--beta", type=float, default=None)
     ap.add_argument("--shape", default=None, help="m,n,r override (tests / rehearsals; the line then says so)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: rooflines, CPU baseline, fixed-work / steady-state / nondeterministic "
+                         "legs, extra_configs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the timed path's outputs of its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-fixed", action="store_true", help="skip the fixed-work line (profiling runs)")
     ap.add_argument("--no-extra", action="store_true", help="skip the config-E leg of the default line")
@@ -229,6 +243,39 @@ def cpu_baseline_ntf(T, F, R, its=2):
             "sample": f"{its} iterations of one_ntf_step (hals, alpha=inf) on the full {T.shape} rank-{R} fp32 tensor: the "
                       f"same tensor as the GPU leg, starting from the factors its timed region started from; "
                       f"NumPy/OpenBLAS threads={threads}"}
+
+
+# ---- --dump-outputs --------------------------------------------------------------------------------------------------
+def host_outputs(cx, sharded, replicated):
+    """What the timed path returned after its last step, copied to the host for --dump-outputs.  `sharded`: name -> this
+    rank's row block of a row-sharded output (2-D, rows first); `replicated`: name -> an output every rank holds alike (rank 0
+    keeps it).  Arrays stay float32 / float64 as computed.  Beyond this rank's share of DUMP_BYTES the sharded arrays keep a
+    fixed sample of their rows (one seeded draw: the same rows for every run with the same arguments), their indices under
+    `<name>_rows` (float64, exact).  Returns name -> NumPy array; with N > 1 ranks a sharded name carries `_rank<k>`."""
+    import numpy as np
+    torch = cx.torch
+    out = {k: v.detach().cpu().numpy() for k, v in replicated.items()} if cx.rank == 0 else {}
+    avail = DUMP_BYTES // cx.world - sum(a.nbytes for a in out.values())
+    need = sum(t.numel() * t.element_size() for t in sharded.values())
+    for name, t in sharded.items():
+        key = name if cx.world == 1 else f"{name}_rank{cx.rank}"
+        rows = int(t.shape[0])
+        row_bytes = t.numel() // max(1, rows) * t.element_size()
+        if need <= avail:
+            out[key] = t.detach().cpu().numpy()
+            continue
+        keep = max(1, min(rows, (avail // len(sharded)) // (row_bytes + 8)))
+        idx = np.sort(np.random.RandomState(1234 + cx.rank).choice(rows, keep, replace=False))
+        out[key] = t.index_select(0, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+        out[key + "_rows"] = idx.astype(np.float64)
+    return out
+
+
+def write_outputs(dirname, arrays):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 # ---- the ranks -------------------------------------------------------------------------------------------------------
@@ -600,7 +647,7 @@ def nmf_kernel_rooflines(cx, run, m, n, r, rule, beta, loop_times=None, steps=20
     return out
 
 
-def bench_nmf(cx, args, cfg, steps, warmup, with_cpu, with_fixed, with_kernels, cpu_its=3, steady=False):
+def bench_nmf(cx, args, cfg, steps, warmup, with_cpu, with_fixed, with_kernels, cpu_its=3, steady=False, dump=False):
     torch = cx.torch
     m, n, r, rule = cfg["m"], cfg["n"], cfg["r"], cfg["rule"]
     beta = args.beta if (args.beta is not None and rule == "mu") else cfg["beta"]
@@ -632,6 +679,8 @@ def bench_nmf(cx, args, cfg, steps, warmup, with_cpu, with_fixed, with_kernels, 
     run = NmfRun(cx, X, Ut, V, r, rule, beta)
     probe = ("xty" if rule == "hals" else "mu_left", 1) if (with_kernels and cx.cuda and cx.rank == 0) else None
     dt, cost, start, loop_times = run.measure(warmup, steps, probe=probe)
+    # (before any leg below runs the loop further)
+    outputs = host_outputs(cx, {"U": run.Ut.t()}, {"V": run.V, "cost": torch.tensor([cost], dtype=torch.float64)}) if dump else None
     sweeps = list(run.sweeps)
     if cx.group is not None and os.environ.get("NNF_BENCH_DEBUG"):
         print(f"[rank {cx.rank}] sharded U-side protocol: {run.ws.async_hits} device-side decisions, "
@@ -639,7 +688,7 @@ def bench_nmf(cx, args, cfg, steps, warmup, with_cpu, with_fixed, with_kernels, 
     out = {"value": units * steps / dt, "ms_per_step": 1e3 * dt / steps, "final_cost": cost,
            "inner_sweeps_per_step_last": sweeps[-1] if sweeps else None,
            "inner_sweeps_mean": (sum(sum(x) for x in sweeps) / len(sweeps)) if sweeps and sweeps[0] else None,
-           "rows_per_rank": int(X.shape[0]), "rule": rule, "beta": beta}
+           "rows_per_rank": int(X.shape[0]), "rule": rule, "beta": beta, "outputs": outputs}
     if cx.group is not None:
         from nn_fac_amd import dist as nd
         out["sharded_protocol"] = {
@@ -700,7 +749,7 @@ def bench_nmf(cx, args, cfg, steps, warmup, with_cpu, with_fixed, with_kernels, 
     return out
 
 
-def bench_ntf(cx, args, cfg, steps, warmup, with_cpu, with_kernels, cpu_its=2):
+def bench_ntf(cx, args, cfg, steps, warmup, with_cpu, with_kernels, cpu_its=2, dump=False):
     import math
     torch = cx.torch
     from nn_fac_amd import ntf as ntf_mod
@@ -731,10 +780,12 @@ def bench_ntf(cx, args, cfg, steps, warmup, with_cpu, with_kernels, cpu_its=2):
     # the timed region carries no probe events: at 0.34 ms per iteration the two stream markers of a bracketed launch cost 12 % of the
     # rate (2561 against 2908 iterations/s, same box); the kernels' in-loop launches are bracketed in further passes of the same loop
     dt, cost = cx.timed(lambda: run(steps))
+    outputs = host_outputs(cx, {"F0": Ft[0].t()}, {"F1": Ft[1].t(), "F2": Ft[2].t(),
+                                                   "cost": torch.tensor([cost], dtype=torch.float64)}) if dump else None
     out = {"value": cx.world * steps / dt, "ms_per_step": 1e3 * dt / steps, "final_cost": cost,
            "inner_sweeps_per_step_last": sweeps[-1] if sweeps else None,
            "inner_sweeps_mean": (sum(sum(x) for x in sweeps) / len(sweeps)) if sweeps else None,
-           "rows_per_rank": I, "rule": "hals", "beta": 2,
+           "rows_per_rank": I, "rule": "hals", "beta": 2, "outputs": outputs,
            "cost_evaluation": ("pass over T (nnf_cp3_partial_cost_f32)" if (st.direct_cost or os.environ.get("NNF_COST") == "direct")
                                else "the reference's expression ||T||^2 - 2<F,rhs> + sum f^T cross f on the last mode's operands "
                                     "(nnf_nmf_gram_cost_f32), fp64 inner products, guarded by its own error estimate")}
@@ -802,14 +853,19 @@ def main():
         shape_note = " [--shape override: NOT the BASELINE configuration]"
     world = cx.world
 
+    # a plain run: the headline only; --full: every other leg, less what --no-* switches off
+    with_cpu, with_fixed = args.full and not args.no_cpu, args.full and not args.no_fixed
+    with_kernels, with_extra = args.full and not args.no_kernels, args.full and not args.no_extra
+    dump = args.dump_outputs is not None
     if cfg["kind"] == "nmf":
-        res = bench_nmf(cx, args, cfg, args.steps, args.warmup, not args.no_cpu, not args.no_fixed, not args.no_kernels,
-                        steady=(args.config == "B" and not args.no_fixed and not args.shape))
+        res = bench_nmf(cx, args, cfg, args.steps, args.warmup, with_cpu, with_fixed, with_kernels,
+                        steady=(args.config == "B" and with_fixed and not args.shape), dump=dump)
     else:
-        res = bench_ntf(cx, args, cfg, args.steps, args.warmup, not args.no_cpu, not args.no_kernels)
+        res = bench_ntf(cx, args, cfg, args.steps, args.warmup, with_cpu, with_kernels, dump=dump)
+    outputs = res.pop("outputs")
 
     extra = None
-    if args.config == "B" and not args.no_extra and not args.shape:
+    if args.config == "B" and with_extra and not args.shape:
         # the 1e6 x 4000 rank-100 problem of configs[4] split over these N ranks (strong scaling), a short measurement
         ecfg = dict(CONFIGS["E"])
         if cx.cuda:
@@ -852,11 +908,11 @@ def main():
             xwhat = (f"{'NMF mu beta=1' if name == 'C' else 'NTF hals'} {xcfg['m']}{'x' + str(xcfg['n']) if name == 'C' else '^3'} rank "
                      f"{xcfg['r']} per GPU ({xcfg['ref']} of BASELINE.json), 10 steps after 3 warm-up")
             try:
-                with_x = world == 1 and not args.no_cpu
+                with_x = world == 1 and with_cpu
                 if xcfg["kind"] == "nmf":
-                    x = bench_nmf(cx, args, xcfg, 10, 3, with_x, False, not args.no_kernels, cpu_its=1)
+                    x = bench_nmf(cx, args, xcfg, 10, 3, with_x, False, with_kernels, cpu_its=1)
                 else:
-                    x = bench_ntf(cx, args, xcfg, 10, 3, with_x, not args.no_kernels, cpu_its=1)
+                    x = bench_ntf(cx, args, xcfg, 10, 3, with_x, with_kernels, cpu_its=1)
                 rlx = x.get("rooflines") or []
                 extra[name] = {"workload": xwhat, "iterations_per_s": x["value"], "ms_per_step": x["ms_per_step"], "steps": 10,
                                "warmup": 3, "inner_sweeps_per_step_last": x.get("inner_sweeps_per_step_last"),
@@ -865,6 +921,8 @@ def main():
             except Exception as exc:
                 extra[name] = {"workload": xwhat, "error": f"{type(exc).__name__}: {exc}"[:300]}
 
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     if cx.rank == 0:
         rule, beta = res["rule"], res["beta"]
         what = {"B": "HALS NMF outer iterations/s (100000x2000 rank-50 row blocks per second)",

@@ -314,6 +314,46 @@ def test_bench_spawns_its_own_ranks(config, shape):
     assert out["config"]["parallelism"].startswith("row-sharded x2")
 
 
+@pytest.mark.parametrize("config,shape", [("B", "301,40,6"), ("D", "14,14,3")])
+def test_bench_plain_line_and_dump_outputs(config, shape, tmp_path):
+    """A plain `python bench.py` line carries the headline only (the other legs come with --full), and --dump-outputs writes
+    what the timed path returned after its last step: the same arrays from a plain and a --full run of the same arguments
+    (one rank, CPU engine double, tiny shapes)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, NNF_BENCH_ENGINE="engine_double:OracleEngine",
+               PYTHONPATH=os.pathsep.join([os.path.join(root, "tests"), root, os.environ.get("PYTHONPATH", "")]))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+
+    def run(out, *more):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--config", config, "--shape", shape, "--dump-outputs", str(out), *more], env=env,
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        return json.loads(lines[0])
+
+    plain = run(tmp_path / "plain")
+    full = run(tmp_path / "full", "--full")
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k]
+    assert plain["steps"] == 3 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert "cpu_baseline" not in plain and "cpu_baseline" in full
+    m, n, r = (int(x) for x in shape.split(","))
+    want = {"U": (m, r), "V": (r, n)} if config == "B" else {f"F{k}": (m, r) for k in range(3)}
+    want["cost"] = (1,)
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(f"{k}.npy" for k in want)
+    for k, shp in want.items():
+        a, b = np.load(tmp_path / "plain" / f"{k}.npy"), np.load(tmp_path / "full" / f"{k}.npy")
+        assert a.shape == shp and a.dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a, b)
+    assert float(np.load(tmp_path / "plain" / "cost.npy")[0]) == plain["config"]["final_cost"]
+
+
 def test_run_steps_falls_back_to_chunked_solves_after_a_timeout():
     """nn_fac_amd.nmf.run_steps: a persistent HALS solve that reports a time-out (status word 1: its workgroups were not all
     resident, e.g. a GPU shared with another process) must not kill the factorisation -- everything in flight is dropped, the

@@ -134,7 +134,7 @@ def test_bench_single_rank_rccl_smoke(built_lib):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--shape", "20000,500,20", "--no-cpu", "--no-extra", "--no-fixed"]
+           "--shape", "20000,500,20", "--full", "--no-cpu", "--no-extra", "--no-fixed"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

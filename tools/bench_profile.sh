@@ -9,7 +9,7 @@ WHAT=${2:-all}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_$CFG
 mkdir -p $O
-cd $R && timeout -k 10 500 python bench.py --config $CFG --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-300
+cd $R && timeout -k 10 500 python bench.py --config $CFG --steps 20 --warmup 3 --full > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-300
 cd /tmp && export TMPDIR=/tmp
 # (the loop of the bench line itself: same --steps / --warmup; the legs that follow the timed region are switched off)
 ARGS="--config $CFG --steps 20 --warmup 3 --no-cpu --no-fixed --no-extra --no-kernels"

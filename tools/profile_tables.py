@@ -58,7 +58,7 @@ def find(rows, key):
     return None, None
 
 
-print(f"### Headline lines (`profiles/{tag}_<cfg>_bench_line.json`: `python bench.py --config <cfg> --steps 20 --warmup 3`, one box, one gpurun call)\n")
+print(f"### Headline lines (`profiles/{tag}_<cfg>_bench_line.json`: `python bench.py --config <cfg> --steps 20 --warmup 3 --full`, one box, one session)\n")
 print("| config | iterations/s | ms per iteration | CPU baseline (same inputs, host of the same box) | dominant kernel: in-loop events | of peak |")
 print("|---|---|---|---|---|---|")
 for cfg in "BCDE":
