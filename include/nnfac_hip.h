@@ -232,11 +232,13 @@ int nnf_hals_row_update_f32(nnf_ctx* ctx, const float* UtM, int64_t ldm, const f
 int nnf_hals_row_scale_f32(nnf_ctx* ctx, float* V, int64_t ldv, int64_t ncols, int k, const double* normsq_f64, int64_t ncols_total,
                            void* stream);
 
-/* Columns the register-resident sweep kernel of rank r keeps on this device (one lane per column, all workgroups co-resident).
- * More columns than that: nnf_hals_solve_f32 / nnf_hals_sweeps_f32 stream the factor through HBM once per sweep and
- * nnf_hals_sweeps_f32 refuses `snapshots`; a caller that runs blind chunks of sweeps (the row-sharded protocol of nnls.py:156, or
- * the solve of a 10^6-column factor on one device) splits the columns into blocks of at most this many and adds the blocks'
- * per-sweep sums. */
+/* Columns the sweep kernels of rank r keep resident on this device (all workgroups co-resident).
+ * r <= 128: the register-resident kernel (one lane per column).  More columns than that: nnf_hals_solve_f32 /
+ * nnf_hals_sweeps_f32 stream the factor through HBM once per sweep and nnf_hals_sweeps_f32 refuses `snapshots`; a caller that
+ * runs blind chunks of sweeps (the row-sharded protocol of nnls.py:156, or the solve of a 10^6-column factor on one device)
+ * splits the columns into blocks of at most this many and adds the blocks' per-sweep sums.
+ * r > 128: the generic kernel with the column in global memory, one column per thread -- the most columns a persistent solve
+ * (or sweeps with NNF_HALS_NORMALIZE / NNF_HALS_NONZERO) takes at that rank; blind sweeps without those flags take any number. */
 int nnf_hals_resident_columns(nnf_ctx* ctx, int r, int64_t* columns_out);
 
 /* Row-sharded solve, device-side stopping decision (no host round trip): after `nsweeps` blind sweeps of

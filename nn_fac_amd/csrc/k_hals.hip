@@ -13,7 +13,8 @@
 //   reach the same decision bit for bit; cdna_hip_programming.md Guideline 16, R1 form).  Spins are bounded.
 //   If ncols exceeds the resident thread count the same kernel strides over column sets, re-reading its own
 //   stores (no cross-workgroup hand-off of V is ever needed).
-// Generic path (NORMALIZE / NONZERO, any r): columns in LDS, run-time rank loop, one grid reduction per row.
+// Generic path (NORMALIZE / NONZERO, and every rank above 128): the column in LDS (or, GCOL, in global memory), run-time rank
+// loop, one grid reduction per row.  Which kernel runs a call: the plan (make_plan, below).
 #include "k_hals_common.h"
 #include <cstdlib>
 
@@ -235,6 +236,10 @@ __global__ __launch_bounds__(256) void nnf_hals_sum_sweeps_kernel(const double* 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The plan: which kernel runs a call, on which grid and after which preparation, decided in ONE place from the shape of the
+// call -- the launch (hals_entry) and the capacity queries (nnf_hals_resident_columns, nnf_hals_resid_floats) read the same
+// answer.  It launches nothing and takes no workspace; the occupancy answers it uses are cached per instantiation.
+// ---------------------------------------------------------------------------------------------------------
 static int pick_rp(int r) {
     static const int opts[] = {8, 16, 24, 32, 40, 48, 50, 52, 56, 64, 80, 96, 100, 104, 112, 128};   // 100: config E's rank
     for (int o : opts)
@@ -242,217 +247,291 @@ static int pick_rp(int r) {
     return (r + 7) & ~7;      // above NNF_MAX_RANK: the generic kernel only (its padded Gram has one row per 8)
 }
 
-// workgroups of 256 columns the register-resident lane kernel of padded rank RP keeps on the chip
-static int64_t lane_resident_blocks(nnf_ctx* ctx, int RP) {
-    hals_args q{};
-    q.ncols = -1;
-    int nb = 0, rc;
-    if (RP <= 48) rc = nnf_hals_fast_part0(ctx, RP, q, NNF_HALS_MAX_BLOCKS, &nb, nullptr);
-    else if (RP <= 64) rc = nnf_hals_fast_part1(ctx, RP, q, NNF_HALS_MAX_BLOCKS, &nb, nullptr);
-    else if (RP <= 104) rc = nnf_hals_fast_part2(ctx, RP, q, NNF_HALS_MAX_BLOCKS, &nb, nullptr);
-    else rc = nnf_hals_fast_part3(ctx, RP, q, NNF_HALS_MAX_BLOCKS, &nb, nullptr);
-    return rc == NNF_OK ? nb : 0;
+struct hals_request {
+    int mode;                      // 0: solve (stopping rule on the device)  1: fixed sweep count, per-sweep sums
+    const float* UtM; int64_t ldm;
+    const float* UtU; const float* UtU2; int64_t ldg;   // UtU2: second Gram of a Hadamard pair (NULL: none)
+    float* V; int64_t ldv;
+    const float* Vsrc; int64_t ldvs;                    // separate start values (NULL: V itself)
+    int r; int64_t ncols;
+    int nsweeps, sweep0;           // sweep0: sweeps already run by earlier launches of the same solve
+    double delta; float sparsity; unsigned flags;
+    double* status; double* nodelta;
+    float* snapshots; int64_t snap_stride; int snap_first;
+    const float* resid_in; float* resid_out;
+};
+
+enum hals_layout { HL_WAVE, HL_QUAD, HL_MFMA, HL_LANE_RES, HL_LANE_STREAM, HL_GENERIC_LDS, HL_GENERIC_BIG, HL_GENERIC_GCOL };
+static const char* const hals_layout_name[] = {"wave", "quad", "mfma", "lane-resident", "lane-streaming", "generic-lds",
+                                               "generic-lds-big", "generic-gcol"};
+
+struct hals_plan {
+    int err = NNF_OK;              // else: what the call is refused with
+    hals_layout layout = HL_LANE_RES;
+    int RP = 0, nblocks = 0, per_cu = 0;   // padded rank (lane, mfma, generic); grid; workgroups per CU it relies on
+    int cpw = 0, nw = 0, ch = 0;   // wave: columns per compute wave, compute waves per workgroup; quad: rows per lane
+    size_t lds = 0;                // generic: dynamic LDS bytes
+    bool hadamard = false, copy = false, prep = true;   // launches in front of the sweep
+    bool gs = false;               // lane, mfma: the row-scaled Gram next to the padded one
+    size_t gram_floats = 0, mfma_floats = 0, snap_floats = 0;   // workspace
+};
+
+// The generic kernel: three forms (column in LDS; four lanes per column in LDS, above rank 128; GCOL) per mode
+constexpr size_t HALS_GENERIC_LDS_MAX = (size_t)150 * 1024;   // columns in LDS up to here
+constexpr size_t HALS_GENERIC_SHM_FIXED = 16 + 3 * 2 * 8 + 64;
+typedef decltype(&nnf_hals_generic_kernel<0, false>) hals_generic_fn;
+static hals_generic_fn generic_kernel(int mode, hals_layout l) {
+    static const hals_generic_fn k[2][3] = {
+        {nnf_hals_generic_kernel<0, false, false>, nnf_hals_generic_kernel<0, false, true>, nnf_hals_generic_kernel<0, true, true>},
+        {nnf_hals_generic_kernel<1, false, false>, nnf_hals_generic_kernel<1, false, true>, nnf_hals_generic_kernel<1, true, true>}};
+    return k[mode][l - HL_GENERIC_LDS];
+}
+// Workgroups per CU of one form with `lds` bytes of dynamic LDS -- a function of r (GCOL: fixed), so cached per r.  The form's
+// dynamic LDS limit is raised as far as the largest size asked for.
+static int generic_per_cu(int mode, hals_layout l, int r, size_t lds, int cap) {
+    static int cached[2][3][HALS_GENERIC_LDS_MAX / 128 + 1];   // workgroups per CU + 1 (0: not asked yet)
+    static size_t lds_set[2][3];
+    const hals_generic_fn k = generic_kernel(mode, l);
+    int& c = cached[mode][l - HL_GENERIC_LDS][l == HL_GENERIC_GCOL ? 0 : r];
+    if (c == 0) {
+        if (l != HL_GENERIC_GCOL && lds > lds_set[mode][l - HL_GENERIC_LDS]) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            lds_set[mode][l - HL_GENERIC_LDS] = lds;
+        }
+        int nb = 0;
+        c = hals_per_cu(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 128, lds), nb, cap) + 1;
+    }
+    return c - 1;
 }
 
-// Many columns at ranks 64..100: the push form on the matrix cores (k_hals_mfma.hip); below rank 64 a k-block has too few
-// MFMAs to cover its own gather -> update -> scatter chain (measured: 9.7-10.6 against 9.4-9.6 us per sweep at rank 50).
-static bool hals_mfma_default(int RP, int64_t ncols) {
-    const char* force = getenv("NNF_HALS_FORCE");
-    if (force && (force[0] == 'l' || force[0] == 'q' || force[0] == 'w')) return false;
-    if (!nnf_hals_mfma_supported(RP)) return false;
-    if (force && force[0] == 'm') return true;
-    return RP >= 64 && ncols > 32768;
+static int64_t hals_cap(nnf_ctx* ctx, int per_cu) {   // workgroups that stay resident at per_cu per CU
+    const int64_t c = (int64_t)per_cu * ctx->num_cus;
+    return c < NNF_HALS_MAX_BLOCKS ? c : NNF_HALS_MAX_BLOCKS;
+}
+static bool hals_32bit(int r, int64_t ld, int64_t ncols) {   // the buffer offsets of an r x ncols operand fit 32 bits
+    return (((int64_t)(r - 1) * ld + ncols) * 4) < (int64_t)0x7fff0000;
 }
 
-template <int MODE>
-static int hals_entry(nnf_ctx* ctx, const float* UtM, int64_t ldm, const float* UtU, int64_t ldg, float* V, int64_t ldv,
-                      int r, int64_t ncols, int nsweeps, double delta, float sparsity, unsigned flags, double* status,
-                      double* nodelta_out, hipStream_t st, float* snapshots = nullptr, int64_t snap_stride = 0,
-                      int sweep0 = 0, const float* UtU2 = nullptr, const float* Vsrc = nullptr, int64_t ldvs = 0,
-                      int snap_first = 0, const float* resid_in = nullptr, float* resid_out = nullptr) {
-    if (!ctx || !UtM || !UtU || !V || r < 1 || ncols < 1 || ldm < ncols || ldv < ncols || ldg < r || nsweeps < 0)
+// the padded Gram (RP x RS, RS = RP rounded up to 32) and the RP (1/diag, nz) pairs + the all-live flag, then (64-byte
+// aligned) the row-scaled Gram of the lane kernel
+static size_t hals_gs_off(int RP) { return ((((size_t)RP * (32 * ((RP + 31) / 32)) + 2 * RP + 1) + 15) & ~(size_t)15); }
+
+static hals_plan refuse(hals_plan p, int err) { p.err = err; return p; }
+
+static hals_plan make_plan(nnf_ctx* ctx, const hals_request& q) {
+    hals_plan p;
+    const int r = q.r; const int64_t n = q.ncols;
+    const bool rowsync = (q.flags & (NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) != 0;
+    const bool generic = r > NNF_MAX_RANK || rowsync;
+    const bool sweeps = q.nsweeps > 0;
+    p.RP = pick_rp(r);
+    // NNF_HALS_FORCE pins the layout (tests run every kernel on the same fixtures); its first letter counts:
+    //   l lane only;  q no wave, no mfma, quad beyond 32768 columns;  w no mfma, a solve wave cannot hold is refused;
+    //   m mfma ahead of wave and quad where it covers the padded rank
+    const char* fenv = getenv("NNF_HALS_FORCE");
+    const char force = fenv ? fenv[0] : 0;
+    // many columns at ranks 64..100: the push form on the matrix cores; below rank 64 a k-block has too few MFMAs to cover its
+    // own gather -> update -> scatter chain (measured: 9.7-10.6 against 9.4-9.6 us per sweep at rank 50)
+    const bool mfma = !generic && sweeps && force != 'l' && force != 'q' && force != 'w' && nnf_hals_mfma_supported(p.RP) &&
+                      (force == 'm' || (p.RP >= 64 && n > 32768));
+    const bool pin_mfma = force == 'm' && mfma;
+
+    // few columns, a persistent solve from its first sweep: one wave per column, 1 or 2 columns per compute wave
+    const bool wave_shape = !generic && q.mode == 0 && q.sweep0 == 0;
+    if (wave_shape && force != 'l' && force != 'q' && !pin_mfma) {
+        for (int cpw = 1; cpw <= 2; ++cpw) {
+            int nw = 0;
+            const int need = nnf_hals_wave_grid(n, cpw, &nw);
+            if (need < 1 || need > NNF_HALS_MAX_BLOCKS) continue;
+            const int pc = nnf_hals_wave_per_cu(r, cpw, nw);
+            if (pc < 1) break;
+            if (need <= (int64_t)pc * ctx->num_cus) {
+                p.layout = HL_WAVE, p.cpw = cpw, p.nw = nw, p.nblocks = need, p.per_cu = pc;
+                p.prep = !sweeps;           // (the sweep kernel builds its Gram image itself)
+                p.copy = !sweeps && q.Vsrc != q.V;
+                p.gram_floats = nnf_hals_wave_gram_floats(r);
+                p.snap_floats = nnf_hals_wave_snap_floats(r, n);
+                return p;
+            }
+        }
+    }
+    if (force == 'w' && wave_shape) return refuse(p, NNF_ERR_UNSUPPORTED);
+
+    // few columns (<= 32768: at most two waves per SIMD): four lanes per column, 16 columns per workgroup
+    if (!generic && force != 'l' && !pin_mfma && (n <= 32768 || force == 'q') &&
+        (int64_t)(r + 16) * (q.ldv > q.ldm ? q.ldv : q.ldm) * 4 < (int64_t)0x7fff0000) {
+        const int ch = (r + 3) / 4, pc = nnf_hals_quad_per_cu(ch);
+        const int64_t need = nnf_cdiv(n, 16);
+        if (pc > 0 && need <= hals_cap(ctx, pc)) {
+            p.layout = HL_QUAD, p.ch = ch, p.nblocks = (int)need, p.per_cu = pc;
+            p.copy = !sweeps && q.Vsrc != q.V;   // (the sweep kernel reads the start values and forms the Hadamard Gram itself)
+            p.gram_floats = nnf_hals_quad_gram_floats(r);
+            return p;
+        }
+    }
+
+    // the padded Gram, 1/diag and the barrier words (nnf_hals_prep_kernel) in front of the lane, mfma and generic kernels; the
+    // Hadamard Gram and separate start values come from two small launches -- except that the resident lane kernel reads its
+    // start values itself (once)
+    const int RS = 32 * ((p.RP + 31) / 32);
+    p.gs = !generic && p.RP > 32 && p.RP <= 52;
+    p.gram_floats = hals_gs_off(p.RP) + (p.gs ? (size_t)p.RP * RS : 0);
+    p.hadamard = q.UtU2 != nullptr;
+    const int lane_pc = generic ? 0 : nnf_hals_fast_per_cu(p.RP, true);
+    const bool lane_fits = lane_pc > 0 && nnf_cdiv(n, 256) <= hals_cap(ctx, lane_pc);
+    p.copy = q.Vsrc != q.V && !(!generic && sweeps && lane_fits && hals_32bit(r, q.ldvs, n));
+    if (!sweeps) {   // the prep kernel only (the status defaults of a solve with no sweep to run)
+        p.layout = generic ? HL_GENERIC_LDS : HL_LANE_RES;
+        return p;
+    }
+
+    if (generic) {
+        // one column per thread; when the workgroups exchange (mode 0, or a row-level reduction per row update) all of them are
+        // resident.  The column in LDS (r x 128 floats per workgroup; above rank 128 four lanes per column, r x 32 floats) while
+        // that fits and -- when the workgroups exchange -- all of them stay resident with it; else (ranks above ~1200, or more
+        // columns than that holds) the column stays in global memory (GCOL).  Measured at rank 200
+        // (tools/probes/bigrank_sweep_probe.py): LDS 3-5x faster per sweep.
+        const bool exchanges = q.mode == 0 || rowsync;
+        if (r > NNF_MAX_RANK) {
+            p.layout = HL_GENERIC_BIG;
+            p.lds = (size_t)r * 32 * 4 + HALS_GENERIC_SHM_FIXED;
+            p.per_cu = p.lds <= HALS_GENERIC_LDS_MAX ? generic_per_cu(q.mode, HL_GENERIC_BIG, r, p.lds, 0) : 0;
+            if (p.per_cu < 1 || (exchanges && nnf_cdiv(n, 32) > hals_cap(ctx, p.per_cu))) {
+                p.layout = HL_GENERIC_GCOL;
+                p.lds = HALS_GENERIC_SHM_FIXED;
+                p.per_cu = generic_per_cu(q.mode, HL_GENERIC_GCOL, r, p.lds, 4);
+            }
+        } else {
+            p.layout = HL_GENERIC_LDS;
+            p.lds = (size_t)r * 128 * 4 + HALS_GENERIC_SHM_FIXED;
+            p.per_cu = generic_per_cu(q.mode, HL_GENERIC_LDS, r, p.lds, 4);
+        }
+        if (p.per_cu < 1) return refuse(p, NNF_ERR_LAUNCH);
+        const int64_t grid = nnf_cdiv(n, p.layout == HL_GENERIC_BIG ? 32 : 128);
+        // blind sweeps without row-level reductions exchange nothing: no residency needed (any number of columns)
+        if (grid > (exchanges ? hals_cap(ctx, p.per_cu) : (int64_t)0x7fffffff)) return refuse(p, NNF_ERR_UNSUPPORTED);
+        p.nblocks = (int)grid;
+        return p;
+    }
+
+    if (!hals_32bit(r, q.ldv, n) || !hals_32bit(r, q.ldm, n)) return refuse(p, NNF_ERR_UNSUPPORTED);
+    const int64_t need = nnf_cdiv(n, 256);
+    if (mfma) {   // when every column stays resident; else the lane kernel
+        const int pc = nnf_hals_mfma_per_cu(p.RP);
+        if (pc > 0 && need <= hals_cap(ctx, pc)) {
+            p.layout = HL_MFMA, p.nblocks = (int)need, p.per_cu = pc;
+            p.mfma_floats = nnf_hals_mfma_gram_floats(p.RP);
+            return p;
+        }
+    }
+    if (lane_pc < 1) return refuse(p, NNF_ERR_LAUNCH);
+    if (lane_fits) {
+        p.layout = HL_LANE_RES, p.nblocks = (int)need, p.per_cu = lane_pc;
+        return p;
+    }
+    // more columns than stay resident: the streaming form strides over column sets (no snapshots)
+    if (q.snapshots != nullptr) return refuse(p, NNF_ERR_UNSUPPORTED);
+    p.layout = HL_LANE_STREAM, p.per_cu = nnf_hals_fast_per_cu(p.RP, false);
+    if (p.per_cu < 1) return refuse(p, NNF_ERR_LAUNCH);
+    p.nblocks = (int)hals_cap(ctx, p.per_cu);
+    return p;
+}
+
+// Checks the arguments, makes the plan, takes the workspace, runs the launches in front of the sweep, launches the layout's
+// kernel and, in mode 1, sums the per-workgroup partials of every sweep.
+static int hals_entry(nnf_ctx* ctx, hals_request q, hipStream_t st) {
+    if (!ctx || !q.UtM || !q.UtU || !q.V || q.r < 1 || q.ncols < 1 || q.ldm < q.ncols || q.ldv < q.ncols || q.ldg < q.r || q.nsweeps < 0)
         return NNF_ERR_ARG;
-    if (MODE == 0 && !status) return NNF_ERR_ARG;
-    if (MODE == 1 && !nodelta_out && nsweeps > 0) return NNF_ERR_ARG;
-    if (nsweeps > NNF_HALS_MAX_SWEEPS) return NNF_ERR_UNSUPPORTED;   // (longer solves: chained by the caller)
-    const bool big_rank = r > NNF_MAX_RANK;   // the generic kernel on columns in global memory (no snapshots, no residual state)
-
-    if (flags & ~(NNF_HALS_SPARSITY | NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) return NNF_ERR_ARG;
-    const int RP = pick_rp(r);
-    const float sp = (flags & NNF_HALS_SPARSITY) ? sparsity : 0.f;
-    const int max_blocks = NNF_HALS_MAX_BLOCKS;
-    nnf_ws_cursor cur(ctx);
-    const int RS = 32 * ((RP + 31) / 32);
-    const bool generic = big_rank || (flags & (NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) != 0;
-    // few columns: four lanes per column (k_hals_quad.hip); many: one lane per column (k_hals_fast.hip)
-    // NNF_HALS_FORCE=lane|quad pins the column layout (tests exercise both kernels on the same fixtures)
-    const char* force = getenv("NNF_HALS_FORCE");
-    const bool force_lane = force && force[0] == 'l', force_quad = force && force[0] == 'q', force_wave = force && force[0] == 'w';
-    const bool force_mfma = force && force[0] == 'm';
-    // fewer still (<= 4800, a persistent solve from its first sweep): one wave per column, push form (k_hals_wave.hip)
-    const bool want_mfma = !generic && nsweeps > 0 && hals_mfma_default(RP, ncols);
-    const bool wave = !generic && MODE == 0 && sweep0 == 0 && !force_lane && !force_quad && !(force_mfma && want_mfma) && nsweeps <= NNF_HALS_MAX_SWEEPS &&
-                      nnf_hals_wave_fits(ctx, r, ncols, max_blocks);
-    // NNF_HALS_FORCE=wave: a solve this layout could take but does not fit is refused instead of moving to another layout
-    if (force_wave && !generic && MODE == 0 && sweep0 == 0 && nsweeps <= NNF_HALS_MAX_SWEEPS && !wave) return NNF_ERR_UNSUPPORTED;
-    const bool quad = !wave && !generic && !force_lane && !(force_mfma && want_mfma) && (ncols <= 32768 || force_quad) && (int64_t)(r + 16) * (ldv > ldm ? ldv : ldm) * 4 < (int64_t)0x7fff0000 &&
-                      nnf_hals_quad_fits(ctx, r, ncols, max_blocks);
+    if (q.mode == 0 && !q.status) return NNF_ERR_ARG;
+    if (q.mode == 1 && !q.nodelta && q.nsweeps > 0) return NNF_ERR_ARG;
+    if (q.nsweeps > NNF_HALS_MAX_SWEEPS) return NNF_ERR_UNSUPPORTED;   // (longer solves: chained by the caller)
+    if (q.flags & ~(NNF_HALS_SPARSITY | NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) return NNF_ERR_ARG;
+    if (q.Vsrc == nullptr || q.Vsrc == q.V) { q.Vsrc = q.V; q.ldvs = q.ldv; }
+    const hals_plan p = make_plan(ctx, q);
     if (getenv("NNF_HALS_DEBUG"))
-        fprintf(stderr, "[nnf hals] r=%d ncols=%lld mode=%d sweeps=%d layout=%s\n", r, (long long)ncols, MODE, nsweeps,
-                wave ? "wave" : quad ? "quad" : generic ? "generic" : "lane");
-    const size_t gs_off = (((size_t)RP * RS + 2 * RP + 1) + 15) & ~(size_t)15;   // scaled image, 64-byte aligned
-    const bool want_gs = !generic && RP > 32 && RP <= 52;
-    size_t gfloats = gs_off + (want_gs ? (size_t)RP * RS : 0);
-    if (quad && nnf_hals_quad_gram_floats(r) > gfloats) gfloats = nnf_hals_quad_gram_floats(r);
-    if (wave && nnf_hals_wave_gram_floats(r) > gfloats) gfloats = nnf_hals_wave_gram_floats(r);
-    // many columns, ranks 48..100: the push form on the matrix cores (k_hals_mfma.hip) when every column stays resident
-    const bool try_mfma = want_mfma && !quad && !wave;
-    float* Gm = try_mfma ? (float*)cur.take(nnf_hals_mfma_gram_floats(RP) * 4) : nullptr;
-    if (try_mfma && !Gm) return NNF_ERR_WORKSPACE;
-    float* Gp = (float*)cur.take(gfloats * 4);   // padded Gram, then the (1/diag, nz) pairs (quad: scaled Gram, 1/diag)
-    float* dinv = Gp ? Gp + (size_t)RP * RS : nullptr;
+        fprintf(stderr, "[nnf hals] r=%d ncols=%lld mode=%d sweeps=%d sweep0=%d flags=%u -> %s grid=%d per_cu=%d cpw=%d nw=%d ch=%d lds=%zu "
+                "hadamard=%d copy=%d prep=%d err=%d\n", q.r, (long long)q.ncols, q.mode, q.nsweeps, q.sweep0, q.flags,
+                hals_layout_name[p.layout], p.nblocks, p.per_cu, p.cpw, p.nw, p.ch, p.lds, p.hadamard, p.copy, p.prep, p.err);
+    if (p.err != NNF_OK) return p.err;
+
+    const bool sweeps = q.nsweeps > 0;
+    const int RS = 32 * ((p.RP + 31) / 32);
+    nnf_ws_cursor cur(ctx);
+    float* Gm = p.mfma_floats ? (float*)cur.take(p.mfma_floats * 4) : nullptr;
+    float* Gp = (float*)cur.take(p.gram_floats * 4);   // padded Gram, then the (1/diag, nz) pairs (quad, wave: their own images)
+    float* dinv = Gp ? Gp + (size_t)p.RP * RS : nullptr;
     unsigned* counter = (unsigned*)cur.take(256);
-    double* slots = (double*)cur.take((size_t)2 * max_blocks * 4 * 8);
+    double* slots = (double*)cur.take((size_t)2 * NNF_HALS_MAX_BLOCKS * 4 * 8);
     // tagged granules of the fast paths: the context's dedicated region (never shared with another kernel's scratch)
-    double* sslots = (MODE == 0) ? (double*)ctx->xch : slots;
-    if (MODE == 0 && (size_t)(nsweeps + 2) * max_blocks * 16 > ctx->xch_bytes) return NNF_ERR_WORKSPACE;
-    double* sweep_partials = nullptr;
-    if (MODE == 1) sweep_partials = (double*)cur.take((size_t)(nsweeps > 0 ? nsweeps : 1) * max_blocks * 8);
-    if (!Gp || !dinv || !counter || !slots || !sslots || (MODE == 1 && !sweep_partials))
+    double* sslots = (q.mode == 0) ? (double*)ctx->xch : slots;
+    if (q.mode == 0 && (size_t)(q.nsweeps + 2) * NNF_HALS_MAX_BLOCKS * 16 > ctx->xch_bytes) return NNF_ERR_WORKSPACE;
+    const int pslots = p.nblocks > NNF_HALS_MAX_BLOCKS ? p.nblocks : NNF_HALS_MAX_BLOCKS;   // sweep partials per sweep
+    double* partials = q.mode == 1 ? (double*)cur.take((size_t)(sweeps ? q.nsweeps : 1) * pslots * 8) : nullptr;
+    float* Gh = p.hadamard ? (float*)cur.take((size_t)q.r * q.r * 4) : nullptr;
+    float* snap = p.snap_floats && sweeps ? (float*)cur.take(p.snap_floats * 4) : nullptr;
+    if ((p.mfma_floats && !Gm) || !Gp || !counter || !slots || (q.mode == 1 && !partials) || (p.hadamard && !Gh) ||
+        (p.snap_floats && sweeps && !snap))
         return NNF_ERR_WORKSPACE;
-    if (Vsrc == nullptr || Vsrc == V) { Vsrc = V; ldvs = ldv; }
-    if (!quad && !wave && (UtU2 != nullptr || Vsrc != V)) {
-        // the Hadamard Gram and the separate start values are native to the few-column (quad) kernel -- the shape they were
-        // made for (NTF factors); the other layouts get them from two small element-wise launches
-        if (UtU2 != nullptr) {
-            float* Gh = (float*)cur.take((size_t)r * r * 4);
-            if (!Gh) return NNF_ERR_WORKSPACE;
-            hipLaunchKernelGGL(nnf_hals_hadamard_kernel, dim3((r * r + 255) / 256), dim3(256), 0, st, UtU, UtU2, ldg, r, Gh);
-            NNF_CHECK_LAUNCH();
-            UtU = Gh;
-            ldg = r;
-            UtU2 = nullptr;
-        }
-        // separate start values: the resident lane kernel reads them itself (once); the generic and the streaming kernels
-        // work in place on a copy
-        const bool lane_resident = !generic && nsweeps > 0 && RP > 0 && nnf_cdiv(ncols, 256) <= lane_resident_blocks(ctx, RP) &&
-                                   (((int64_t)(r - 1) * ldvs + ncols) * 4) < (int64_t)0x7fff0000;
-        if (Vsrc != V && !lane_resident) {
-            if (hipMemcpy2DAsync(V, (size_t)ldv * 4, Vsrc, (size_t)ldvs * 4, (size_t)ncols * 4, (size_t)r, hipMemcpyDeviceToDevice,
-                                 st) != hipSuccess)
-                return NNF_ERR_LAUNCH;
-            Vsrc = V;
-            ldvs = ldv;
-        }
-    }
-    if (!quad && !wave) {
-        hipLaunchKernelGGL(nnf_hals_prep_kernel, dim3(RP), dim3(128), 0, st, UtU, ldg, r, RP, Gp, dinv,
-                           want_gs ? Gp + gs_off : (float*)nullptr, counter,
-                           (MODE == 0 && sweep0 == 0) ? status : (double*)nullptr);
+
+    if (p.hadamard) {
+        hipLaunchKernelGGL(nnf_hals_hadamard_kernel, dim3((q.r * q.r + 255) / 256), dim3(256), 0, st, q.UtU, q.UtU2, q.ldg, q.r, Gh);
         NNF_CHECK_LAUNCH();
-        if (nsweeps == 0) return NNF_OK;
+        q.UtU = Gh, q.ldg = q.r, q.UtU2 = nullptr;
     }
+    const bool native = p.layout == HL_WAVE || p.layout == HL_QUAD;   // read the start values themselves: copy after the prep
+    auto copy_start_values = [&]() {
+        const hipError_t e = hipMemcpy2DAsync(q.V, (size_t)q.ldv * 4, q.Vsrc, (size_t)q.ldvs * 4, (size_t)q.ncols * 4, (size_t)q.r,
+                                              hipMemcpyDeviceToDevice, st);
+        q.Vsrc = q.V, q.ldvs = q.ldv;
+        return e == hipSuccess ? NNF_OK : NNF_ERR_LAUNCH;
+    };
+    if (p.copy && !native && copy_start_values() != NNF_OK) return NNF_ERR_LAUNCH;
+    double* const status0 = (q.mode == 0 && q.sweep0 == 0) ? q.status : nullptr;   // the status defaults (a solve's first launch)
+    int rc = NNF_OK;
+    if (p.prep) {
+        if (p.layout == HL_WAVE) rc = nnf_hals_wave_prep(q.UtU, q.UtU2, q.ldg, q.r, Gp, counter, q.status, st);
+        else if (p.layout == HL_QUAD) rc = nnf_hals_quad_prep(q.UtU, q.UtU2, q.ldg, q.r, Gp, counter, status0, st);
+        else {
+            hipLaunchKernelGGL(nnf_hals_prep_kernel, dim3(p.RP), dim3(128), 0, st, q.UtU, q.ldg, q.r, p.RP, Gp, dinv,
+                               p.gs ? Gp + hals_gs_off(p.RP) : (float*)nullptr, counter, status0);
+            NNF_CHECK_LAUNCH();
+        }
+        if (rc != NNF_OK) return rc;
+    }
+    if (p.copy && native && copy_start_values() != NNF_OK) return NNF_ERR_LAUNCH;
+    if (!sweeps) return NNF_OK;
+
     ctx->hals_epoch = (ctx->hals_epoch + 1u) & 0x3fffffu;   // tag = epoch*1024 + sweep stays below 2^32
     if (ctx->hals_epoch == 0u) {   // wrapped (2^22 solves): clear the region so that tags of the previous round cannot match
         if (hipMemsetAsync(ctx->xch, 0, ctx->xch_bytes, st) != hipSuccess) return NNF_ERR_LAUNCH;
         ctx->hals_epoch = 1u;
     }
-    hals_sync sy{counter, slots, sslots, ctx->hals_epoch};
-    int nblocks = 0, rc = NNF_OK;
-    if (wave) {
-        hals_args a{UtM, ldm, nullptr, nullptr, nullptr, V, ldv, r, ncols, nsweeps, delta, sp, MODE, sy, status, sweep_partials,
-                    snapshots, snap_stride, sweep0, Vsrc, ldvs};
-        float* snap = (float*)cur.take(nnf_hals_wave_snap_floats(r, ncols) * 4);
-        if (!snap) return NNF_ERR_WORKSPACE;
-        rc = nnf_hals_wave_run(ctx, UtU, UtU2, ldg, Gp, snap, counter, a, &nblocks, st);
-        if (rc != NNF_OK) return rc;
-        if (nsweeps == 0) return NNF_OK;
-    } else if (quad) {
-        if ((((int64_t)(r - 1) * ldv + ncols) * 4) >= (int64_t)0x7fff0000 || (((int64_t)(r - 1) * ldm + ncols) * 4) >= (int64_t)0x7fff0000)
-            return NNF_ERR_UNSUPPORTED;   // 32-bit buffer offsets
-        hals_args a{UtM, ldm, nullptr, nullptr, nullptr, V, ldv, r, ncols, nsweeps, delta, sp, MODE, sy, status, sweep_partials,
-                    snapshots, snap_stride, sweep0, Vsrc, ldvs};
-        a.snap_first = snap_first;
-        rc = nnf_hals_quad_run(ctx, UtU, UtU2, ldg, Gp, counter, a, &nblocks, st);
-        if (rc != NNF_OK) return rc;
-        if (nsweeps == 0) return NNF_OK;
-    } else if (generic) {
-        // one column per thread, all workgroups resident (row-level grid reductions)
-        // blind sweeps without row-level reductions exchange nothing: no residency needed (any number of columns)
-        const bool exchanges = MODE == 0 || (flags & (NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) != 0;
-        // the column in LDS (r x 128 floats per workgroup) while that fits and -- when the workgroups exchange -- all of them are
-        // resident with it; else (ranks above ~300, or more columns than one LDS-bound workgroup per CU holds) the column stays
-        // in global memory (GCOL).  Measured at rank 200 (tools/probes/bigrank_sweep_probe.py): LDS 3-5x faster per sweep.
-        static const int force_gcol = [] { const char* e = getenv("NNF_HALS_GCOL"); return e ? atoi(e) : 0; }();   // A/B knob
-        const int cw_lds = big_rank ? 32 : 128;            // columns per workgroup with the column in LDS (four lanes per column above rank 128)
-        const size_t shm_lds = (size_t)r * cw_lds * 4 + 16 + 3 * 2 * 8 + 64, shm_g = 16 + 3 * 2 * 8 + 64;
-        bool gcol = big_rank && (force_gcol || shm_lds > (size_t)150 * 1024);
-        int64_t grid = nnf_cdiv(ncols, cw_lds);
-        int nb = 0;
-        hipError_t he = hipSuccess;
-        if (!gcol && big_rank) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_hals_generic_kernel<MODE, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_lds);
-            he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_generic_kernel<MODE, false, true>, 128, shm_lds);
-        } else if (!gcol) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_hals_generic_kernel<MODE, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_lds);
-            he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_generic_kernel<MODE, false>, 128, shm_lds);
-            if (big_rank && (he != hipSuccess || nb < 1 ||
-                             (exchanges && (grid > max_blocks || grid > (int64_t)(nb >= 3 ? nb - 1 : nb) * ctx->num_cus)))) gcol = true;
-        }
-        if (gcol) {
-            grid = nnf_cdiv(ncols, 128);
-            he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_generic_kernel<MODE, true>, 128, shm_g);
-        }
-        if (he != hipSuccess || nb < 1) return NNF_ERR_LAUNCH;
-        const size_t shm = gcol ? shm_g : shm_lds;
-        int bpc = nb >= 3 ? nb - 1 : nb;
-        if (bpc > 4 && !(big_rank && !gcol)) bpc = 4;
-        if ((exchanges && grid > (int64_t)bpc * ctx->num_cus) || grid > (exchanges ? (int64_t)max_blocks : (int64_t)0x7fffffff))
-            return NNF_ERR_UNSUPPORTED;
-        if (!exchanges && MODE == 1 && grid > max_blocks) {   // the per-sweep partial sums: one double per workgroup and sweep
-            sweep_partials = (double*)cur.take((size_t)(nsweeps > 0 ? nsweeps : 1) * (size_t)grid * 8);
-            if (!sweep_partials) return NNF_ERR_WORKSPACE;
-        }
-        nblocks = (int)grid;
-        if (getenv("NNF_HALS_DEBUG")) fprintf(stderr, "[nnf hals] generic: %s, %d workgroups, %d per CU\n", gcol ? "columns in global memory" : "columns in LDS", nblocks, bpc);
-        if (gcol)
-            hipLaunchKernelGGL((nnf_hals_generic_kernel<MODE, true>), dim3(nblocks), dim3(128), shm, st, UtM, ldm, Gp, dinv, RS, V,
-                               ldv, r, ncols, nsweeps, delta, sp, flags, sy, status, sweep_partials, sweep0, snapshots, snap_stride, snap_first);
-        else if (big_rank)
-            hipLaunchKernelGGL((nnf_hals_generic_kernel<MODE, false, true>), dim3(nblocks), dim3(128), shm, st, UtM, ldm, Gp, dinv, RS, V,
-                               ldv, r, ncols, nsweeps, delta, sp, flags, sy, status, sweep_partials, sweep0, snapshots, snap_stride, snap_first);
-        else
-            hipLaunchKernelGGL((nnf_hals_generic_kernel<MODE, false>), dim3(nblocks), dim3(128), shm, st, UtM, ldm, Gp, dinv, RS, V,
-                               ldv, r, ncols, nsweeps, delta, sp, flags, sy, status, sweep_partials, sweep0, snapshots, snap_stride, snap_first);
-        NNF_CHECK_LAUNCH();
-    } else {
-        if ((((int64_t)(r - 1) * ldv + ncols) * 4) >= (int64_t)0x7fff0000 || (((int64_t)(r - 1) * ldm + ncols) * 4) >= (int64_t)0x7fff0000)
-            return NNF_ERR_UNSUPPORTED;   // 32-bit buffer offsets
-        hals_args a{UtM, ldm, Gp, dinv, want_gs ? Gp + gs_off : nullptr, V, ldv, r, ncols, nsweeps, delta, sp, MODE, sy, status,
-                    sweep_partials, snapshots, snap_stride, sweep0, Vsrc, ldvs};
-        a.snap_first = snap_first;
-        a.resid_in = resid_in;
-        a.resid_out = resid_out;
-        nnf_probe(ctx, NNF_PROBE_HALS, 0, st);
-        rc = NNF_ERR_UNSUPPORTED;
-        if (try_mfma) rc = nnf_hals_mfma_run(ctx, RP, UtU, ldg, Gm, a, max_blocks, &nblocks, st);
-        if (rc == NNF_OK) {
-            if (getenv("NNF_HALS_DEBUG")) fprintf(stderr, "[nnf hals] -> mfma kernel, %d workgroups\n", nblocks);
-        } else if (rc != NNF_ERR_UNSUPPORTED) {
-            return rc;
-        } else
-        if (RP <= 48) rc = nnf_hals_fast_part0(ctx, RP, a, max_blocks, &nblocks, st);
-        else if (RP <= 64) rc = nnf_hals_fast_part1(ctx, RP, a, max_blocks, &nblocks, st);
-        else if (RP <= 104) rc = nnf_hals_fast_part2(ctx, RP, a, max_blocks, &nblocks, st);
-        else rc = nnf_hals_fast_part3(ctx, RP, a, max_blocks, &nblocks, st);
-        if (rc != NNF_OK) return rc;
-        nnf_probe(ctx, NNF_PROBE_HALS, 1, st);
+    const hals_sync sy{counter, slots, sslots, ctx->hals_epoch};
+    const float sp = (q.flags & NNF_HALS_SPARSITY) ? q.sparsity : 0.f;
+    hals_args a{q.UtM, q.ldm, Gp, dinv, p.gs ? Gp + hals_gs_off(p.RP) : nullptr, q.V, q.ldv, q.r, q.ncols, q.nsweeps,
+                q.delta, sp, q.mode, sy, q.status, partials, q.snapshots, q.snap_stride, q.sweep0, q.Vsrc, q.ldvs};
+    a.snap_first = q.snap_first, a.resid_in = q.resid_in, a.resid_out = q.resid_out;
+    const bool probed = p.layout < HL_GENERIC_LDS;
+    if (probed) nnf_probe(ctx, NNF_PROBE_HALS, 0, st);
+    switch (p.layout) {
+        case HL_WAVE:   // the kernel builds its image from the Gram(s) itself
+            a.Gp = q.UtU, a.Gs = q.UtU2, a.dinv = nullptr;
+            rc = nnf_hals_wave_launch(p.cpw, p.nw, a, q.ldg, snap, p.nblocks, st);
+            break;
+        case HL_QUAD: rc = nnf_hals_quad_launch(p.ch, a, Gp, p.nblocks, st); break;
+        case HL_MFMA: rc = nnf_hals_mfma_launch(p.RP, q.UtU, q.ldg, Gm, a, p.nblocks, st); break;
+        case HL_LANE_RES:
+        case HL_LANE_STREAM: rc = nnf_hals_fast_launch(p.RP, p.layout == HL_LANE_RES, a, p.nblocks, st); break;
+        default:
+            hipLaunchKernelGGL(generic_kernel(q.mode, p.layout), dim3(p.nblocks), dim3(128), p.lds, st, q.UtM, q.ldm, Gp, dinv, RS, q.V,
+                               q.ldv, q.r, q.ncols, q.nsweeps, q.delta, sp, q.flags, sy, q.status, partials, q.sweep0, q.snapshots,
+                               q.snap_stride, q.snap_first);
+            if (hipGetLastError() != hipSuccess) rc = NNF_ERR_LAUNCH;
     }
-    if (MODE == 1) {
-        hipLaunchKernelGGL(nnf_hals_sum_sweeps_kernel, dim3(nsweeps), dim3(256), 0, st, sweep_partials, nblocks,
-                           nodelta_out);
+    if (rc != NNF_OK) return rc;
+    if (probed) nnf_probe(ctx, NNF_PROBE_HALS, 1, st);
+    if (q.mode == 1) {
+        hipLaunchKernelGGL(nnf_hals_sum_sweeps_kernel, dim3(q.nsweeps), dim3(256), 0, st, partials, p.nblocks, q.nodelta);
         NNF_CHECK_LAUNCH();
     }
     return NNF_OK;
@@ -461,20 +540,15 @@ static int hals_entry(nnf_ctx* ctx, const float* UtM, int64_t ldm, const float* 
 extern "C" int nnf_hals_solve_f32(nnf_ctx* ctx, const float* UtM, int64_t ldm, const float* UtU, int64_t ldg, float* V,
                                   int64_t ldv, int r, int64_t ncols, int max_sweeps, double delta, float sparsity,
                                   unsigned flags, double* status_f64, void* stream) {
-    return hals_entry<0>(ctx, UtM, ldm, UtU, ldg, V, ldv, r, ncols, max_sweeps, delta, sparsity, flags, status_f64,
-                         nullptr, (hipStream_t)stream);
+    return hals_entry(ctx, {0, UtM, ldm, UtU, nullptr, ldg, V, ldv, nullptr, 0, r, ncols, max_sweeps, 0, delta, sparsity, flags, status_f64},
+                      (hipStream_t)stream);
 }
 
 extern "C" int nnf_hals_sweeps_f32(nnf_ctx* ctx, const float* UtM, int64_t ldm, const float* UtU, int64_t ldg, float* V,
                                    int64_t ldv, int r, int64_t ncols, int nsweeps, float sparsity, unsigned flags,
                                    double* nodelta_f64, float* snapshots, int64_t snap_stride, void* stream) {
-    if (snapshots) {
-        // snapshots are written by the resident fast path only
-        if ((flags & (NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) || snap_stride < (int64_t)r * ncols) return NNF_ERR_ARG;
-        // (whether the columns fit the resident kernel is decided where the kernel is picked: launch_rp / the quad path)
-    }
-    return hals_entry<1>(ctx, UtM, ldm, UtU, ldg, V, ldv, r, ncols, nsweeps, 0.0, sparsity, flags, nullptr, nodelta_f64,
-                         (hipStream_t)stream, snapshots, snap_stride);
+    return nnf_hals_sweeps_ex_f32(ctx, UtM, ldm, UtU, ldg, V, ldv, r, ncols, nsweeps, 0, sparsity, flags, nodelta_f64, snapshots,
+                                  snap_stride, 0, nullptr, nullptr, stream);
 }
 
 // Blind sweeps that CONTINUE a solve (the chunks of the row-sharded protocol, dist.py): `sweeps_done` sweeps of this solve
@@ -488,17 +562,18 @@ extern "C" int nnf_hals_sweeps_ex_f32(nnf_ctx* ctx, const float* UtM, int64_t ld
                                       unsigned flags, double* nodelta_f64, float* snapshots, int64_t snap_stride, int snap_first,
                                       const float* resid_in, float* resid_out, void* stream) {
     if (sweeps_done < 0 || snap_first < 0 || (snapshots && snap_first >= nsweeps && nsweeps > 0)) return NNF_ERR_ARG;
+    // snapshots: every layout but the streaming lane kernel writes them (the plan refuses that one); no row-level reductions
     if (snapshots && ((flags & (NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) || snap_stride < (int64_t)r * ncols)) return NNF_ERR_ARG;
-    return hals_entry<1>(ctx, UtM, ldm, UtU, ldg, V, ldv, r, ncols, nsweeps, 0.0, sparsity, flags, nullptr, nodelta_f64,
-                         (hipStream_t)stream, snapshots, snap_stride, sweeps_done, nullptr, nullptr, 0, snap_first, resid_in,
-                         resid_out);
+    return hals_entry(ctx, {1, UtM, ldm, UtU, nullptr, ldg, V, ldv, nullptr, 0, r, ncols, nsweeps, sweeps_done, 0.0, sparsity, flags, nullptr,
+                            nodelta_f64, snapshots, snap_stride, snap_first, resid_in, resid_out}, (hipStream_t)stream);
 }
 
 // floats of residual state per buffer for nnf_hals_sweeps_ex_f32 on an r x ncols factor (0: the layout that runs carries none)
 extern "C" int nnf_hals_resid_floats(nnf_ctx* ctx, int r, int64_t ncols, int64_t* floats_out) {
     if (!ctx || r < 1 || ncols < 1 || !floats_out) return NNF_ERR_ARG;
-    const int RP = pick_rp(r);
-    *floats_out = (RP > 0 && hals_mfma_default(RP, ncols)) ? (int64_t)nnf_hals_mfma_resid_floats(RP, ncols) : 0;
+    // the blind launch of a chunk: it carries state when its plan is the matrix-core kernel
+    const hals_plan p = make_plan(ctx, {1, nullptr, ncols, nullptr, nullptr, r, nullptr, ncols, nullptr, ncols, r, ncols, 1});
+    *floats_out = (p.err == NNF_OK && p.layout == HL_MFMA) ? (int64_t)nnf_hals_mfma_resid_floats(p.RP, ncols) : 0;
     return NNF_OK;
 }
 
@@ -511,8 +586,8 @@ extern "C" int nnf_hals_solve_continue_f32(nnf_ctx* ctx, const float* UtM, int64
                                            float* V, int64_t ldv, int r, int64_t ncols, int sweeps_done, int max_sweeps,
                                            double delta, float sparsity, unsigned flags, double* status_f64, void* stream) {
     if (sweeps_done < 1 || max_sweeps < 1) return NNF_ERR_ARG;
-    return hals_entry<0>(ctx, UtM, ldm, UtU, ldg, V, ldv, r, ncols, max_sweeps, delta, sparsity, flags, status_f64, nullptr,
-                         (hipStream_t)stream, nullptr, 0, sweeps_done);
+    return hals_entry(ctx, {0, UtM, ldm, UtU, nullptr, ldg, V, ldv, nullptr, 0, r, ncols, max_sweeps, sweeps_done, delta, sparsity, flags,
+                            status_f64}, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -567,20 +642,15 @@ __global__ __launch_bounds__(256) void nnf_hals_stop_restore_kernel(const double
 // (the row-sharded protocol, the solve of a 10^6-column factor on one device) split the columns into blocks of this size.
 extern "C" int nnf_hals_resident_columns(nnf_ctx* ctx, int r, int64_t* columns_out) {
     if (!ctx || r < 1 || !columns_out) return NNF_ERR_ARG;
-    const int RP = pick_rp(r);
-    if (r > NNF_MAX_RANK) {   // the generic kernel: four 128-column workgroups per CU
-        *columns_out = (int64_t)4 * ctx->num_cus * 128;
+    if (r > NNF_MAX_RANK) {   // the generic kernel with the column per thread in global memory (GCOL), 128 per workgroup
+        const int pc = generic_per_cu(0, HL_GENERIC_GCOL, r, HALS_GENERIC_SHM_FIXED, 4);
+        if (pc < 1) return NNF_ERR_LAUNCH;
+        *columns_out = hals_cap(ctx, pc) * 128;
         return NNF_OK;
     }
-    hals_args a{};
-    a.ncols = -1;
-    int nblocks = 0, rc;
-    if (RP <= 48) rc = nnf_hals_fast_part0(ctx, RP, a, NNF_HALS_MAX_BLOCKS, &nblocks, nullptr);
-    else if (RP <= 64) rc = nnf_hals_fast_part1(ctx, RP, a, NNF_HALS_MAX_BLOCKS, &nblocks, nullptr);
-    else if (RP <= 104) rc = nnf_hals_fast_part2(ctx, RP, a, NNF_HALS_MAX_BLOCKS, &nblocks, nullptr);
-    else rc = nnf_hals_fast_part3(ctx, RP, a, NNF_HALS_MAX_BLOCKS, &nblocks, nullptr);
-    if (rc != NNF_OK) return rc;
-    *columns_out = (int64_t)nblocks * 256;
+    const int pc = nnf_hals_fast_per_cu(pick_rp(r), true);   // the resident lane kernel, 256 columns per workgroup
+    if (pc < 1) return NNF_ERR_LAUNCH;
+    *columns_out = hals_cap(ctx, pc) * 256;
     return NNF_OK;
 }
 
@@ -611,8 +681,8 @@ extern "C" int nnf_hals_solve_cross_f32(nnf_ctx* ctx, const float* UtM, int64_t 
                                         double* status_f64, void* stream) {
     if (!V_in || ldvi < ncols) return NNF_ERR_ARG;
     if (max_sweeps > NNF_HALS_MAX_SWEEPS) return NNF_ERR_UNSUPPORTED;
-    return hals_entry<0>(ctx, UtM, ldm, UtU_a, ldg, V_out, ldvo, r, ncols, max_sweeps, delta, sparsity, flags, status_f64,
-                         nullptr, (hipStream_t)stream, nullptr, 0, 0, UtU_b, V_in, ldvi);
+    return hals_entry(ctx, {0, UtM, ldm, UtU_a, UtU_b, ldg, V_out, ldvo, V_in, ldvi, r, ncols, max_sweeps, 0, delta, sparsity, flags,
+                            status_f64}, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

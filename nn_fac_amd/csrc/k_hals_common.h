@@ -369,27 +369,41 @@ __device__ __forceinline__ bool hals_take_over(const double* status, int sweep0,
     return true;
 }
 
-int nnf_hals_fast_part0(nnf_ctx*, int RP, const hals_args&, int max_blocks_cap, int* nblocks_out, hipStream_t);
-int nnf_hals_fast_part1(nnf_ctx*, int RP, const hals_args&, int max_blocks_cap, int* nblocks_out, hipStream_t);
-int nnf_hals_fast_part2(nnf_ctx*, int RP, const hals_args&, int max_blocks_cap, int* nblocks_out, hipStream_t);
-int nnf_hals_fast_part3(nnf_ctx*, int RP, const hals_args&, int max_blocks_cap, int* nblocks_out, hipStream_t);
+// Workgroups per CU a persistent launch relies on, from the occupancy API's answer `nb`: one fewer from three up (the API can
+// over-report by one block per CU), then at most `cap` (0: no cap).  0: the kernel does not fit at all.
+static inline int hals_per_cu(hipError_t e, int nb, int cap) {
+    if (e != hipSuccess || nb < 1) return 0;
+    const int b = nb >= 3 ? nb - 1 : nb;
+    return cap > 0 && b > cap ? cap : b;
+}
 
-// k_hals_wave.hip: one wave per column (lane = row), push form of the sweep; solve mode, <= 4800 columns
-bool nnf_hals_wave_fits(nnf_ctx*, int r, int64_t ncols, int max_blocks_cap);
+// Each layout exports a cached "workgroups per CU" query for one instantiation and a launcher that only launches; which
+// layout runs, and with which grid, is decided by the plan in k_hals.hip.
+
+// k_hals_fast.hip: one lane per column, padded rank RP <= 128; `resident`: the columns stay in registers (all workgroups
+// co-resident), else the streaming form strides over column sets.  Lane cap: 3 workgroups per CU.
+int nnf_hals_fast_per_cu(int RP, bool resident);
+int nnf_hals_fast_launch(int RP, bool resident, const hals_args& a, int nblocks, hipStream_t);
+
+// k_hals_wave.hip: one wave per column (lane = row), push form of the sweep; solve mode from the first sweep, r <= 128
+int nnf_hals_wave_grid(int64_t ncols, int cpw, int* nw_out);   // workgroups for cpw columns per compute wave (0: too many)
+int nnf_hals_wave_per_cu(int r, int cpw, int nw);
 size_t nnf_hals_wave_gram_floats(int r);
 size_t nnf_hals_wave_snap_floats(int r, int64_t ncols);
-int nnf_hals_wave_run(nnf_ctx*, const float* UtU, const float* UtU2, int64_t ldg, float* Gw, float* snap, unsigned* counter,
-                      hals_args a, int* nblocks_out, hipStream_t);
+int nnf_hals_wave_prep(const float* UtU, const float* UtU2, int64_t ldg, int r, float* Gw, unsigned* counter, double* status,
+                       hipStream_t);   // status defaults and barrier word of a solve that runs no sweep
+int nnf_hals_wave_launch(int cpw, int nw, const hals_args& a, int64_t ldg, float* snap, int nblocks, hipStream_t);
 
 // k_hals_mfma.hip: push form on the matrix cores, many columns, ranks 48..100 (resident columns only)
 bool nnf_hals_mfma_supported(int RP);
+int nnf_hals_mfma_per_cu(int RP);
 size_t nnf_hals_mfma_gram_floats(int RP);
 size_t nnf_hals_mfma_resid_floats(int RP, int64_t ncols);
-int nnf_hals_mfma_run(nnf_ctx*, int RP, const float* UtU, int64_t ldg, float* gram, hals_args a, int max_blocks_cap, int* nblocks_out,
-                      hipStream_t);
+int nnf_hals_mfma_launch(int RP, const float* UtU, int64_t ldg, float* gram, hals_args a, int nblocks, hipStream_t);   // prep + sweep
 
-// k_hals_quad.hip: four lanes per column, for solves with few columns
-bool nnf_hals_quad_fits(nnf_ctx*, int r, int64_t ncols, int max_blocks_cap);
+// k_hals_quad.hip: four lanes per column, for solves with few columns (16 per workgroup), CH = ceil(r / 4) rows per lane
+int nnf_hals_quad_per_cu(int ch);
 size_t nnf_hals_quad_gram_floats(int r);
-int nnf_hals_quad_run(nnf_ctx*, const float* UtU, const float* UtU2, int64_t ldg, float* Gq, unsigned* counter, hals_args a,
-                      int* nblocks_out, hipStream_t);
+int nnf_hals_quad_prep(const float* UtU, const float* UtU2, int64_t ldg, int r, float* Gq, unsigned* counter, double* status,
+                       hipStream_t);
+int nnf_hals_quad_launch(int ch, hals_args a, float* Gq, int nblocks, hipStream_t);

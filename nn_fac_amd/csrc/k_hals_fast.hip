@@ -403,64 +403,62 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
 }
 
 template <int RP>
-static int launch_rp(nnf_ctx* ctx, const hals_args& a, int max_blocks_cap, int* nblocks_out, hipStream_t st) {
-    static int cached_bpc[2] = {0, 0};
-    auto bpc_of = [&](bool res) -> int {
-        int& c = cached_bpc[res ? 1 : 0];
-        if (c == 0) {
-            int nb = 0;
-            hipError_t e = res ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_kernel<RP, true>, 256, 0)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_kernel<RP, false>, 256, 0);
-            if (e != hipSuccess || nb < 1) return -1;
-            int b = nb >= 3 ? nb - 1 : nb;  // margin: the occupancy API can over-report by one block per CU
-            if (b > 3) b = 3;
-            c = b;
-        }
-        return c;
-    };
-    int bpc = bpc_of(true);
-    if (bpc < 1) return NNF_ERR_LAUNCH;
-    int64_t cap = (int64_t)bpc * ctx->num_cus;
-    if (cap > max_blocks_cap) cap = max_blocks_cap;
-    if (a.ncols < 0) {   // capacity query (nnf_hals_resident_columns): workgroups of 256 columns the resident kernel keeps on the chip
-        *nblocks_out = (int)cap;
-        return NNF_OK;
+static int fast_per_cu(bool res) {
+    static int cached[2] = {-1, -1};
+    int& c = cached[res ? 1 : 0];
+    if (c < 0) {
+        int nb = 0;
+        const hipError_t e = res ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_kernel<RP, true>, 256, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_kernel<RP, false>, 256, 0);
+        c = hals_per_cu(e, nb, 3);
     }
-    const int64_t need = nnf_cdiv(a.ncols, 256);
-    if (need <= cap) {
-        *nblocks_out = (int)need;
-        hipLaunchKernelGGL((nnf_hals_kernel<RP, true>), dim3((int)need), dim3(256), 0, st, a);
-    } else {
-        if (a.snapshots != nullptr) return NNF_ERR_UNSUPPORTED;   // per-sweep snapshots are written by the resident kernel only
-        bpc = bpc_of(false);
-        if (bpc < 1) return NNF_ERR_LAUNCH;
-        cap = (int64_t)bpc * ctx->num_cus;
-        if (cap > max_blocks_cap) cap = max_blocks_cap;
-        *nblocks_out = (int)cap;
-        hipLaunchKernelGGL((nnf_hals_kernel<RP, false>), dim3((int)cap), dim3(256), 0, st, a);
-    }
+    return c;
+}
+
+template <int RP>
+static int fast_launch(bool res, const hals_args& a, int nblocks, hipStream_t st) {
+    if (res) hipLaunchKernelGGL((nnf_hals_kernel<RP, true>), dim3(nblocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((nnf_hals_kernel<RP, false>), dim3(nblocks), dim3(256), 0, st, a);
     NNF_CHECK_LAUNCH();
     return NNF_OK;
 }
 
-#define HALS_CASE(N) \
-    case N:          \
-        return launch_rp<N>(ctx, a, max_blocks_cap, nblocks_out, st);
+// The instantiations are compiled as four translation units (-DHALS_PART=0..3); part 0 also holds the dispatchers.
+#define HALS_CASE(N, FN, ...) \
+    case N:                   \
+        return FN<N>(__VA_ARGS__);
+#if HALS_PART == 0
+#define HALS_CASES(FN, ...) HALS_CASE(8, FN, __VA_ARGS__) HALS_CASE(16, FN, __VA_ARGS__) HALS_CASE(24, FN, __VA_ARGS__) \
+    HALS_CASE(32, FN, __VA_ARGS__) HALS_CASE(40, FN, __VA_ARGS__) HALS_CASE(48, FN, __VA_ARGS__)
+#elif HALS_PART == 1
+#define HALS_CASES(FN, ...) HALS_CASE(50, FN, __VA_ARGS__) HALS_CASE(52, FN, __VA_ARGS__) HALS_CASE(56, FN, __VA_ARGS__) \
+    HALS_CASE(64, FN, __VA_ARGS__)
+#elif HALS_PART == 2
+#define HALS_CASES(FN, ...) HALS_CASE(80, FN, __VA_ARGS__) HALS_CASE(96, FN, __VA_ARGS__) HALS_CASE(100, FN, __VA_ARGS__) \
+    HALS_CASE(104, FN, __VA_ARGS__)
+#else
+#define HALS_CASES(FN, ...) HALS_CASE(112, FN, __VA_ARGS__) HALS_CASE(128, FN, __VA_ARGS__)
+#endif
+int NNF_CAT(nnf_hals_fast_per_cu_part, HALS_PART)(int RP, bool res) {
+    switch (RP) { HALS_CASES(fast_per_cu, res) default: return 0; }
+}
+int NNF_CAT(nnf_hals_fast_launch_part, HALS_PART)(int RP, bool res, const hals_args& a, int nblocks, hipStream_t st) {
+    switch (RP) { HALS_CASES(fast_launch, res, a, nblocks, st) default: return NNF_ERR_UNSUPPORTED; }
+}
 
 #if HALS_PART == 0
-int nnf_hals_fast_part0(nnf_ctx* ctx, int RP, const hals_args& a, int max_blocks_cap, int* nblocks_out, hipStream_t st) {
-    switch (RP) { HALS_CASE(8) HALS_CASE(16) HALS_CASE(24) HALS_CASE(32) HALS_CASE(40) HALS_CASE(48) default: return NNF_ERR_UNSUPPORTED; }
+int nnf_hals_fast_per_cu_part1(int, bool);
+int nnf_hals_fast_per_cu_part2(int, bool);
+int nnf_hals_fast_per_cu_part3(int, bool);
+int nnf_hals_fast_launch_part1(int, bool, const hals_args&, int, hipStream_t);
+int nnf_hals_fast_launch_part2(int, bool, const hals_args&, int, hipStream_t);
+int nnf_hals_fast_launch_part3(int, bool, const hals_args&, int, hipStream_t);
+int nnf_hals_fast_per_cu(int RP, bool res) {
+    return RP <= 48 ? nnf_hals_fast_per_cu_part0(RP, res) : RP <= 64 ? nnf_hals_fast_per_cu_part1(RP, res)
+         : RP <= 104 ? nnf_hals_fast_per_cu_part2(RP, res) : nnf_hals_fast_per_cu_part3(RP, res);
 }
-#elif HALS_PART == 1
-int nnf_hals_fast_part1(nnf_ctx* ctx, int RP, const hals_args& a, int max_blocks_cap, int* nblocks_out, hipStream_t st) {
-    switch (RP) { HALS_CASE(50) HALS_CASE(52) HALS_CASE(56) HALS_CASE(64) default: return NNF_ERR_UNSUPPORTED; }
-}
-#elif HALS_PART == 2
-int nnf_hals_fast_part2(nnf_ctx* ctx, int RP, const hals_args& a, int max_blocks_cap, int* nblocks_out, hipStream_t st) {
-    switch (RP) { HALS_CASE(80) HALS_CASE(96) HALS_CASE(100) HALS_CASE(104) default: return NNF_ERR_UNSUPPORTED; }
-}
-#else
-int nnf_hals_fast_part3(nnf_ctx* ctx, int RP, const hals_args& a, int max_blocks_cap, int* nblocks_out, hipStream_t st) {
-    switch (RP) { HALS_CASE(112) HALS_CASE(128) default: return NNF_ERR_UNSUPPORTED; }
+int nnf_hals_fast_launch(int RP, bool res, const hals_args& a, int nblocks, hipStream_t st) {
+    return RP <= 48 ? nnf_hals_fast_launch_part0(RP, res, a, nblocks, st) : RP <= 64 ? nnf_hals_fast_launch_part1(RP, res, a, nblocks, st)
+         : RP <= 104 ? nnf_hals_fast_launch_part2(RP, res, a, nblocks, st) : nnf_hals_fast_launch_part3(RP, res, a, nblocks, st);
 }
 #endif

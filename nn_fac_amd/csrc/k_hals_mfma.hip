@@ -584,44 +584,45 @@ size_t nnf_hals_mfma_resid_floats(int RP, int64_t ncols) {
 }
 
 template <int RT, int REM, int NKB>
-static int mfma_launch(nnf_ctx* ctx, const hals_args& a, int max_blocks_cap, int* nblocks_out, hipStream_t st) {
-    static int cached = 0;
-    if (cached == 0) {
+static int mfma_per_cu() {
+    static int cached = -1;
+    if (cached < 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_mfma_kernel<RT, REM, NKB>, 256, 0) != hipSuccess || nb < 1) return NNF_ERR_LAUNCH;
-        cached = nb > 2 ? 2 : nb;
+        cached = hals_per_cu(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_mfma_kernel<RT, REM, NKB>, 256, 0), nb, 2);
     }
-    int64_t cap = (int64_t)cached * ctx->num_cus;
-    if (cap > max_blocks_cap) cap = max_blocks_cap;
-    if (a.ncols < 0) { *nblocks_out = (int)cap; return NNF_OK; }
-    const int64_t need = nnf_cdiv(a.ncols, 256);
-    if (need > cap) return NNF_ERR_UNSUPPORTED;
-    *nblocks_out = (int)need;
-    hipLaunchKernelGGL((nnf_hals_mfma_kernel<RT, REM, NKB>), dim3((int)need), dim3(256), 0, st, a);
+    return cached;
+}
+template <int RT, int REM, int NKB>
+static int mfma_launch(const hals_args& a, int nblocks, hipStream_t st) {
+    hipLaunchKernelGGL((nnf_hals_mfma_kernel<RT, REM, NKB>), dim3(nblocks), dim3(256), 0, st, a);
     NNF_CHECK_LAUNCH();
     return NNF_OK;
 }
+#define MFMA_CASES(FN, ...)                                                                                                           \
+    MFMA_CASE(3, 0, 12, FN, __VA_ARGS__) MFMA_CASE(3, 2, 13, FN, __VA_ARGS__) MFMA_CASE(3, 4, 13, FN, __VA_ARGS__)                    \
+    MFMA_CASE(4, 0, 16, FN, __VA_ARGS__) MFMA_CASE(5, 0, 20, FN, __VA_ARGS__) MFMA_CASE(6, 0, 24, FN, __VA_ARGS__)                    \
+    MFMA_CASE(6, 4, 25, FN, __VA_ARGS__)
+#define MFMA_CASE(RT_, REM_, NKB_, FN, ...) \
+    if (s.rt == RT_ && s.rem == REM_ && s.nkb == NKB_) return FN<RT_, REM_, NKB_>(__VA_ARGS__);
 
-// a.ncols < 0: capacity query (workgroups of 256 columns that stay resident).  NNF_ERR_UNSUPPORTED: rank or column count not
-// covered (the caller takes the lane kernel).  `gram` = nnf_hals_mfma_gram_floats(RP) floats of workspace.
-int nnf_hals_mfma_run(nnf_ctx* ctx, int RP, const float* UtU, int64_t ldg, float* gram, hals_args a, int max_blocks_cap, int* nblocks_out,
-                      hipStream_t st) {
+int nnf_hals_mfma_per_cu(int RP) {
+    mfma_shape s;
+    if (!mfma_shape_of(RP, s)) return 0;
+    MFMA_CASES(mfma_per_cu)
+    return 0;
+}
+
+// The Gram image (prep) and the sweep.  `gram` = nnf_hals_mfma_gram_floats(RP) floats of workspace.
+int nnf_hals_mfma_launch(int RP, const float* UtU, int64_t ldg, float* gram, hals_args a, int nblocks, hipStream_t st) {
     mfma_shape s;
     if (!mfma_shape_of(RP, s)) return NNF_ERR_UNSUPPORTED;
-    if (a.ncols >= 0) {
-        const int rtq = (s.rt + 3) / 4;
-        float* img = gram;
-        float* lt = gram + (size_t)s.nkb * rtq * 256;
-        a.Mimg = img;
-        a.Mlt = lt;
-        a.rp = RP;
-        const int total = s.nkb * rtq * 256;
-        hipLaunchKernelGGL(nnf_hals_mfma_prep_kernel, dim3((total + 255) / 256), dim3(256), 0, st, UtU, ldg, a.r, s.rt, s.rem, s.nkb, img, lt);
-        NNF_CHECK_LAUNCH();
-    }
-#define MFMA_CASE(RT_, REM_, NKB_) \
-    if (s.rt == RT_ && s.rem == REM_ && s.nkb == NKB_) return mfma_launch<RT_, REM_, NKB_>(ctx, a, max_blocks_cap, nblocks_out, st);
-    MFMA_CASE(3, 0, 12) MFMA_CASE(3, 2, 13) MFMA_CASE(3, 4, 13) MFMA_CASE(4, 0, 16) MFMA_CASE(5, 0, 20) MFMA_CASE(6, 0, 24) MFMA_CASE(6, 4, 25)
-#undef MFMA_CASE
+    const int total = s.nkb * ((s.rt + 3) / 4) * 256;
+    a.Mimg = gram;
+    a.Mlt = gram + total;
+    a.rp = RP;
+    hipLaunchKernelGGL(nnf_hals_mfma_prep_kernel, dim3((total + 255) / 256), dim3(256), 0, st, UtU, ldg, a.r, s.rt, s.rem, s.nkb, gram,
+                       gram + total);
+    NNF_CHECK_LAUNCH();
+    MFMA_CASES(mfma_launch, a, nblocks, st)
     return NNF_ERR_UNSUPPORTED;
 }

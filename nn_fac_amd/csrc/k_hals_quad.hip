@@ -278,27 +278,22 @@ __global__ __launch_bounds__(64) void nnf_hals_quad_kernel(hals_args a) {
     }
 }
 
-static int quad_ch(int r) { return r <= 128 ? (r + 3) / 4 : 0; }   // rows per lane; 0: not built
 static size_t quad_lds(int ch) { return (size_t)(4 * ch) * (size_t)(4 * ((ch + 3) & ~3)) * 4; }
 
 template <int CH>
-static int quad_cap(nnf_ctx* ctx) {   // workgroups that can be co-resident (all of them must be: persistent kernel)
-    static int cached = 0;
-    if (cached == 0) {
+static int quad_per_cu() {   // workgroups per CU that can be co-resident (all of them must be: persistent kernel)
+    static int cached = -1;
+    if (cached < 0) {
         int nb = 0;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_hals_quad_kernel<CH>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)quad_lds(CH));
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_quad_kernel<CH>, 64, quad_lds(CH)) != hipSuccess || nb < 1)
-            return -1;
-        int b = nb >= 3 ? nb - 1 : nb;   // margin: the occupancy API can over-report by one block per CU
-        if (b > 8) b = 8;
-        cached = b;
+        cached = hals_per_cu(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_quad_kernel<CH>, 64, quad_lds(CH)), nb, 8);
     }
-    return cached * ctx->num_cus;
+    return cached;
 }
 
 // The 32 instantiations are compiled as four translation units (-DQUAD_PART=0..3, like k_hals_fast.hip); each part exports
-// one residency query and one launcher for its range of CH, part 0 also holds the prep kernel's launcher and the host logic.
+// one residency query and one launcher for its range of CH, part 0 also holds the prep kernel's launcher and the dispatchers.
 #define QUAD_CASE(N, FN, ...) \
     case N:                   \
         return FN<N>(__VA_ARGS__);
@@ -336,65 +331,44 @@ static int quad_launch(const hals_args& a, int nblocks, hipStream_t st) {
     NNF_CHECK_LAUNCH();
     return NNF_OK;
 }
-int QUAD_PART_FN(nnf_hals_quad_cap_part)(nnf_ctx* ctx, int ch) {
-    switch (ch) { QUAD_CASES(quad_cap, ctx) default: return -1; }
+int QUAD_PART_FN(nnf_hals_quad_per_cu_part)(int ch) {
+    switch (ch) { QUAD_CASES(quad_per_cu) default: return 0; }
 }
 int QUAD_PART_FN(nnf_hals_quad_launch_part)(int ch, const hals_args& a, int nblocks, hipStream_t st) {
     switch (ch) { QUAD_CASES(quad_launch, a, nblocks, st) default: return NNF_ERR_UNSUPPORTED; }
 }
 
 #if QUAD_PART == 0
-int nnf_hals_quad_cap_part1(nnf_ctx*, int);
-int nnf_hals_quad_cap_part2(nnf_ctx*, int);
-int nnf_hals_quad_cap_part3(nnf_ctx*, int);
+int nnf_hals_quad_per_cu_part1(int);
+int nnf_hals_quad_per_cu_part2(int);
+int nnf_hals_quad_per_cu_part3(int);
 int nnf_hals_quad_launch_part1(int, const hals_args&, int, hipStream_t);
 int nnf_hals_quad_launch_part2(int, const hals_args&, int, hipStream_t);
 int nnf_hals_quad_launch_part3(int, const hals_args&, int, hipStream_t);
-static int quad_cap_dispatch(nnf_ctx* ctx, int ch) {
-    return ch <= 14 ? nnf_hals_quad_cap_part0(ctx, ch) : ch <= 21 ? nnf_hals_quad_cap_part1(ctx, ch)
-         : ch <= 27 ? nnf_hals_quad_cap_part2(ctx, ch) : nnf_hals_quad_cap_part3(ctx, ch);
-}
-
-// Heuristic + residency: the quad kernel wins while its waves stay at <= 2 per SIMD (ncols <= 32768 on 256 CUs).
-bool nnf_hals_quad_fits(nnf_ctx* ctx, int r, int64_t ncols, int max_blocks_cap) {
-    const int ch = quad_ch(r);
-    if (ch == 0) return false;
-    const int64_t need = nnf_cdiv(ncols, 16);
-    if (need > (int64_t)8 * ctx->num_cus || need > max_blocks_cap) return false;
-    const int cap = quad_cap_dispatch(ctx, ch);
-    return cap > 0 && need <= cap;
+int nnf_hals_quad_per_cu(int ch) {
+    return ch <= 14 ? nnf_hals_quad_per_cu_part0(ch) : ch <= 21 ? nnf_hals_quad_per_cu_part1(ch)
+         : ch <= 27 ? nnf_hals_quad_per_cu_part2(ch) : nnf_hals_quad_per_cu_part3(ch);
 }
 
 size_t nnf_hals_quad_gram_floats(int r) {
-    const int ch = quad_ch(r), rq = 4 * ch, rs = 4 * ((ch + 3) & ~3);
+    const int ch = (r + 3) / 4, rq = 4 * ch, rs = 4 * ((ch + 3) & ~3);
     return (size_t)rq * rs + rq;
 }
 
-// Gq: workspace of nnf_hals_quad_gram_floats(r) floats.  a.Gp / a.dinv are set here.
-int nnf_hals_quad_run(nnf_ctx* ctx, const float* UtU, const float* UtU2, int64_t ldg, float* Gq, unsigned* counter, hals_args a,
-                      int* nblocks_out, hipStream_t st) {
-    const int ch = quad_ch(a.r), rq = 4 * ch, rs = 4 * ((ch + 3) & ~3);
-    if (ch == 0) return NNF_ERR_UNSUPPORTED;
-    float* dinvq = Gq + (size_t)rq * rs;
-    hipLaunchKernelGGL(nnf_hals_prep_quad_kernel, dim3(4 * ch), dim3(64), 0, st, UtU, UtU2, ldg, a.r, ch, Gq, dinvq, counter,
-                       (a.mode == 0 && a.sweep0 == 0) ? a.status : (double*)nullptr);
+// Gq: workspace of nnf_hals_quad_gram_floats(r) floats (the row-scaled Gram image, then 1/diag per row)
+int nnf_hals_quad_prep(const float* UtU, const float* UtU2, int64_t ldg, int r, float* Gq, unsigned* counter, double* status,
+                       hipStream_t st) {
+    const int ch = (r + 3) / 4, rq = 4 * ch, rs = 4 * ((ch + 3) & ~3);
+    hipLaunchKernelGGL(nnf_hals_prep_quad_kernel, dim3(rq), dim3(64), 0, st, UtU, UtU2, ldg, r, ch, Gq, Gq + (size_t)rq * rs, counter,
+                       status);
     NNF_CHECK_LAUNCH();
-    if (a.max_sweeps == 0) {
-        // no sweep: the result is the start value (nnls.py:147 returns in_V.copy() when the loop does not run); the other
-        // layouts have made that copy already, this one reads its start values inside the sweep kernel, which is not launched
-        if (a.Vsrc != a.V && hipMemcpy2DAsync(a.V, (size_t)a.ldv * 4, a.Vsrc, (size_t)a.ldvs * 4, (size_t)a.ncols * 4, (size_t)a.r,
-                                               hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return NNF_ERR_LAUNCH;
-        return NNF_OK;
-    }
+    return NNF_OK;
+}
+
+int nnf_hals_quad_launch(int ch, hals_args a, float* Gq, int nblocks, hipStream_t st) {
     a.Gp = Gq;
-    a.dinv = dinvq;
-    const int nblocks = (int)nnf_cdiv(a.ncols, 16);
-    *nblocks_out = nblocks;
-    nnf_probe(ctx, NNF_PROBE_HALS, 0, st);
-    const int rc = ch <= 14 ? nnf_hals_quad_launch_part0(ch, a, nblocks, st) : ch <= 21 ? nnf_hals_quad_launch_part1(ch, a, nblocks, st)
-                 : ch <= 27 ? nnf_hals_quad_launch_part2(ch, a, nblocks, st) : nnf_hals_quad_launch_part3(ch, a, nblocks, st);
-    nnf_probe(ctx, NNF_PROBE_HALS, 1, st);
-    return rc;
+    a.dinv = Gq + (size_t)(4 * ch) * (4 * ((ch + 3) & ~3));
+    return ch <= 14 ? nnf_hals_quad_launch_part0(ch, a, nblocks, st) : ch <= 21 ? nnf_hals_quad_launch_part1(ch, a, nblocks, st)
+         : ch <= 27 ? nnf_hals_quad_launch_part2(ch, a, nblocks, st) : nnf_hals_quad_launch_part3(ch, a, nblocks, st);
 }
 #endif   // QUAD_PART == 0

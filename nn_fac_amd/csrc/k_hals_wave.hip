@@ -489,101 +489,65 @@ __global__ __launch_bounds__(1024) void nnf_hals_wave_kernel(hals_args a, int64_
 static int wave_ru(int r) { return (r + 7) & ~7; }
 static int wave_rl(int r) { return r <= 64 ? 1 : 2; }
 static size_t wave_lds(int r) { return (size_t)wave_ru(r) * 64 * wave_rl(r) * 4 + sizeof(wave_ctl) + 16; }
-static int wave_nw(int64_t ncols) {      // compute waves per workgroup: about one workgroup per CU
-    int nw = (int)nnf_cdiv(ncols, 256);
-    if (nw < 1) nw = 1;
-    if (nw > WAVE_MAX_NW) nw = WAVE_MAX_NW;
-    return nw;
-}
-
 size_t nnf_hals_wave_gram_floats(int r) { return (size_t)wave_ru(r) * 64 * wave_rl(r) + 128; }
 size_t nnf_hals_wave_snap_floats(int r, int64_t ncols) { return (size_t)ncols * WAVE_SNAP * 64 * wave_rl(r); }
 
+// nw compute waves per workgroup (about one workgroup per CU), workgroups for cpw columns per compute wave; 0: more
+// workgroups than the communication waves collect
+int nnf_hals_wave_grid(int64_t ncols, int cpw, int* nw_out) {
+    int nw = (int)nnf_cdiv(ncols, 256);
+    if (nw < 1) nw = 1;
+    if (nw > WAVE_MAX_NW) nw = WAVE_MAX_NW;
+    *nw_out = nw;
+    const int64_t need = nnf_cdiv(ncols, (int64_t)nw * cpw);
+    return need > 64 * WAVE_NP ? 0 : (int)need;
+}
+
 template <int RL, int RU, int CPW>
-static int wave_launch(const hals_args& a, int64_t ldg, float* snap, int nblocks, int nw, size_t lds, hipStream_t st, int* occupancy) {
-    static bool attr = false;
-    if (!attr) {
+static int wave_per_cu(int nw) {
+    static int cached[WAVE_MAX_NW + 1];               // per instance and nw: workgroups per CU + 1 (0 = not asked yet)
+    if (cached[nw] == 0) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_hals_wave_kernel<RL, RU, CPW>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        attr = true;
+        int nb = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_wave_kernel<RL, RU, CPW>, 64 * (nw + WAVE_COMM),
+                                                                           wave_lds(RU));
+        cached[nw] = hals_per_cu(e, nb, 0) + 1;
     }
-    if (occupancy) {
-        static int cached[WAVE_MAX_NW + 1];               // per (RL, RU, CPW) instance and nw: resident workgroups per CU + 1 (0 = not asked yet)
-        if (cached[nw] == 0) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nnf_hals_wave_kernel<RL, RU, CPW>, 64 * (nw + WAVE_COMM), lds) != hipSuccess)
-                nb = 0;
-            cached[nw] = nb + 1;
-        }
-        *occupancy = cached[nw] - 1;
-        return NNF_OK;
-    }
-    hipLaunchKernelGGL((nnf_hals_wave_kernel<RL, RU, CPW>), dim3(nblocks), dim3(64 * (nw + WAVE_COMM)), lds, st, a, ldg, snap);
+    return cached[nw] - 1;
+}
+template <int RL, int RU, int CPW>
+static int wave_launch(int nw, const hals_args& a, int64_t ldg, float* snap, int nblocks, hipStream_t st) {
+    hipLaunchKernelGGL((nnf_hals_wave_kernel<RL, RU, CPW>), dim3(nblocks), dim3(64 * (nw + WAVE_COMM)), wave_lds(RU), st, a, ldg, snap);
     NNF_CHECK_LAUNCH();
     return NNF_OK;
 }
-static int wave_dispatch(int r, int cpw, const hals_args& a, int64_t ldg, float* snap, int nblocks, int nw, hipStream_t st, int* occupancy) {
-    const size_t lds = wave_lds(r);
-    switch (wave_ru(r)) {
-#define WAVE_CASE(N)                                                                                               \
-    case N:                                                                                                        \
-        return cpw == 1 ? wave_launch<(N <= 64 ? 1 : 2), N, 1>(a, ldg, snap, nblocks, nw, lds, st, occupancy)      \
-                        : wave_launch<(N <= 64 ? 1 : 2), N, 2>(a, ldg, snap, nblocks, nw, lds, st, occupancy);
-        WAVE_CASE(8) WAVE_CASE(16) WAVE_CASE(24) WAVE_CASE(32) WAVE_CASE(40) WAVE_CASE(48) WAVE_CASE(56) WAVE_CASE(64)
-        WAVE_CASE(72) WAVE_CASE(80) WAVE_CASE(88) WAVE_CASE(96) WAVE_CASE(104) WAVE_CASE(112) WAVE_CASE(120) WAVE_CASE(128)
-#undef WAVE_CASE
-        default: return NNF_ERR_UNSUPPORTED;
+#define WAVE_CASES(FN, ...)                                                                                                  \
+    switch (wave_ru(r)) {                                                                                                    \
+        WAVE_CASE(8, FN, __VA_ARGS__) WAVE_CASE(16, FN, __VA_ARGS__) WAVE_CASE(24, FN, __VA_ARGS__) WAVE_CASE(32, FN, __VA_ARGS__)     \
+        WAVE_CASE(40, FN, __VA_ARGS__) WAVE_CASE(48, FN, __VA_ARGS__) WAVE_CASE(56, FN, __VA_ARGS__) WAVE_CASE(64, FN, __VA_ARGS__)    \
+        WAVE_CASE(72, FN, __VA_ARGS__) WAVE_CASE(80, FN, __VA_ARGS__) WAVE_CASE(88, FN, __VA_ARGS__) WAVE_CASE(96, FN, __VA_ARGS__)    \
+        WAVE_CASE(104, FN, __VA_ARGS__) WAVE_CASE(112, FN, __VA_ARGS__) WAVE_CASE(120, FN, __VA_ARGS__) WAVE_CASE(128, FN, __VA_ARGS__) \
     }
-}
+#define WAVE_CASE(N, FN, ...) \
+    case N: return cpw == 1 ? FN<(N <= 64 ? 1 : 2), N, 1>(__VA_ARGS__) : FN<(N <= 64 ? 1 : 2), N, 2>(__VA_ARGS__);
 
-// Columns per compute wave with which every workgroup of the persistent kernel is co-resident (1, or 2 when one column per
-// wave would take more workgroups than the chip holds at once: 4000 columns at rank 100); 0: this layout does not fit.
-static int wave_plan(nnf_ctx* ctx, int r, int64_t ncols, int max_blocks_cap) {
-    if (r < 1 || r > 128 || ncols < 1) return 0;
-    const int nw = wave_nw(ncols);
-    const char* pin = getenv("NNF_WAVE_CPW");             // measurement knob (tools/probes/vside_probe.py): start at 2 columns per wave
-    for (int cpw = (pin && pin[0] == '2') ? 2 : 1; cpw <= 2; ++cpw) {
-        const int64_t need = nnf_cdiv(ncols, (int64_t)nw * cpw);
-        if (need > 64 * WAVE_NP || need > max_blocks_cap) continue;
-        int nb = 0;
-        hals_args dummy{};
-        const int rc = wave_dispatch(r, cpw, dummy, 0, nullptr, 0, nw, nullptr, &nb);
-        if (getenv("NNF_HALS_DEBUG"))
-            fprintf(stderr, "[nnf hals wave] r=%d ncols=%lld nw=%d cpw=%d need=%lld occupancy=%d rc=%d lds=%zu\n", r, (long long)ncols,
-                    nw, cpw, (long long)need, nb, rc, wave_lds(r));
-        if (rc != NNF_OK || nb < 1) return 0;
-        const int b = nb >= 3 ? nb - 1 : nb;              // margin: the occupancy API can over-report by one block per CU
-        if (need <= (int64_t)b * ctx->num_cus) return cpw;
-    }
+int nnf_hals_wave_per_cu(int r, int cpw, int nw) {
+    WAVE_CASES(wave_per_cu, nw)
     return 0;
 }
-bool nnf_hals_wave_fits(nnf_ctx* ctx, int r, int64_t ncols, int max_blocks_cap) { return wave_plan(ctx, r, ncols, max_blocks_cap) > 0; }
+int nnf_hals_wave_launch(int cpw, int nw, const hals_args& a, int64_t ldg, float* snap, int nblocks, hipStream_t st) {
+    const int r = a.r;
+    WAVE_CASES(wave_launch, nw, a, ldg, snap, nblocks, st)
+    return NNF_ERR_UNSUPPORTED;
+}
 
-// Gw: workspace of nnf_hals_wave_gram_floats(r) floats, snap: nnf_hals_wave_snap_floats(r, ncols) floats.
-// Solve mode only (a.mode == 0, a.sweep0 == 0).
-int nnf_hals_wave_run(nnf_ctx* ctx, const float* UtU, const float* UtU2, int64_t ldg, float* Gw, float* snap, unsigned* counter,
-                      hals_args a, int* nblocks_out, hipStream_t st) {
-    if (a.max_sweeps == 0) {
-        // nothing to sweep: only the status defaults (the preparation kernel writes them) and V_out := V_in
-        const int ru = wave_ru(a.r), rl = wave_rl(a.r);
-        hipLaunchKernelGGL(nnf_hals_prep_wave_kernel, dim3(ru), dim3(64), 0, st, UtU, UtU2, ldg, a.r, rl, Gw, Gw + (size_t)ru * 64 * rl,
-                           counter, a.status);
-        NNF_CHECK_LAUNCH();
-        if (a.Vsrc != a.V && hipMemcpy2DAsync(a.V, (size_t)a.ldv * 4, a.Vsrc, (size_t)a.ldvs * 4, (size_t)a.ncols * 4, (size_t)a.r,
-                                               hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return NNF_ERR_LAUNCH;
-        return NNF_OK;
-    }
-    a.Gp = UtU;              // the kernel builds its image from the Gram(s) itself
-    a.Gs = UtU2;
-    a.dinv = nullptr;
-    const int cpw = wave_plan(ctx, a.r, a.ncols, NNF_HALS_MAX_BLOCKS);
-    if (cpw < 1) return NNF_ERR_UNSUPPORTED;
-    const int nw = wave_nw(a.ncols);
-    const int nblocks = (int)nnf_cdiv(a.ncols, (int64_t)nw * cpw);
-    *nblocks_out = nblocks;
-    nnf_probe(ctx, NNF_PROBE_HALS, 0, st);
-    const int rc = wave_dispatch(a.r, cpw, a, ldg, snap, nblocks, nw, st, nullptr);
-    nnf_probe(ctx, NNF_PROBE_HALS, 1, st);
-    return rc;
+// status defaults and the barrier word (a solve with no sweep to run); the sweep kernel builds its image from the Gram(s)
+int nnf_hals_wave_prep(const float* UtU, const float* UtU2, int64_t ldg, int r, float* Gw, unsigned* counter, double* status,
+                       hipStream_t st) {
+    const int ru = wave_ru(r), rl = wave_rl(r);
+    hipLaunchKernelGGL(nnf_hals_prep_wave_kernel, dim3(ru), dim3(64), 0, st, UtU, UtU2, ldg, r, rl, Gw, Gw + (size_t)ru * 64 * rl,
+                       counter, status);
+    NNF_CHECK_LAUNCH();
+    return NNF_OK;
 }

@@ -77,7 +77,7 @@ def test_cost_above_rank_128_from_the_workspace_tail_and_without_room(built_lib)
                                                 None), "nnf_frob_resid_f32")
 
 
-@pytest.mark.parametrize("r,ncols", [(200, 500), (129, 3000), (257, 700), (300, 64), (160, 20000)])
+@pytest.mark.parametrize("r,ncols", [(200, 500), (129, 3000), (257, 700), (300, 64), (160, 20000), (200, 100000), (400, 20000)])
 @pytest.mark.parametrize("opts", [{}, {"sparsity_coefficient": 0.05}, {"normalize": True}, {"nonzero": True}])
 def test_hals_above_rank_128_vs_oracle(eng, r, ncols, opts):
     if ncols > 4000 and opts:
@@ -156,6 +156,20 @@ def test_nmf_driver_at_rank_130_random_init(built_lib):
     assert U.shape == (400, 130) and V.shape == (130, 600) and np.all(U >= 0) and np.all(V >= 0)
     assert all(b <= a * (1 + 1e-4) for a, b in zip(costs, costs[1:]))
     want = np.linalg.norm(X.astype(np.float64) - U.astype(np.float64) @ V.astype(np.float64)) ** 2      # nmf.py:452, no sparsity
+    assert abs(costs[-1] - want) <= 1e-3 * want
+
+
+def test_nmf_at_rank_130_with_more_columns_than_the_lds_form_holds(built_lib):
+    """100000 x 2000 at rank 130: the U-side solves have more columns than the column-in-LDS form keeps resident, so they run
+    with the column in global memory (the columns nnf_hals_resident_columns reports for ranks above 128)."""
+    from nn_fac_amd.nmf import nmf
+    g = torch.Generator(device="cuda").manual_seed(6)
+    Xd = torch.rand(100000, 130, device="cuda", generator=g) @ torch.rand(130, 2000, device="cuda", generator=g)
+    X = Xd.cpu().numpy()
+    U, V, costs, _ = nmf(X, 130, init="random", n_iter_max=3, tol=0, update_rule="hals", return_costs=True, deterministic=True)
+    assert U.shape == (100000, 130) and V.shape == (130, 2000) and np.all(U >= 0) and np.all(V >= 0)
+    assert all(b <= a * (1 + 1e-4) for a, b in zip(costs, costs[1:]))
+    want = torch.linalg.norm(Xd.double() - torch.from_numpy(U).cuda().double() @ torch.from_numpy(V).cuda().double()).item() ** 2
     assert abs(costs[-1] - want) <= 1e-3 * want
 
 

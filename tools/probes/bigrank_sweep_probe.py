@@ -1,5 +1,6 @@
-"""Sweeps of the generic kernel above rank 128: the column in LDS (r x 128 floats per workgroup) against the column left in
-global memory (NNF_HALS_GCOL=1), microseconds per blind sweep and per sweep of a persistent solve."""
+"""Sweeps of the generic kernel above rank 128, microseconds per blind sweep and per sweep of a persistent solve, in the
+layout the plan of k_hals.hip picks (the column in LDS, or in global memory where that form does not keep every workgroup
+resident; NNF_HALS_DEBUG=1 prints the plan of every call)."""
 import os
 import sys
 
@@ -19,7 +20,7 @@ for r, n in ((200, 2000), (200, 20000), (130, 30000), (256, 8000), (300, 2000), 
     W = V.clone()
     a.record(); eng.hals_sweeps(M, G, W, 10); b.record(); torch.cuda.synchronize()
     blind = a.elapsed_time(b) * 100
-    line = f"NNF_HALS_GCOL={os.environ.get('NNF_HALS_GCOL', '0')}  rank {r} x {n} columns: {blind:9.1f} us per blind sweep"
+    line = f"rank {r} x {n} columns: {blind:9.1f} us per blind sweep"
     if n <= 131072:
         W = V.clone()
         try:
