@@ -452,9 +452,9 @@ int nnf_small_gemm_launch(const float* A, int64_t lda, int p, int q, const float
                           int64_t ldo, int64_t batch, int64_t bstride, int64_t ostride, hipStream_t st) {
     if ((int64_t)8 * q * 4 > 64 * 1024 || batch > 65535 || nnf_cdiv(p, 8) > 65535) return NNF_ERR_UNSUPPORTED;
     const size_t shm = (size_t)8 * q * 4;
-    if (shm > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_small_gemm_rect_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    if (shm > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_small_gemm_rect_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
+        return NNF_ERR_LAUNCH;
     hipLaunchKernelGGL(nnf_small_gemm_rect_kernel, dim3((unsigned)nnf_cdiv(cols, 256), (unsigned)nnf_cdiv(p, 8), (unsigned)batch),
                        dim3(256), shm, st, A, lda, p, q, B, ldb, cols, out, ldo, bstride, ostride);
     NNF_CHECK_LAUNCH();
@@ -504,12 +504,14 @@ __global__ __launch_bounds__(256) void nnf_deep_kl_apply_kernel(const float* __r
         const double a = hsum[k] - lambda * log((double)WHn[k * ldw + i]);
         double res;
         const double q = a / lambda;
-        const double Lz = log(b) + q - loglam;
+        const double Lb = log(b) + q;
+        const double Lz = Lb - loglam;
         if (!(b > 0.0)) {
             res = 0.0;   // b = 0: numerator 0 (the reference gives 0 / (0 + eps) = 0, then the 1e-12 floor)
-        } else if (q > 709.782712893384 || Lz > 709.782712893384) {
-            // the reference forms exp(a/lambda) and b*exp(.)/lambda in float64 (deep_mu.py:11): beyond log(DBL_MAX) that is
-            // +inf, lambertw(inf) = inf and the quotient is 0 -> the floor.  Kept: results identical to the reference's.
+        } else if (q > 709.782712893384 || Lb > 709.782712893384 || Lz > 709.782712893384) {
+            // the reference forms exp(a/lambda), b*exp(.) and then /lambda in float64 (deep_mu.py:11): once any of the three
+            // passes log(DBL_MAX) it is +inf (for lambda > 1 the product overflows although the quotient would not),
+            // lambertw(inf) = inf and the quotient is 0 -> the floor.  Kept: results identical to the reference's.
             res = 0.0;
         } else {
             const double w = nnf_lambertw_logarg(Lz);

@@ -13,6 +13,9 @@
 //     norm falls below delta times the first one; then the Gram-form reconstruction error.  The core has a few hundred
 //     to a few thousand entries, so the whole loop runs in one workgroup with the core in LDS, in fp64 (the reference's
 //     arithmetic: the 300-step loop is a recurrence, and the error expression cancels to ~1e-8 of its terms).
+#include <cstdio>
+#include <cstdlib>
+
 #include "nnf_internal.h"
 
 // ---------------------------------------------------------------------------------------------------------
@@ -399,12 +402,18 @@ extern "C" int nnf_ntd_core_pg_f32(nnf_ctx* ctx, float* core, const float* MtX, 
     const size_t lim = (size_t)160 * 1024;
     const int threads = S >= 1024 ? 1024 : (S >= 512 ? 512 : 256);
     hipStream_t st = (hipStream_t)stream;
+    // NNF_NTD_DEBUG: one stderr line per call naming the form the selection below takes (tests/test_gpu_ntd.py keys on it)
+    static const bool dbg = getenv("NNF_NTD_DEBUG") != nullptr;
+    auto report = [&](const char* form) {
+        if (dbg) fprintf(stderr, "[nnf ntd] pg d=(%d,%d,%d) S=%lld form=%s\n", d0, d1, d2, (long long)S, form);
+    };
     {   // a few thousand entries and several mode-0 slabs: one workgroup per slab (NNF_NTD_PG_MULTI=0: the one-workgroup form)
         static const bool multi_ok = !(getenv("NNF_NTD_PG_MULTI") && getenv("NNF_NTD_PG_MULTI")[0] == '0');
         const int64_t S1 = (int64_t)d1 * d2;
         const size_t shm = (size_t)(128 + 128 + 16 + 128) * 8 + ((size_t)d1 * ((d1 + 3) & ~3) + (size_t)d2 * ((d2 + 3) & ~3) + 2) * 4 +
                            (size_t)4 * S1 * 8;
         if (multi_ok && S >= 2048 && d0 >= 4 && d0 <= ctx->num_cus && shm <= (size_t)150 * 1024) {
+            report("multi");
             nnf_ws_cursor cur(ctx);
             unsigned* counter = (unsigned*)cur.take(256);
             unsigned long long* Y = (unsigned long long*)cur.take((size_t)2 * S * 8);
@@ -422,6 +431,7 @@ extern "C" int nnf_ntd_core_pg_f32(nnf_ctx* ctx, float* core, const float* MtX, 
     }
     if (fixed + (size_t)4 * S * 8 <= lim) {          // everything in LDS, fp64 storage
         const size_t shm = fixed + (size_t)4 * S * 8;
+        report("lds64");
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_ntd_core_pg_kernel<double>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
             return NNF_ERR_LAUNCH;
@@ -429,12 +439,14 @@ extern "C" int nnf_ntd_core_pg_f32(nnf_ctx* ctx, float* core, const float* MtX, 
                            delta, max_iter, norm_sq, status_f64, (double*)nullptr);
     } else if (fixed + (size_t)4 * S * 4 <= lim) {   // everything in LDS, fp32 storage, fp64 accumulation
         const size_t shm = fixed + (size_t)4 * S * 4;
+        report("lds32");
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_ntd_core_pg_kernel<float>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
             return NNF_ERR_LAUNCH;
         hipLaunchKernelGGL(nnf_ntd_core_pg_kernel<float>, dim3(1), dim3(threads), shm, st, core, MtX, M0, M1, M2, d0, d1, d2, sparse,
                            delta, max_iter, norm_sq, status_f64, (double*)nullptr);
     } else {                                          // core-sized arrays in the context workspace (slow: L2 latency per access)
+        report("ws");
         nnf_ws_cursor cur(ctx);
         double* gbuf = (double*)cur.take((size_t)4 * S * 8);
         if (!gbuf) return NNF_ERR_WORKSPACE;

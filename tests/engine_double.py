@@ -49,11 +49,12 @@ class OracleEngine:
 
     def hals_solve(self, UtM, UtU, V, max_sweeps, delta=0.01, sparsity=None, normalize=False, nonzero=False,
                    status=None):
+        log = []
         Vn, eps, cnt, _ = orc.hals_nnls_acc(UtM.numpy(), UtU.numpy(), V.numpy(), maxiter=max_sweeps, alpha=math.inf,
-                                            delta=delta, sparsity_coefficient=sparsity, normalize=normalize)
+                                            delta=delta, sparsity_coefficient=sparsity, normalize=normalize, sweep_log=log)
         V.copy_(torch.from_numpy(Vn))
         st = status if status is not None else torch.zeros(8, dtype=torch.float64)
-        st[0], st[1], st[3] = float(eps), float(cnt), 0.0
+        st[0], st[1], st[2], st[3] = float(eps), float(cnt), (log[0] if log else 0.0), 0.0     # ST_EPS, ST_CNT, ST_EPS0, ST_ERR
         return st
 
 

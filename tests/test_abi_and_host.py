@@ -179,3 +179,41 @@ def test_streaming_kernels_keep_their_prefetch_ring_in_flight(built_lib):
                 main = [l for l in loops if l["mfma"] >= max(90, 16 * mt + 1)]
                 assert main, (k, loops)
                 assert all(l["vmcnt0"] == 0 for l in main), (k, main)
+
+
+# Parameters of Engine methods the double does not take, each with the reason it may lack them.
+ENGINE_ONLY_PARAMS = {
+    ("gram", "out64"): "the fp64 Gram sums feed the Gram-identity cost, which nmf.py only turns on for the HIP engine",
+    ("mu_left", "cost_out"): "the KL cost fused into the left update (r <= 64) is an Engine-only shortcut; drivers fall back to betadiv",
+}
+
+
+def test_engine_double_keeps_the_engine_signatures():
+    """tests/engine_double.OracleEngine stands in for nn_fac_amd.engine.Engine in the gloo world-size-2 suite and bench.py's
+    multi-rank launch test: every public method it has must exist on Engine with the same parameters (names, order, kinds,
+    defaults) up to ENGINE_ONLY_PARAMS, the class constants both carry must agree, and every method must have a case in the GPU
+    contract table (tests/test_gpu_engine_contract.py) that compares the two on the device."""
+    import inspect
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from engine_double import OracleEngine
+    from nn_fac_amd.engine import Engine
+    from test_gpu_engine_contract import CONTRACT
+    public = [n for n in vars(OracleEngine) if not n.startswith("_")]
+    methods = [n for n in public if callable(getattr(OracleEngine, n))]
+    consts = [n for n in public if n not in methods]
+    assert methods and consts
+    for name in methods:
+        assert callable(getattr(Engine, name, None)), f"Engine has no method {name}"
+        want = [p for p in inspect.signature(getattr(Engine, name)).parameters.values()
+                if (name, p.name) not in ENGINE_ONLY_PARAMS]
+        got = list(inspect.signature(getattr(OracleEngine, name)).parameters.values())
+        assert [(p.name, p.kind, p.default) for p in got] == [(p.name, p.kind, p.default) for p in want], name
+    for (name, param) in ENGINE_ONLY_PARAMS:           # the allow-list names real, current differences only
+        assert param in inspect.signature(getattr(Engine, name)).parameters
+        assert param not in inspect.signature(getattr(OracleEngine, name)).parameters
+    for name in consts:
+        assert getattr(Engine, name, None) == getattr(OracleEngine, name), name
+    missing = sorted(set(methods) - set(CONTRACT))
+    assert not missing, f"OracleEngine methods without a GPU contract case: {missing}"
+    assert all(CONTRACT[m] for m in methods)

@@ -53,11 +53,95 @@ def test_ttm3_all_modes(eng, shape, r):
         assert rel(got, want) < 1e-5
 
 
+# The form nnf_ntd_core_pg_f32 (k_ntd.hip) picks for a core: `multi` (one workgroup per mode-0 slab: S >= 2048, 4 <= d0 <= CUs, its
+# LDS need <= 150 KiB), else one workgroup with the core-sized arrays in LDS as fp64 (`lds64`), in LDS as fp32 with fp64
+# accumulation (`lds32`), or as fp64 in the context workspace (`ws`).  Checked against the library's own report
+# (NNF_NTD_DEBUG) by test_core_update_forms, so a change to the selection cannot quietly empty a case.
+PG_FORMS = {(9, 9, 3): "lds64", (4, 3, 2): "lds64", (1, 5, 1): "lds64", (3, 20, 20): "lds64", (3, 16, 32): "lds64",
+            (3, 24, 32): "lds64",                    # d0 = 3: one below the multi form's slab count
+            (23, 89, 1): "lds64",                    # S = 2047: one below the multi form's size
+            (4, 16, 32): "multi",                    # S = 2048, d0 = 4: both thresholds met exactly
+            (4, 24, 32): "multi", (16, 12, 20): "multi", (20, 20, 20): "multi", (24, 24, 24): "multi", (128, 8, 2): "multi",
+            (2, 48, 64): "lds32", (3, 40, 50): "lds32",
+            (2, 64, 64): "ws", (8, 64, 64): "ws", (2, 128, 128): "ws"}
+
+
+@pytest.fixture(scope="module")
+def pg_forms(built_lib):
+    """{dims: form} as reported by the library for every core of PG_FORMS (one subprocess with NNF_NTD_DEBUG set)."""
+    import re
+    import subprocess
+    code = r"""
+import sys, os, torch
+sys.path.insert(0, os.getcwd())
+from nn_fac_amd.engine import get_engine
+eng = get_engine("cuda:0")
+for d in %r:
+    c = torch.ones(d, device="cuda")
+    eng.ntd_core_pg(c, torch.ones(d, device="cuda"), [torch.eye(n, device="cuda") for n in d], 0.0, 0.01, 0, 1.0)
+    torch.cuda.synchronize()
+print("done")
+""" % (sorted(PG_FORMS),)
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    p = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, NNF_NTD_DEBUG="1"), capture_output=True, text=True,
+                       timeout=300, cwd=root)
+    assert p.returncode == 0 and "done" in p.stdout, p.stderr[-2000:]
+    got = {}
+    for m in re.finditer(r"\[nnf ntd\] pg d=\((\d+),(\d+),(\d+)\) S=\d+ form=(\w+)", p.stderr):
+        got[tuple(int(x) for x in m.groups()[:3])] = m.group(4)
+    return got
+
+
+def test_core_update_forms(pg_forms):
+    """Every core of PG_FORMS takes the form this file says it does, and all four forms are reached."""
+    assert pg_forms == PG_FORMS
+    assert set(pg_forms.values()) == {"multi", "lds64", "lds32", "ws"}
+
+
+def _pg_reference(core0, MtX, M, sparse, delta, max_iter):
+    """ntd.py:592-619 in fp64: returns (core, iterations, step)."""
+    step = 1.0
+    for m_ in M:
+        step *= 1 / np.linalg.svd(m_, compute_uv=False)[0]
+    step = round(step, 6)
+    core, cnt, upd0, upd = core0.copy(), 1, 0, 1
+    while cnt <= max_iter and upd >= delta * upd0:
+        grad = -MtX + orc.multi_mode_dot(core, M) + sparse * np.ones(core.shape)
+        dc = np.minimum(step * grad, core)
+        core = core - dc
+        upd = np.sqrt(np.sum(dc ** 2))
+        if cnt == 1:
+            upd0 = upd
+        cnt += 1
+    return core, cnt - 1, step
+
+
 @pytest.mark.parametrize("dims,sparse,scale", [((9, 9, 3), 0.0, 1.0), ((4, 3, 2), 0.05, 1.0), ((16, 12, 20), 0.0, 0.1),
                                                ((1, 5, 1), 0.0, 1.0),
-                                               ((20, 20, 20), 0.0, 0.1),    # fp32 storage in LDS, fp64 accumulation
-                                               ((24, 24, 24), 0.0, 0.1)])   # does not fit in LDS: workspace path
-def test_core_projected_gradient(eng, dims, sparse, scale):
+                                               ((20, 20, 20), 0.0, 0.1),    # multi (fp64): strict bound
+                                               ((24, 24, 24), 0.0, 0.1)])   # multi (fp64): strict bound
+def test_core_projected_gradient(eng, pg_forms, dims, sparse, scale):
+    _check_core_pg(eng, pg_forms, dims, sparse, scale, 300, 0.01)
+
+
+@pytest.mark.parametrize("dims,sparse,scale,max_iter,delta", [
+    ((3, 20, 20), 0.0, 0.1, 300, 0.01), ((3, 16, 32), 0.0, 0.1, 300, 0.01), ((128, 8, 2), 0.0, 0.1, 300, 0.01),
+    ((3, 24, 32), 0.0, 0.1, 300, 0.01), ((4, 24, 32), 0.0, 0.1, 300, 0.01),       # d0 = 3 | 4 at the multi threshold
+    ((23, 89, 1), 0.0, 0.1, 300, 0.01), ((4, 16, 32), 0.0, 0.1, 300, 0.01),       # S = 2047 | 2048
+    ((2, 48, 64), 0.0, 0.1, 300, 0.01), ((3, 40, 50), 0.0, 0.1, 300, 0.01),       # lds32
+    ((2, 64, 64), 0.0, 0.1, 25, 0.01), ((8, 64, 64), 0.0, 0.1, 25, 0.01), ((2, 128, 128), 0.0, 0.1, 12, 0.01),   # ws
+    ((9, 9, 3), 0.0, 1.0, 0, 0.01), ((9, 9, 3), 0.0, 1.0, 1, 0.01), ((16, 12, 20), 0.0, 0.1, 0, 0.01),
+    ((16, 12, 20), 0.0, 0.1, 1, 0.01), ((2, 48, 64), 0.0, 0.1, 1, 0.01), ((2, 64, 64), 0.0, 0.1, 1, 0.01),
+    ((9, 9, 3), 0.0, 1.0, 40, 0.0), ((20, 20, 20), 0.0, 0.1, 40, 0.0), ((3, 40, 50), 0.0, 0.1, 40, 0.0),   # delta = 0: every step
+    ((9, 9, 3), "median", 1.0, 300, 0.01), ((16, 12, 20), "median", 0.1, 300, 0.01),   # a sparsity that zeroes entries
+    ((3, 40, 50), "median", 0.1, 300, 0.01)])
+def test_core_projected_gradient_forms_and_edges(eng, pg_forms, dims, sparse, scale, max_iter, delta):
+    """Every form of the core update (PG_FORMS), the multi form's thresholds, max_iter 0 / 1, delta = 0 (every step runs) and a
+    sparsity that drives entries to exactly 0 -- same bounds as test_core_projected_gradient."""
+    _check_core_pg(eng, pg_forms, dims, sparse, scale, max_iter, delta)
+
+
+def _check_core_pg(eng, pg_forms, dims, sparse, scale, max_iter, delta):
     rng = np.random.RandomState(sum(dims))
     shape = tuple(5 * d + 3 for d in dims)
     F = [scale * rng.rand(shape[i], dims[i]) for i in range(3)]   # scale keeps the 6-decimal step away from 0
@@ -67,28 +151,75 @@ def test_core_projected_gradient(eng, dims, sparse, scale):
     MtX = orc.multi_mode_dot(T, F, transpose=True).astype(np.float32).astype(np.float64)
     M = [(f.T @ f).astype(np.float32).astype(np.float64) for f in F]
     core0 = rng.rand(*dims).astype(np.float32).astype(np.float64)
-    step = 1.0
-    for m_ in M:
-        step *= 1 / np.linalg.svd(m_, compute_uv=False)[0]
-    step = round(step, 6)
-    core, cnt, upd0, upd = core0.copy(), 1, 0, 1
-    while cnt <= 300 and upd >= 0.01 * upd0:
-        grad = -MtX + orc.multi_mode_dot(core, M) + sparse * np.ones(core.shape)
-        dc = np.minimum(step * grad, core)
-        core = core - dc
-        upd = np.sqrt(np.sum(dc ** 2))
-        if cnt == 1:
-            upd0 = upd
-        cnt += 1
+    zeroing = sparse == "median"
+    if zeroing:
+        sparse = float(np.float32(np.median(MtX)))
+    core, iters, step = _pg_reference(core0, MtX, M, sparse, delta, max_iter)
     nrm2 = float(np.sum(T ** 2))
     want_err = nrm2 - 2 * np.sum(MtX * core) + np.sum(orc.multi_mode_dot(core, M) * core)
     cd = dev(core0)
-    st = eng.ntd_core_pg(cd, dev(MtX), [dev(m_) for m_ in M], sparse, 0.01, 300, nrm2).cpu().numpy()
-    fp32_store = 4500 < core.size < 9500
-    assert abs(int(st[0]) - (cnt - 1)) <= (3 if fp32_store else 0)      # the stop test compares fp32-rounded updates there
+    st = eng.ntd_core_pg(cd, dev(MtX), [dev(m_) for m_ in M], sparse, delta, max_iter, nrm2).cpu().numpy()
+    assert pg_forms[dims] == PG_FORMS[dims]
+    # the fp32-storage form rounds the core to fp32 after every step, so the stop test compares fp32-rounded updates; every
+    # other form keeps the reference's fp64 recurrence
+    fp32_store = pg_forms[dims] == "lds32"
+    assert st[5] == 0.0
+    assert abs(int(st[0]) - iters) <= (3 if fp32_store and delta > 0 else 0)
     assert abs(st[3] - step) <= 1e-12
-    assert rel(cd.cpu().numpy(), core) < (1e-4 if fp32_store else 1e-5)
+    got = cd.cpu().numpy()
+    assert rel(got, core) < (1e-4 if fp32_store else 1e-5)
     assert abs(st[4] - want_err) <= 1e-6 * nrm2
+    if zeroing:
+        zeros = int(np.sum(core == 0))
+        assert zeros >= core.size // 10 and abs(int(np.sum(got == 0)) - zeros) <= core.size // 100, (zeros, int(np.sum(got == 0)))
+
+
+@pytest.mark.parametrize("K", [1, 255, 256, 257])
+@pytest.mark.parametrize("J", [2048, 2049, 5000])
+def test_ttm3_middle_axis_on_both_kernels(eng, J, K):
+    """Mode 1 of nnf_ttm3_f32: the batched small GEMM while J <= 2048 (8 rows of the factor in LDS), nnf_ttm_mid_kernel<16>
+    beyond, at the rank-chunk edges of RC = 16.  Per entry one fp32 FMA chain of length J over positive terms:
+    |out - want| <= (J + 1) u want; and the suite's rel 1e-5 (the chain error grows like sqrt(J) u).  `out` starts as NaN."""
+    I = 3
+    rng = np.random.RandomState(J + K)
+    T = rng.rand(I, J, K).astype(np.float32)
+    Td, T64 = dev(T), T.astype(np.float64)
+    for r in (1, 15, 16, 17, 33, 128):
+        F = rng.rand(r, J).astype(np.float32)
+        out = torch.full((I, r, K), float("nan"), dtype=torch.float32, device="cuda")
+        eng.ttm3(Td, dev(F), 1, out=out)
+        got = out.double().cpu().numpy()
+        want = np.matmul(F.astype(np.float64)[None], T64)            # (I, r, K)
+        assert np.isfinite(got).all(), r
+        assert (np.abs(got - want) <= (J + 1) * 2.0 ** -24 * want).all(), r
+        assert rel(got, want) < 1e-5, r
+
+
+def test_ttm3_limits(eng):
+    """Mode 1 refuses more than 65535 slabs (the slab index is a grid dimension) on both kernels, and ranks above 128; modes 0
+    and 2 take ranks above 128 (the W^T X / X H^T kernels walk the rank in passes).  A refusal leaves `out` untouched."""
+    from nn_fac_amd.utils.errors import EngineError
+    for J in (2, 2049):
+        T = torch.zeros((65536, J, 1), dtype=torch.float32, device="cuda")
+        out = torch.full((65536, 4, 1), 7.0, dtype=torch.float32, device="cuda")
+        with pytest.raises(EngineError):
+            eng.ttm3(T, torch.ones((4, J), device="cuda"), 1, out=out)
+        assert bool((out == 7.0).all())
+        del T
+    rng = np.random.RandomState(1)
+    T = rng.rand(40, 30, 50)
+    for r in (129, 200):
+        for mode in (0, 2):
+            F = rng.rand(T.shape[mode], r)
+            want = orc.mode_dot(T, F.T, mode)
+            got = eng.ttm3(dev(T), dev(F.T.copy()), mode).cpu().numpy()
+            if mode == 2:
+                got = np.moveaxis(got, 0, 2)
+            assert rel(got, want) < 1e-5, (r, mode)
+        out = torch.full((40, r, 50), 7.0, dtype=torch.float32, device="cuda")
+        with pytest.raises(EngineError):
+            eng.ttm3(dev(T), dev(rng.rand(r, 30)), 1, out=out)
+        assert bool((out == 7.0).all())
 
 
 def _small(golden):
@@ -280,7 +411,8 @@ def test_ntd_early_stop_drops_the_speculative_iteration(built_lib, rule, beta):
         assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("shape,ranks", [((9, 8, 7, 6), (3, 2, 3, 2)), ((6, 5, 4, 5, 4), (2, 2, 2, 3, 2)), ((20, 6, 11, 9), (4, 3, 5, 2))])
+@pytest.mark.parametrize("shape,ranks", [((9, 8, 7, 6), (3, 2, 3, 2)), ((6, 5, 4, 5, 4), (2, 2, 2, 3, 2)), ((20, 6, 11, 9), (4, 3, 5, 2)),
+                                         ((5, 2100, 4, 3), (2, 3, 2, 2))])   # mode 1: J = 2100, nnf_ttm_mid_kernel
 @pytest.mark.parametrize("rule,beta", [("hals", 2), ("mu", 1), ("mu", 2)])
 def test_ntd_order_n(built_lib, shape, ranks, rule, beta):
     """Tensors of order 4 and 5 (the reference loops over arbitrary modes, ntd.py:534-557): every mode product is the 3-way
