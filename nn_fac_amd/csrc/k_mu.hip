@@ -174,8 +174,9 @@ static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int
     const int nacc = (BM == BM_GEN) ? 2 : 1;
     int64_t nsplit = (BM == BM_KL ? 2 : 1) * (int64_t)ctx->num_cus / ncb;   // resident 4-wave workgroups per CU
     if (nsplit < 1) nsplit = 1;
+    const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
     const int64_t max_split = nnf_cdiv(m, 64);
-    if (nsplit > max_split) nsplit = max_split;
+    if (nsplit > max_split) { nsplit = max_split; bound = "min_rows"; }
     const int64_t slab_elems = (int64_t)r * ldp;
     double* dvec = (double*)cur.take((size_t)r * 8);
     if (!dvec) return NNF_ERR_WORKSPACE;
@@ -185,14 +186,18 @@ static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int
     }
     const int64_t ws_max = (int64_t)(cur.remaining() / 4) / (slab_elems * nacc);
     if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit > ws_max) nsplit = ws_max;
+    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
     int64_t rps = nnf_rup(nnf_cdiv(m, nsplit), 64);
     while ((rps + 128) * ldx * 4 >= (int64_t)0x7fff0000) {
         if (rps <= 64) return NNF_ERR_UNSUPPORTED;
         rps = nnf_rup(rps / 2, 64);
+        bound = "offset32";
     }
     nsplit = nnf_cdiv(m, rps);
     if (nsplit > ws_max) return NNF_ERR_WORKSPACE;
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] mu_right m=%lld n=%lld r=%d mt=%d rem=%d vec=%d bm=%s nsplit=%lld rps=%lld bound=%s\n", (long long)m,
+                (long long)n, r, MT, REM, (int)VEC, BM == BM_KL ? "KL" : "GEN", (long long)nsplit, (long long)rps, bound);
     float* snum = (float*)cur.take((size_t)nsplit * slab_elems * 4);
     float* sden = nacc == 2 ? (float*)cur.take((size_t)nsplit * slab_elems * 4) : nullptr;
     if (!snum || (nacc == 2 && !sden)) return NNF_ERR_WORKSPACE;
@@ -253,6 +258,11 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
         n_mid = nnf_cdiv(T - 8 * W, 4);
     }
     if (n_hi * 256 + n_mid * 192 + (grid - n_hi - n_mid) * 128 < m) return NNF_ERR_UNSUPPORTED;   // (cannot happen)
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] mu_left m=%lld n=%lld r=%d mt=%d rem=%d vec=%d bm=%s form=%s grid=%lld n_hi=%lld n_mid=%lld\n",
+                (long long)m, (long long)n, r, MT, REM, (int)VEC,
+                BM == BM_KL ? "KL" : BM == BM_KLC ? "KLC" : BM == BM_FROB ? "FROB" : "GEN",
+                T <= 8 * slots ? "small" : n_hi > 0 ? "hi" : "mid", (long long)grid, (long long)n_hi, (long long)n_mid);
     if (BM == BM_FROB || BM == BM_KLC) {
         ex.partial = (double*)cur.take((size_t)grid * 8);
         if (!ex.partial || !cost_out) return NNF_ERR_WORKSPACE;

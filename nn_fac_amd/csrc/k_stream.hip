@@ -300,6 +300,7 @@ static int launch_xty(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
     int64_t target = nnf_xty_wg_per_cu<MT, REM>() * (int64_t)ctx->num_cus / ncb;   // resident workgroups per CU
     if (target < 1) target = 1;
     int64_t nsplit = target;
+    const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
     // a workgroup sums its rows in fp32 (MFMA accumulators); the slabs are added in fp64.  Cap the rows per workgroup: at
     // 1e6 x 4000 rank 100 the plan above is 16 splits of 62500 rows, and an entry of U^T X came out with 9.5e-7 relative rms
     // and a -2.2e-7 MEAN error (tools/probes/accum_error_probe.py) -- enough to take the Gram-identity cost of a HALS iteration
@@ -309,19 +310,20 @@ static int launch_xty(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
     // bound, actual error 1.4e4).  2048 rows: 489 slabs of 1.6 MB there (+10 % traffic on an MFMA-bound pass; fewer if the
     // context workspace is smaller -- the Python engine creates its main context with 1 GiB).
     const int64_t ROWS_CAP = 2048;
-    if (nsplit < nnf_cdiv(m, ROWS_CAP)) nsplit = nnf_cdiv(m, ROWS_CAP);
+    if (nsplit < nnf_cdiv(m, ROWS_CAP)) { nsplit = nnf_cdiv(m, ROWS_CAP); bound = "rows_cap"; }
     const int64_t max_split = nnf_cdiv(m, 64);
-    if (nsplit > max_split) nsplit = max_split;
+    if (nsplit > max_split) { nsplit = max_split; bound = "min_rows"; }
     // workspace bound
     const int64_t slab_elems = (int64_t)r * ldp;
     const int64_t ws_max = (int64_t)(cur.remaining() / 4) / slab_elems;
     if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit > ws_max) nsplit = ws_max;
+    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
     int64_t rows_per_split = nnf_rup(nnf_cdiv(m, nsplit), 64);
     // 32-bit buffer offsets inside one split
     while ((rows_per_split + 128) * ldx * 4 >= (int64_t)0x7fff0000) {
         if (rows_per_split <= 64) return NNF_ERR_UNSUPPORTED;
         rows_per_split = nnf_rup(rows_per_split / 2, 64);
+        bound = "offset32";
     }
     nsplit = nnf_cdiv(m, rows_per_split);
     if (nsplit > ws_max) return NNF_ERR_WORKSPACE;
@@ -329,6 +331,9 @@ static int launch_xty(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
     if (!slabs) return NNF_ERR_WORKSPACE;
     const int a_vec_ok = ((((uintptr_t)Ut) & 15) == 0 && (ldu & 3) == 0) ? 1 : 0;
     const int grid = 8 * (int)nnf_cdiv(nsplit, 8) * ncb;
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] xty m=%lld n=%lld r=%d mt=%d rem=%d vec=%d nsplit=%lld rows_per_split=%lld bound=%s grid=%d\n",
+                (long long)m, (long long)n, r, MT, REM, (int)VEC, (long long)nsplit, (long long)rows_per_split, bound, grid);
     nnf_probe(ctx, NNF_PROBE_XTY, 0, st);   // measurement hook: the main kernel alone (bench.py)
     hipLaunchKernelGGL((nnf_xty_kernel<MT, REM, VEC>), dim3(grid), dim3(256), 0, st, X, m, n, ldx, Ut, ldu, r, slabs, ldp, ncb,
                        (int)nsplit, rows_per_split, a_vec_ok);
@@ -521,13 +526,17 @@ static int launch_xht(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
     // NNF_XHT_NT2=0 / 1 forces either form (A/B on one box).
     static const int nt2 = [] { const char* e = getenv("NNF_XHT_NT2"); return e ? atoi(e) : -1; }();
     const bool two_tiles = MT + (REM > 0) > 4 && T > 4 * waves && (nt2 >= 0 ? nt2 != 0 : (MT + (REM > 0) >= 6 && T > 14 * waves));
+    const char* form;   // (NNF_PLAN_DEBUG)
     if (two_tiles) {
+        form = "two_tiles";
         nth = 2;
         n_hi = grid = nnf_cdiv(m, 128);
     } else if (T > 4 * waves) {            // several rounds: 256-row workgroups
+        form = "rounds";
         n_hi = grid = nnf_cdiv(m, 256);
     } else if (T > 2 * waves) {     // one round: (4,3) or (3,2) tiles per wave
         nth = T > 3 * waves ? 4 : 3;
+        form = nth == 4 ? "round43" : "round32";
         n_hi = nnf_cdiv(T - 4 * (nth - 1) * slots, 4);
         grid = slots;
         // few tiles beyond a whole round of nth - 1 per wave (config B: 106 beyond 6144): every workgroup stays at nth - 1 and the
@@ -550,11 +559,16 @@ static int launch_xht(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
             }
         }
     } else {                        // small: 128-row workgroups
+        form = "small";
         nth = 3;
         n_hi = 0;
         grid = nnf_cdiv(m, 128);
     }
     if (n_hi * 64 * nth + (grid - n_hi) * 64 * (nth - 1) + 16 * (int64_t)tail_tiles < m) return NNF_ERR_UNSUPPORTED;   // (cannot happen: the split covers m by construction)
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] xht m=%lld n=%lld r=%d mt=%d rem=%d vec=%d form=%s nth=%d n_hi=%lld grid=%lld tail_parts=%d "
+                        "tail_tiles=%d tail_cpp=%d\n", (long long)m, (long long)n, r, MT, REM, (int)VEC, form, nth, (long long)n_hi,
+                (long long)grid, tail_parts, tail_parts ? tail_tiles : 0, tail_parts ? tail_cpp : 0);
     nnf_probe(ctx, NNF_PROBE_XHT, 0, st);
     if (nth == 4)
         hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, 4>), dim3((int)grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo,
@@ -748,6 +762,8 @@ static int launch_gram(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* A, int r, 
                        hipStream_t st, double* G64) {
     if constexpr (MT <= 4) {
         if (K <= 1024 && (K & 3) == 0 && ldg == r && ((((uintptr_t)A) & 15) == 0) && (lda & 3) == 0) {
+            if (nnf_plan_debug())
+                fprintf(stderr, "[nnf plan] gram r=%d K=%lld form=small nsplit=1 kps=%lld bound=none\n", r, (long long)K, (long long)K);
             const int rc = launch_gram_small<MT>(A, r, K, lda, G, st);
             return rc != NNF_OK ? rc : launch_gram_widen(G, ldg, r, G64, st);
         }
@@ -758,23 +774,30 @@ static int launch_gram(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* A, int r, 
     // 50 x 100000 factor was 7 dependent round trips = 15.7 us in front of W^T X; two resident workgroups per CU halve the
     // chain and overlap each other's waits)
     int64_t nsplit = ctx->num_cus > 8 ? 2 * (int64_t)ctx->num_cus : 8;
+    const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
     const int64_t max_split = nnf_cdiv(K, 64);
-    if (nsplit > max_split) nsplit = max_split;
+    if (nsplit > max_split) { nsplit = max_split; bound = "min_cols"; }
     if (nsplit < 1) nsplit = 1;
     // short factors (the I_mode x R factors of NTF / NTD, K <= 1024): one workgroup, no split, written straight into G -- the
     // whole Gram is a few microseconds of work and the slab reduction would be a second launch of the same length
-    if (K <= 1024 && ldg == r) nsplit = 1;
+    if (K <= 1024 && ldg == r) { nsplit = 1; bound = "short"; }
     // keep the fp32 chain inside a split short (<= 512 columns; r*r*4 bytes of slab each): what the chains leave is all the error
     // the fp64 copy of the sums has (nnf_gram_f64_f32).  The same plan with and without the copy: the fp32 Gram does not depend
     // on which entry point formed it.
+    // (a workspace without room for one slab is refused, as in launch_gram_blocks, rather than run as one chain over all of K)
     if (nsplit > 1 && nsplit < nnf_cdiv(K, 512)) {
         nsplit = nnf_cdiv(K, 512);
+        bound = "chain512";
         const int64_t ws_max = (int64_t)(cur.remaining() / 4) / ((int64_t)r * r);
-        if (nsplit > ws_max) nsplit = ws_max > 0 ? ws_max : 1;
+        if (ws_max < 1) return NNF_ERR_WORKSPACE;
+        if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
     }
     const int64_t kps = nnf_rup(nnf_cdiv(K, nsplit), 64);
     nsplit = nnf_cdiv(K, kps);
     const int a_vec_ok = ((((uintptr_t)A) & 15) == 0 && (lda & 3) == 0) ? 1 : 0;
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] gram r=%d K=%lld form=%s nsplit=%lld kps=%lld bound=%s\n", r, (long long)K,
+                nsplit == 1 && ldg == r ? "single" : "slabs", (long long)nsplit, (long long)kps, bound);
     if (nsplit == 1 && ldg == r) {
         hipLaunchKernelGGL((nnf_gram_kernel<MT>), dim3(1), dim3(256), 0, st, A, r, K, lda, G, kps, a_vec_ok);
         NNF_CHECK_LAUNCH();
@@ -848,16 +871,20 @@ static int launch_gram_blocks(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* A, 
     const int nb = (r + 63) / 64;
     // splits: about two workgroups per CU over all block pairs, 64-column chunks, as many slabs as the workspace holds
     int64_t nsplit = nnf_cdiv((int64_t)2 * ctx->num_cus, (int64_t)nb * nb);
+    const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
     const int64_t max_split = nnf_cdiv(K, 64);
-    if (nsplit > max_split) nsplit = max_split;
+    if (nsplit > max_split) { nsplit = max_split; bound = "min_cols"; }
     const int64_t ws_max = (int64_t)(cur.remaining() / 4) / ((int64_t)r * r);
     if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit < nnf_cdiv(K, 512)) nsplit = nnf_cdiv(K, 512);   // (short fp32 chains, as in launch_gram)
-    if (nsplit > ws_max) nsplit = ws_max;
+    if (nsplit < nnf_cdiv(K, 512)) { nsplit = nnf_cdiv(K, 512); bound = "chain512"; }   // (short fp32 chains, as in launch_gram)
+    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
     if (nsplit < 1) nsplit = 1;
     const int64_t kps = nnf_rup(nnf_cdiv(K, nsplit), 64);
     nsplit = nnf_cdiv(K, kps);
     const int a_vec_ok = ((((uintptr_t)A) & 15) == 0 && (lda & 3) == 0) ? 1 : 0;
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] gram r=%d K=%lld form=blocks nsplit=%lld kps=%lld bound=%s\n", r, (long long)K, (long long)nsplit,
+                (long long)kps, bound);
     float* slabs = (float*)cur.take((size_t)nsplit * r * r * 4);
     if (!slabs) return NNF_ERR_WORKSPACE;
     hipLaunchKernelGGL(nnf_gram_blocks_kernel, dim3((int)nsplit, nb * nb), dim3(256), 0, st, A, r, K, lda, slabs, kps, a_vec_ok, nb);
@@ -1410,6 +1437,13 @@ static int launch_cost(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64
         hipLaunchKernelGGL((nnf_cost_kernel<OP, VV, NN, PP>), dim3(grid, csplit), dim3(256), shm, st, X, m, n, ldx, Ut, ldu, Vf, r, \
                            beta, partial, Ub, ldub, nbu, R1, R2, ldr, u_vec_ok, vdb, Pin);                                   \
     } while (0)
+    if (nnf_plan_debug()) {
+        static const char* const ops[] = {"frob", "kl", "is", "gen", "ratio_kl", "ratio_gen", "prod"};
+        const bool vv = Pin != nullptr ? x_vec_ok(X, ldx) && ldr >= n && x_vec_ok(Pin, ldr) : x_vec_ok(X, ldx);
+        const int nn = (Pin != nullptr || OP == NNF_PROD || KS > 16) ? 8 : 4;
+        fprintf(stderr, "[nnf plan] cost m=%lld n=%lld r=%d op=%s grid=%d csplit=%d NN=%d vdb=%d VEC=%d pin=%d\n", (long long)m,
+                (long long)n, r, ops[OP], grid, csplit, nn, vdb, (int)vv, (int)(Pin != nullptr));
+    }
     nnf_probe(ctx, NNF_PROBE_COST, 0, st);
     if (Pin != nullptr) {           // a later rank chunk of a rank above 128 (launch_cost_chunked): one instance per load width
         if (ldr < n) return NNF_ERR_ARG;

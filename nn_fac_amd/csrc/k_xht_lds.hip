@@ -181,21 +181,30 @@ static int launch_xht_lds(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, in
     int64_t off = (ldx * 4) % 128, gcd = 128;
     while (off) { const int64_t t = gcd % off; gcd = off; off = t; }
     const bool shared_lines = pin ? pin == 2 : (128 / gcd >= 4);
+    const char* tiling;   // (NNF_PLAN_DEBUG)
     if (shared_lines) {
+        tiling = "shared_lines";
         nth = 2;
         n_hi = grid = nnf_cdiv(m, 128);
     } else if (T > 4 * waves) {            // several rounds of 256-row workgroups
+        tiling = "rounds";
         n_hi = grid = nnf_cdiv(m, 256);
     } else if (T > 2 * waves) {     // one round: (4,3) or (3,2) tiles per wave
         nth = T > 3 * waves ? 4 : 3;
+        tiling = nth == 4 ? "round43" : "round32";
         n_hi = nnf_cdiv(T - 4 * (nth - 1) * slots, 4);
         grid = slots;
     } else {                        // small: 128-row workgroups
+        tiling = "small";
         nth = 3;
         n_hi = 0;
         grid = nnf_cdiv(m, 128);
     }
     if (n_hi * 64 * nth + (grid - n_hi) * 64 * (nth - 1) < m) return NNF_ERR_UNSUPPORTED;   // (the split covers m by construction)
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] xht m=%lld n=%lld r=%d mt=%d rem=%d vec=1 form=lds tiling=%s nth=%d n_hi=%lld grid=%lld "
+                        "tail_parts=0 tail_tiles=0 tail_cpp=0\n", (long long)m, (long long)n, r, MT, REM, tiling, nth, (long long)n_hi,
+                (long long)grid);
     nnf_probe(ctx, NNF_PROBE_XHT, 0, st);
     if (nth == 4)
         hipLaunchKernelGGL((nnf_xht_lds_kernel<MT, REM, 4>), dim3((int)grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo,

@@ -116,8 +116,10 @@ def test_gram_of_short_factors(eng, K, r):
 @pytest.mark.parametrize("n,r", [(70, 50), (129, 64), (70, 30), (129, 18), (64, 16), (500, 20)])
 def test_xht_row_tilings(eng, m, n, r):
     """X H^T picks its rows-per-workgroup from m (one balanced round of (3,2)- or (4,3)-tile workgroups, or several
-    rounds of 256-row workgroups): every branch, with ragged ends, against an fp64 product on the device -- in both kernel
-    forms (ranks <= 32 stage X through LDS in 256-byte row pieces, k_xht_lds.hip; the others read fragments directly)."""
+    rounds of 256-row workgroups): those row tilings, with ragged ends, against an fp64 product on the device -- in both kernel
+    forms (ranks <= 32 stage X through LDS in 256-byte row pieces, k_xht_lds.hip; the others read fragments directly).
+    These (n, r) pairs never take the k-split tail (it needs r > 32 and n > 192) or the two-tile form (r > 80, m > 229376 on
+    256 CUs): tests/test_gpu_launch_plans.py covers those, case by case."""
     g = torch.Generator(device="cuda").manual_seed(m + n)
     X = torch.rand(m, n, device="cuda", generator=g)
     V = torch.rand(r, n, device="cuda", generator=g)
