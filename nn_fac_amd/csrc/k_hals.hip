@@ -308,8 +308,11 @@ static int64_t hals_cap(nnf_ctx* ctx, int per_cu) {   // workgroups that stay re
     const int64_t c = (int64_t)per_cu * ctx->num_cus;
     return c < NNF_HALS_MAX_BLOCKS ? c : NNF_HALS_MAX_BLOCKS;
 }
-static bool hals_32bit(int r, int64_t ld, int64_t ncols) {   // the buffer offsets of an r x ncols operand fit 32 bits
-    return (((int64_t)(r - 1) * ld + ncols) * 4) < (int64_t)0x7fff0000;
+// The buffer offsets of rows 0 .. rows-1 of an operand with row stride ld fit 32 bits.  The lane and mfma kernels load (and
+// store) all RP padded rows of a column and rely on the rows >= r falling outside the descriptor: checked with rows = RP, so
+// that no padded row's offset wraps back into the rows of the operand.
+static bool hals_32bit(int rows, int64_t ld, int64_t ncols) {
+    return (((int64_t)(rows - 1) * ld + ncols) * 4) < (int64_t)0x7fff0000;
 }
 
 // the padded Gram (RP x RS, RS = RP rounded up to 32) and the RP (1/diag, nz) pairs + the all-live flag, then (64-byte
@@ -357,14 +360,16 @@ static hals_plan make_plan(nnf_ctx* ctx, const hals_request& q) {
     }
     if (force == 'w' && wave_shape) return refuse(p, NNF_ERR_UNSUPPORTED);
 
-    // few columns (<= 32768: at most two waves per SIMD): four lanes per column, 16 columns per workgroup
-    if (!generic && force != 'l' && !pin_mfma && (n <= 32768 || force == 'q') &&
-        (int64_t)(r + 16) * (q.ldv > q.ldm ? q.ldv : q.ldm) * 4 < (int64_t)0x7fff0000) {
+    // few columns (<= 32768: at most two waves per SIMD): four lanes per column, 16 columns per workgroup.  Its buffer
+    // offsets reach row r + 15 of V, UtM and the start values in 32 bits: start values beyond that are copied into V first.
+    auto quad_32bit = [&](int64_t ld) { return (int64_t)(r + 16) * ld * 4 < (int64_t)0x7fff0000; };
+    if (!generic && force != 'l' && !pin_mfma && (n <= 32768 || force == 'q') && quad_32bit(q.ldv > q.ldm ? q.ldv : q.ldm)) {
         const int ch = (r + 3) / 4, pc = nnf_hals_quad_per_cu(ch);
         const int64_t need = nnf_cdiv(n, 16);
         if (pc > 0 && need <= hals_cap(ctx, pc)) {
             p.layout = HL_QUAD, p.ch = ch, p.nblocks = (int)need, p.per_cu = pc;
-            p.copy = !sweeps && q.Vsrc != q.V;   // (the sweep kernel reads the start values and forms the Hadamard Gram itself)
+            // (the sweep kernel reads the start values and forms the Hadamard Gram itself)
+            p.copy = q.Vsrc != q.V && (!sweeps || !quad_32bit(q.ldvs));
             p.gram_floats = nnf_hals_quad_gram_floats(r);
             return p;
         }
@@ -379,7 +384,7 @@ static hals_plan make_plan(nnf_ctx* ctx, const hals_request& q) {
     p.hadamard = q.UtU2 != nullptr;
     const int lane_pc = generic ? 0 : nnf_hals_fast_per_cu(p.RP, true);
     const bool lane_fits = lane_pc > 0 && nnf_cdiv(n, 256) <= hals_cap(ctx, lane_pc);
-    p.copy = q.Vsrc != q.V && !(!generic && sweeps && lane_fits && hals_32bit(r, q.ldvs, n));
+    p.copy = q.Vsrc != q.V && !(!generic && sweeps && lane_fits && hals_32bit(p.RP, q.ldvs, n));
     if (!sweeps) {   // the prep kernel only (the status defaults of a solve with no sweep to run)
         p.layout = generic ? HL_GENERIC_LDS : HL_LANE_RES;
         return p;
@@ -414,7 +419,7 @@ static hals_plan make_plan(nnf_ctx* ctx, const hals_request& q) {
         return p;
     }
 
-    if (!hals_32bit(r, q.ldv, n) || !hals_32bit(r, q.ldm, n)) return refuse(p, NNF_ERR_UNSUPPORTED);
+    if (!hals_32bit(p.RP, q.ldv, n) || !hals_32bit(p.RP, q.ldm, n)) return refuse(p, NNF_ERR_UNSUPPORTED);
     const int64_t need = nnf_cdiv(n, 256);
     if (mfma) {   // when every column stays resident; else the lane kernel
         const int pc = nnf_hals_mfma_per_cu(p.RP);
@@ -449,9 +454,10 @@ static int hals_entry(nnf_ctx* ctx, hals_request q, hipStream_t st) {
     if (q.Vsrc == nullptr || q.Vsrc == q.V) { q.Vsrc = q.V; q.ldvs = q.ldv; }
     const hals_plan p = make_plan(ctx, q);
     if (getenv("NNF_HALS_DEBUG"))
-        fprintf(stderr, "[nnf hals] r=%d ncols=%lld mode=%d sweeps=%d sweep0=%d flags=%u -> %s grid=%d per_cu=%d cpw=%d nw=%d ch=%d lds=%zu "
-                "hadamard=%d copy=%d prep=%d err=%d\n", q.r, (long long)q.ncols, q.mode, q.nsweeps, q.sweep0, q.flags,
-                hals_layout_name[p.layout], p.nblocks, p.per_cu, p.cpw, p.nw, p.ch, p.lds, p.hadamard, p.copy, p.prep, p.err);
+        fprintf(stderr, "[nnf hals] r=%d ncols=%lld mode=%d sweeps=%d sweep0=%d flags=%u -> %s grid=%d per_cu=%d cpw=%d nw=%d ch=%d "
+                "RP=%d gs=%d lds=%zu hadamard=%d copy=%d prep=%d err=%d\n", q.r, (long long)q.ncols, q.mode, q.nsweeps, q.sweep0,
+                q.flags, hals_layout_name[p.layout], p.nblocks, p.per_cu, p.cpw, p.nw, p.ch, p.RP, p.gs, p.lds, p.hadamard, p.copy,
+                p.prep, p.err);
     if (p.err != NNF_OK) return p.err;
 
     const bool sweeps = q.nsweeps > 0;
