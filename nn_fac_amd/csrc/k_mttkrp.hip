@@ -376,19 +376,24 @@ static int launch_seg(nnf_ctx* ctx, const float* T, int64_t nrows, int64_t ldrow
     const int nrb = (int)nnf_cdiv(nrows, 256);
     const int64_t ldp = nnf_rup(nrows, 4);
     int64_t nsplit = 2 * (int64_t)ctx->num_cus / nrb;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > nseg) nsplit = nseg;
+    const char* bound = "occupancy";      // (report only, NNF_PLAN_DEBUG)
+    if (nsplit < 1) { nsplit = 1; bound = "one"; }
+    if (nsplit > nseg) { nsplit = nseg; bound = "segments"; }
     nnf_ws_cursor cur(ctx);
     const int64_t slab_elems = (int64_t)r * ldp;
     const int64_t ws_max = (int64_t)(cur.remaining() / 4) / slab_elems;
     if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit > ws_max) nsplit = ws_max;
+    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
     const int64_t sps = nnf_cdiv(nseg, nsplit);
     nsplit = nnf_cdiv(nseg, sps);
     float* slabs = (float*)cur.take((size_t)nsplit * slab_elems * 4);
     if (!slabs) return NNF_ERR_WORKSPACE;
     const int fk_vec_ok = ((((uintptr_t)Fk) & 15) == 0 && (ldk & 3) == 0) ? 1 : 0;
     const int grid = 8 * (int)nnf_cdiv(nsplit, 8) * nrb;
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] mttkrp_seg nrows=%lld nseg=%lld klen=%lld r=%d mt=%d VEC=%d fkvec=%d pp=%d nsplit=%lld sps=%lld bound=%s\n",
+                (long long)nrows, (long long)nseg, (long long)klen, r, MT, (int)VEC, fk_vec_ok, (int)(MT <= 2), (long long)nsplit,
+                (long long)sps, bound);
     nnf_probe(ctx, NNF_PROBE_MTTKRP, 0, st);
     hipLaunchKernelGGL((nnf_mttkrp_seg_kernel<MT, VEC>), dim3(grid), dim3(256), 0, st, T, nrows, ldrow, nseg, segstride,
                        klen, Fs, lds_, Fk, ldk, r, slabs, ldp, nrb, (int)nsplit, sps, fk_vec_ok);
@@ -403,18 +408,20 @@ static int launch_rows(nnf_ctx* ctx, const float* M, int64_t m, int64_t n, const
     const int ncb = (int)nnf_cdiv(n, 256);
     const int64_t ldp = nnf_rup(n, 4);
     int64_t nsplit = 2 * (int64_t)ctx->num_cus / ncb;
+    const char* bound = "occupancy";      // (report only, NNF_PLAN_DEBUG)
     if (nsplit < 1) nsplit = 1;
     const int64_t max_split = nnf_cdiv(m, 64);
-    if (nsplit > max_split) nsplit = max_split;
+    if (nsplit > max_split) { nsplit = max_split; bound = "rows"; }
     nnf_ws_cursor cur(ctx);
     const int64_t slab_elems = (int64_t)r * ldp;
     const int64_t ws_max = (int64_t)(cur.remaining() / 4) / slab_elems;
     if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit > ws_max) nsplit = ws_max;
+    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
     int64_t rps = nnf_rup(nnf_cdiv(m, nsplit), 64);
     while ((rps + 128) * n * 4 >= (int64_t)0x7fff0000) {
         if (rps <= 64) return NNF_ERR_UNSUPPORTED;
         rps = nnf_rup(rps / 2, 64);
+        bound = "offset32";
     }
     nsplit = nnf_cdiv(m, rps);
     if (nsplit > ws_max) return NNF_ERR_WORKSPACE;
@@ -424,6 +431,10 @@ static int launch_rows(nnf_ctx* ctx, const float* M, int64_t m, int64_t n, const
     nnf_probe(ctx, NNF_PROBE_MTTKRP, 0, st);
     // buffer-addressed Khatri-Rao generation: 31-bit byte offsets into both factors, at most one wrap inside four rows
     const bool kr_fast = nb >= 4 && (int64_t)(16 * MT) * lda * 4 < (int64_t)0x7fff0000 && (int64_t)(16 * MT) * ldb * 4 < (int64_t)0x7fff0000;   // (padded rank rows: their offsets must not wrap either)
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] mttkrp_rows m=%lld n=%lld nb=%lld r=%d mt=%d VEC=%d krf=%d krdiv=%s nsplit=%lld rps=%lld bound=%s\n",
+                (long long)m, (long long)n, (long long)nb, r, MT, (int)VEC, (int)kr_fast, !kr_fast ? "slow" : nb >= 64 ? "carry" : "redivide",
+                (long long)nsplit, (long long)rps, bound);
     if (kr_fast)
         hipLaunchKernelGGL((nnf_mttkrp_rows_kernel<MT, VEC, true>), dim3(grid), dim3(256), 0, st, M, m, n, n, Fa, lda, Fb, ldb, nb,
                            r, slabs, ldp, ncb, (int)nsplit, rps);
@@ -579,6 +590,9 @@ extern "C" int nnf_mttkrp3_from_partial_f32(nnf_ctx* ctx, const float* Y, int64_
     if (axis == 2) {
         int64_t grid = nnf_cdiv((int64_t)R * A, 4);
         if (grid > 8192) grid = 8192;
+        if (nnf_plan_debug())
+            fprintf(stderr, "[nnf plan] partial_last A=%lld B=%lld r=%d grid=%lld strided=%d\n", (long long)A, (long long)B, R,
+                    (long long)grid, (int)((int64_t)R * A > 4 * grid));
         hipLaunchKernelGGL(nnf_partial_last_kernel, dim3((int)grid), dim3(256), 0, st, Y, A, B, Ft, ldf, R, out, ldo);
         NNF_CHECK_LAUNCH();
         return NNF_OK;
@@ -586,9 +600,10 @@ extern "C" int nnf_mttkrp3_from_partial_f32(nnf_ctx* ctx, const float* Y, int64_
     // axis 1: enough a-chunks to fill the chip, at least 16 rows each
     const int64_t cb = nnf_cdiv(B, 256);
     int64_t nchunk = nnf_cdiv((int64_t)4 * ctx->num_cus, cb * R);
+    const char* bound = "occupancy";      // (report only, NNF_PLAN_DEBUG)
     if (nchunk < 1) nchunk = 1;
-    if (nchunk > nnf_cdiv(A, 16)) nchunk = nnf_cdiv(A, 16);
-    if (nchunk > 65535) nchunk = 65535;
+    if (nchunk > nnf_cdiv(A, 16)) { nchunk = nnf_cdiv(A, 16); bound = "rows16"; }
+    if (nchunk > 65535) { nchunk = 65535; bound = "grid"; }
     const int64_t a_per = nnf_cdiv(A, nchunk);
     nchunk = nnf_cdiv(A, a_per);
     const int64_t ldp = nnf_rup(B, 4);
@@ -596,6 +611,9 @@ extern "C" int nnf_mttkrp3_from_partial_f32(nnf_ctx* ctx, const float* Y, int64_
     float* slabs = (float*)cur.take((size_t)nchunk * R * ldp * 4);
     if (!slabs) return NNF_ERR_WORKSPACE;
     if (cb > 65535) return NNF_ERR_UNSUPPORTED;
+    if (nnf_plan_debug())
+        fprintf(stderr, "[nnf plan] partial_mid A=%lld B=%lld r=%d nchunk=%lld a_per=%lld bound=%s\n", (long long)A, (long long)B, R,
+                (long long)nchunk, (long long)a_per, bound);
     hipLaunchKernelGGL(nnf_partial_mid_kernel, dim3((unsigned)cb, (unsigned)nchunk, (unsigned)R), dim3(256), 0, st, Y, A, B, Ft,
                        ldf, a_per, slabs, ldp, R);
     NNF_CHECK_LAUNCH();

@@ -1441,8 +1441,8 @@ static int launch_cost(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64
         static const char* const ops[] = {"frob", "kl", "is", "gen", "ratio_kl", "ratio_gen", "prod"};
         const bool vv = Pin != nullptr ? x_vec_ok(X, ldx) && ldr >= n && x_vec_ok(Pin, ldr) : x_vec_ok(X, ldx);
         const int nn = (Pin != nullptr || OP == NNF_PROD || KS > 16) ? 8 : 4;
-        fprintf(stderr, "[nnf plan] cost m=%lld n=%lld r=%d op=%s grid=%d csplit=%d NN=%d vdb=%d VEC=%d pin=%d\n", (long long)m,
-                (long long)n, r, ops[OP], grid, csplit, nn, vdb, (int)vv, (int)(Pin != nullptr));
+        fprintf(stderr, "[nnf plan] cost m=%lld n=%lld r=%d op=%s grid=%d csplit=%d NN=%d vdb=%d VEC=%d pin=%d kr=%lld\n", (long long)m,
+                (long long)n, r, ops[OP], grid, csplit, nn, vdb, (int)vv, (int)(Pin != nullptr), (long long)(Ub ? nbu : 0));
     }
     nnf_probe(ctx, NNF_PROBE_COST, 0, st);
     if (Pin != nullptr) {           // a later rank chunk of a rank above 128 (launch_cost_chunked): one instance per load width

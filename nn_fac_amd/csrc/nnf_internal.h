@@ -64,8 +64,8 @@ static inline void nnf_probe(nnf_ctx* c, int id, int which, hipStream_t st) {
 static inline int64_t nnf_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t nnf_rup(int64_t a, int64_t b) { return nnf_cdiv(a, b) * b; }
 
-// NNF_PLAN_DEBUG: the streaming and MU launchers write one stderr line per call naming the plan they took,
-// "[nnf plan] <launcher> m=.. n=.. r=.. key=value ..." (tests/test_gpu_launch_plans.py keys on it).  Read once per unit.
+// NNF_PLAN_DEBUG: the streaming, MU, MTTKRP and dimension-tree launchers write one stderr line per call naming the plan they took,
+// "[nnf plan] <launcher> m=.. n=.. r=.. key=value ..." (tests/test_gpu_launch_plans.py and test_gpu_tensor_plans.py key on it).  Read once per unit.
 static inline bool nnf_plan_debug() {
     static const bool dbg = getenv("NNF_PLAN_DEBUG") != nullptr;
     return dbg;
