@@ -41,8 +41,10 @@ extern "C" {
  * points (nnf_gram / xty / xht / frob_resid / betadiv / mu_ratio / nmf_gram_cost / hals_solve / hals_sweeps / hals_row_* /
  * mttkrp3 / mttkrp3_from_partial / cp3_betadiv / ttm3 along the first and last axis) go on above it, as the reference does
  * (nn_fac/nmf.py:175-178: any rank <= min(shape); nnls.py:158 loops range(r)): the contractions and cost passes walk the rank
- * in chunks of 128, the sweeps run in the generic kernel on columns in global memory.  The fused MU kernels, nnf_ttm3_f32
- * along the middle axis and the Tucker core update return NNF_ERR_UNSUPPORTED above it. */
+ * in chunks of 128, the sweeps run in the generic kernel on columns in global memory.  The fused MU updates (nnf_mu_left /
+ * mu_right / mu_right_accum: every beta up to this rank, beta = 2 beyond it as well), nnf_ttm3_f32 along the middle axis and
+ * the Tucker core update return NNF_ERR_UNSUPPORTED above it; the cost-carrying fused forms (nnf_mu_left_kl_cost_f32,
+ * nnf_mu_left_num_f32, nnf_cp3_partial_cost_f32) stop at rank 64. */
 #define NNF_MAX_RANK 128
 
 /* hals flags */
@@ -253,8 +255,8 @@ int nnf_hals_stop_restore_f32(nnf_ctx* ctx, const double* sums_f64, int nsweeps,
 /* mu_betadivmin (mu.py:79-97) for the left factor, transposed storage:
  *   Ut_out[k,i] = max(Ut[k,i] * (num[k,i]/den[k,i])^gamma(beta), 1e-12),
  *   num = ((UV)^(beta-2) .* X) V^T, den = (UV)^(beta-1) V^T       (beta=1: den = rowsum(V); beta=2: Gram form)
- * One pass over X; U@V is never materialised.  Ut_out must not alias Ut.  beta != 2 needs r <= 64 (else
- * NNF_ERR_UNSUPPORTED). */
+ * One pass over X; U@V is never materialised and no data-sized temporary is used (device memory: the context workspace).
+ * Ut_out must not alias Ut.  beta != 2 needs r <= NNF_MAX_RANK (else NNF_ERR_UNSUPPORTED). */
 int nnf_mu_left_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
                     const float* V, int64_t ldv, int r, double beta, float* Ut_out, int64_t lduo, void* stream);
 
@@ -266,7 +268,8 @@ int nnf_mu_left_kl_cost_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, 
                             const float* V, int64_t ldv, int r, float* Ut_out, int64_t lduo, double* cost_f64, void* stream);
 
 /* switch_alternate_mu(..., "V") (mu.py:26-27): V_out[k,j] = max(V[k,j] * (num/den)^gamma, 1e-12) with
- *   num = U^T((UV)^(beta-2) .* X), den = U^T (UV)^(beta-1); split over m, fixed-order slab reduction. */
+ *   num = U^T((UV)^(beta-2) .* X), den = U^T (UV)^(beta-1); split over m, fixed-order slab reduction.
+ * beta != 2 needs r <= NNF_MAX_RANK (else NNF_ERR_UNSUPPORTED), like nnf_mu_right_accum_f32 below. */
 int nnf_mu_right_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
                      const float* V, int64_t ldv, int r, double beta, float* V_out, int64_t ldvo, void* stream);
 
@@ -283,7 +286,7 @@ int nnf_mu_apply_f32(nnf_ctx* ctx, const float* F, int64_t ldf, int r, int64_t c
                      const float* den, int64_t ldden, const double* den_vec_f64, double beta, float* out, int64_t ldo,
                      void* stream);
 
-/* Ranks beyond the fused kernels (64 < r <= 128, beta != 2): the element-wise operands of mu_betadivmin (mu.py:84-97),
+/* Ranks beyond the fused kernels (r > NNF_MAX_RANK, every beta): the element-wise operands of mu_betadivmin (mu.py:84-97),
  *   R1 = X .* (UV)^(beta-2)   and, unless beta == 1,   R2 = (UV)^(beta-1)        (both m x n, row stride ldr, caller-owned),
  * written in one pass over X; the two contractions are then plain nnf_xht_f32 / nnf_xty_f32 calls on R1 / R2 and
  * nnf_mu_apply_f32 finishes (nn_fac_amd/engine.py composes them when the fused entry points return NNF_ERR_UNSUPPORTED). */

@@ -13,15 +13,20 @@
 //             tile of MFMA #1 is used AS the B operand of MFMA #2 with no lane movement, because P is computed in the
 //             orientation whose row index is the contracted one (cdna_hip_programming.md s.3, "accumulator as operand").
 // X goes HBM -> VGPR once, 16 bytes per lane; K is never written anywhere.
-// Built for r <= 64 (MT <= 4); larger ranks return NNF_ERR_UNSUPPORTED for beta != 2.
+// Built for r <= NNF_MAX_RANK = 128 (MT <= 8 rank tiles of 16).  Up to rank 64 the KL forms keep the resident factor
+// fragments in registers and the general-beta form keeps them in LDS; above it (MT = 5 .. 8) the chunk images alone fill LDS
+// (16 KiB per rank tile), so both forms keep the fragments in registers and a wave takes half the output tile (32 columns in
+// the right kernel, 32 rows in the left one; the KL left kernel also 48) to make room for them: see DESIGN.md.  The
+// cost-carrying forms stop at 64.
 #include "k_mu_kernels.h"
 
-// One source, three translation units (Makefile: -DMU_PART=0|1|2) so that the ~60 instantiations of the two fused kernels
+// One source, seven translation units (Makefile: -DMU_PART=0..6) so that the ~90 instantiations of the two fused kernels
 // compile side by side: 0 = right update + the small helpers, 1 = left update (beta = 1 and general beta), 2 = the left
-// kernel's cost-carrying forms (KL cost, NTF cost + partial product).  The small kernels and launch templates above the
-// entry points are `static`: every unit sees them, only the units that use them emit them.
+// kernel's cost-carrying forms (KL cost, NTF cost + partial product); ranks 65 .. 128 (MT = 5 .. 8): 3 = right KL, 4 = right
+// general beta, 5 = left KL, 6 = left general beta.  The small kernels and launch templates above the entry points are
+// `static`: every unit sees them, only the units that use them emit them.
 #ifndef MU_PART
-#error "k_mu.hip is compiled per part: -DMU_PART=0|1|2"
+#error "k_mu.hip is compiled per part: -DMU_PART=0..6"
 #endif
 NNF_BUILD_FLAGS(NNF_CAT(k_mu, MU_PART), "MU_WG_PER_CU=" NNF_STR(MU_WG_PER_CU) " MU_STEP_FENCE()=" NNF_STR(MU_STEP_FENCE()))
 
@@ -128,10 +133,6 @@ static __global__ __launch_bounds__(256) void nnf_mu2_finish_kernel(const float*
 
 static float gamma_of(double beta) { return beta < 1.0 ? (float)(1.0 / (2.0 - beta)) : (beta > 2.0 ? (float)(1.0 / (beta - 1.0)) : 1.f); }
 
-static size_t mu_shm(int MT, int REM, int r, bool regf) {   // two double-buffered chunk images (+ the resident fragments unless in registers)
-    return ((regf ? 0 : (size_t)4 * ((r + 3) / 4) * 64) + (size_t)2 * (2 * MT + (REM > 0 ? 1 : 0)) * 256) * 16;
-}
-
 // leftover ranks handled on the VALU pipe: up to 4 next to one MFMA tile (ranks 17..20), up to 2 next to two or three (33, 34,
 // 49, 50) -- four leftover ranks at two tiles left scratch reloads inside the right kernel's chunk loop, at three tiles hipcc
 // spilled hundreds of registers (256 per wave at two workgroups per CU)
@@ -169,10 +170,10 @@ static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int
                            int64_t ldvo, hipStream_t st, float* num_out = nullptr, int64_t ldnum = 0,
                            float* den_out = nullptr, int64_t ldden = 0, double* den_vec_out = nullptr) {
     if ((int64_t)(16 * (MT + 1)) * ldu * 4 + 4 * (m + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;   // 32-bit image offsets
-    const int ncb = (int)nnf_cdiv(n, 256);
+    const int ncb = (int)nnf_cdiv(n, 64 * MU_RIGHT_NC(MT));   // column blocks: 256 columns per workgroup, 128 at MT > 4
     const int64_t ldp = nnf_rup(n, 4);
     const int nacc = (BM == BM_GEN) ? 2 : 1;
-    int64_t nsplit = (BM == BM_KL ? 2 : 1) * (int64_t)ctx->num_cus / ncb;   // resident 4-wave workgroups per CU
+    int64_t nsplit = (BM == BM_KL && MT <= 4 ? 2 : 1) * (int64_t)ctx->num_cus / ncb;   // resident 4-wave workgroups per CU
     if (nsplit < 1) nsplit = 1;
     const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
     const int64_t max_split = nnf_cdiv(m, 64);
@@ -202,7 +203,7 @@ static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int
     float* sden = nacc == 2 ? (float*)cur.take((size_t)nsplit * slab_elems * 4) : nullptr;
     if (!snum || (nacc == 2 && !sden)) return NNF_ERR_WORKSPACE;
     const int a_vec_ok = ((((uintptr_t)Ut) & 15) == 0 && (ldu & 3) == 0) ? 1 : 0;
-    const size_t shm = mu_shm(MT, REM, r, BM == BM_KL);
+    const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, BM == BM_GEN));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_mu_right_kernel<MT, REM, BM, VEC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     const int grid = 8 * (int)nnf_cdiv(nsplit, 8) * ncb;
@@ -235,7 +236,7 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
     double* dvec = (double*)cur.take((size_t)r * 8);
     if (!dvec) return NNF_ERR_WORKSPACE;
     const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
-    const size_t shm = mu_shm(MT, REM, r, BM != BM_GEN);
+    const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, BM == BM_GEN));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_mu_left_kernel<MT, REM, BM, VEC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     if (BM == BM_KL || BM == BM_KLC) {  // den[k] = rowsum(V)[k]   (mu.py:86-87)
@@ -249,8 +250,12 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
     const int64_t slots = (int64_t)MU_LEFT_WGPC(MT, REM, BM) * ctx->num_cus, T = nnf_cdiv(m, 16);
     const int64_t W = nnf_cdiv(T, 16 * slots) * slots;
     int64_t n_hi = 0, n_mid = 0, grid = W;
-    if (T <= 8 * slots) {
+    if (MU_LEFT_ROWS128(MT, BM) || T <= 8 * slots) {
         grid = nnf_cdiv(m, 128);
+    } else if (MT > 4) {   // ranks 81 .. 128, KL: 192- and 128-row workgroups (rounds of 8 to 12 tiles each; 16 do not fit the registers)
+        const int64_t W3 = nnf_cdiv(T, 12 * slots) * slots;
+        if (T <= 8 * W3) grid = nnf_cdiv(m, 128);
+        else { grid = W3; n_mid = nnf_cdiv(T - 8 * W3, 4); }
     } else if (T > 12 * W) {
         n_hi = nnf_cdiv(T - 12 * W, 4);
         n_mid = W - n_hi;
@@ -262,7 +267,7 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
         fprintf(stderr, "[nnf plan] mu_left m=%lld n=%lld r=%d mt=%d rem=%d vec=%d bm=%s form=%s grid=%lld n_hi=%lld n_mid=%lld\n",
                 (long long)m, (long long)n, r, MT, REM, (int)VEC,
                 BM == BM_KL ? "KL" : BM == BM_KLC ? "KLC" : BM == BM_FROB ? "FROB" : "GEN",
-                T <= 8 * slots ? "small" : n_hi > 0 ? "hi" : "mid", (long long)grid, (long long)n_hi, (long long)n_mid);
+                T <= 8 * slots ? "small" : n_hi > 0 ? "hi" : n_mid > 0 ? "mid" : MT > 4 ? "rows128" : "mid", (long long)grid, (long long)n_hi, (long long)n_mid);
     if (BM == BM_FROB || BM == BM_KLC) {
         ex.partial = (double*)cur.take((size_t)grid * 8);
         if (!ex.partial || !cost_out) return NNF_ERR_WORKSPACE;
@@ -282,6 +287,59 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
         if (beta == 1.0) MU_CALL(FN, BM_KL, true, r, vec, __VA_ARGS__);                                   \
         MU_CALL(FN, BM_GEN, false, r, vec, __VA_ARGS__);                                                  \
     } while (0)
+
+// ranks 65 .. 128 (MT = 5 .. 8, no leftover-rank forms): the instantiations live in units 3 .. 6
+#define MU_CALL_BIG(FN, BMV, R, VECF, ...)                                                                   \
+    do {                                                                                                     \
+        switch (((R) + 15) / 16) {                                                                           \
+            case 5: return (VECF) ? FN<5, 0, BMV, true>(__VA_ARGS__) : FN<5, 0, BMV, false>(__VA_ARGS__);    \
+            case 6: return (VECF) ? FN<6, 0, BMV, true>(__VA_ARGS__) : FN<6, 0, BMV, false>(__VA_ARGS__);    \
+            case 7: return (VECF) ? FN<7, 0, BMV, true>(__VA_ARGS__) : FN<7, 0, BMV, false>(__VA_ARGS__);    \
+            case 8: return (VECF) ? FN<8, 0, BMV, true>(__VA_ARGS__) : FN<8, 0, BMV, false>(__VA_ARGS__);    \
+            default: return NNF_ERR_UNSUPPORTED;                                                             \
+        }                                                                                                    \
+    } while (0)
+int nnf_mu_right_big_kl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut,
+                        int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* V_out, int64_t ldvo, hipStream_t st,
+                        float* num_out, int64_t ldnum, float* den_out, int64_t ldden, double* den_vec_out);
+int nnf_mu_right_big_gen(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut,
+                         int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* V_out, int64_t ldvo, hipStream_t st,
+                         float* num_out, int64_t ldnum, float* den_out, int64_t ldden, double* den_vec_out);
+int nnf_mu_left_big_kl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut,
+                       int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* Ut_out, int64_t lduo, hipStream_t st);
+int nnf_mu_left_big_gen(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut,
+                        int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* Ut_out, int64_t lduo, hipStream_t st);
+#if MU_PART == 3 || MU_PART == 4
+#if MU_PART == 3
+int nnf_mu_right_big_kl(
+#else
+int nnf_mu_right_big_gen(
+#endif
+    nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
+    const float* V, int64_t ldv, int r, double beta, float* V_out, int64_t ldvo, hipStream_t st, float* num_out, int64_t ldnum,
+    float* den_out, int64_t ldden, double* den_vec_out) {
+    MU_CALL_BIG(launch_mu_right, (MU_PART == 3 ? BM_KL : BM_GEN), r, x_vec_ok(X, ldx), ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r,
+                beta, V_out, ldvo, st, num_out, ldnum, den_out, ldden, den_vec_out);
+}
+#endif
+#if MU_PART == 5 || MU_PART == 6
+#if MU_PART == 5
+int nnf_mu_left_big_kl(
+#else
+int nnf_mu_left_big_gen(
+#endif
+    nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
+    const float* V, int64_t ldv, int r, double beta, float* Ut_out, int64_t lduo, hipStream_t st) {
+#if MU_PART == 5
+    // ranks 97 .. 100 (config E's rank), KL, aligned X: six tiles on MFMA and the four leftover ranks on the VALU pipe (REM)
+    // instead of a padded seventh tile -- 6.25 tiles' worth of work instead of 6.5 + 7 in the two MFMAs
+    if (r > 96 && r <= 100 && x_vec_ok(X, ldx))
+        return launch_mu_left<6, 4, BM_KL, true>(ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, Ut_out, lduo, st);
+#endif
+    MU_CALL_BIG(launch_mu_left, (MU_PART == 5 ? BM_KL : BM_GEN), r, x_vec_ok(X, ldx), ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r,
+                beta, Ut_out, lduo, st);
+}
+#endif
 
 static int mu_args_ok(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
                       const float* V, int64_t ldv, int r, double beta, const float* out) {
@@ -313,6 +371,9 @@ extern "C" int nnf_mu_left_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t 
         NNF_CHECK_LAUNCH();
         return NNF_OK;
     }
+    if (r > 64)
+        return (beta == 1.0 ? nnf_mu_left_big_kl : nnf_mu_left_big_gen)(ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, Ut_out,
+                                                                       lduo, st);
     MU_DISPATCH(launch_mu_left, ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, Ut_out, lduo, st);
 }
 
@@ -339,6 +400,9 @@ extern "C" int nnf_mu_right_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t
         NNF_CHECK_LAUNCH();
         return NNF_OK;
     }
+    if (r > 64)
+        return (beta == 1.0 ? nnf_mu_right_big_kl : nnf_mu_right_big_gen)(ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, V_out,
+                                                                         ldvo, st, nullptr, 0, nullptr, 0, nullptr);
     MU_DISPATCH(launch_mu_right, ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, V_out, ldvo, st);
 }
 
@@ -388,6 +452,9 @@ extern "C" int nnf_mu_right_accum_f32(nnf_ctx* ctx, const float* X, int64_t m, i
         NNF_CHECK_LAUNCH();
         return NNF_OK;
     }
+    if (r > 64)
+        return (beta == 1.0 ? nnf_mu_right_big_kl : nnf_mu_right_big_gen)(ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, nullptr,
+                                                                         0, st, num, ldnum, den, ldden, den_vec_f64);
     MU_DISPATCH(launch_mu_right, ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, nullptr, 0, st, num, ldnum, den, ldden,
                 den_vec_f64);
 }

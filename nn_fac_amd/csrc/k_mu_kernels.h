@@ -2,6 +2,7 @@
 // instantiation can be compiled alone (tools/mu_kernel_regs.sh: registers, spills, ISA of a single kernel in seconds).
 #pragma once
 #include "k_stream_common.h"
+#include "k_mu_plan.h"
 #include <math.h>
 
 enum { BM_KL = 1, BM_FROB = 2, BM_KLC = 3, BM_GEN = 9 };   // BM_KLC: the KL update + the KL divergence of its INPUT factors   // BM_FROB: R = X (plain X V^T) + the squared residual, see nnf_cp3_partial_cost_f32
@@ -23,7 +24,7 @@ __device__ __forceinline__ void stageK_store(f32x4* __restrict__ img, const f32x
     for (int s4 = 0; s4 < MT; ++s4) img[(t * MT + s4) * 64 + L] = regs[s4];
 }
 // Which rank steps (4 ranks each) of MFMA #1 run.  MT = ceil(r / 16), so every 16-rank group but the last is full; with the
-// resident fragments in registers (zero beyond r, like the chunk image) the last group runs 2 or 4 steps behind ONE
+// resident fragments in registers (KL forms, and every form at MT > 4; zero beyond r, like the chunk image) the last group runs 2 or 4 steps behind ONE
 // wave-uniform flag: a test per step (4*s4 + c < KS) splits the product into 16 basic blocks and pins every LDS read of
 // the image behind a full wait.  The LDS-resident form (general beta) holds exactly KS fragments per wave: exact test.
 template <int MT, bool REGF>
@@ -33,13 +34,38 @@ __device__ __forceinline__ bool mu_kstep_on(int s4, int c, int KS, bool tail4) {
 }
 
 // resident workgroups per CU of the left kernel: three for the small Frobenius forms (<= 168 VGPRs), one for general beta
-#define MU_LEFT_WGPC(MT, REM, BM) ((BM) == BM_GEN ? 1 : (((MT) + ((REM) > 0) <= 2 && (REM) <= 2 && (BM) == BM_FROB) ? 3 : 2))
+// and for ranks above 80 (MT > 5: 16 KiB of chunk images per rank tile)
+#define MU_LEFT_WGPC(MT, REM, BM) ((BM) == BM_GEN || (MT) > 5 ? 1 : (((MT) + ((REM) > 0) <= 2 && (REM) <= 2 && (BM) == BM_FROB) ? 3 : 2))
+// above rank 64 the left kernel has its 128-row form only for general beta (numerator + denominator + fragments in registers)
+// and at MT = 5 (there that form stays within 256 registers and 80 KiB of LDS: two workgroups share a CU, which measured
+// faster than the better balanced mix of 192- and 128-row workgroups at one per CU: 719 against 792 us at 100000 x 2000, r = 65)
+#define MU_LEFT_ROWS128(MT, BM) ((MT) > 4 && ((BM) == BM_GEN || (MT) == 5))
 #ifndef MU_WG_PER_CU
 #define MU_WG_PER_CU 2
 #endif
 #ifndef MU_STEP_FENCE
 #define MU_STEP_FENCE() __builtin_amdgcn_sched_barrier(0)
 #endif
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// N = 4 or 2 consecutive floats of a row of X in the low components of a float4 (N = 2: the upper two are never read)
+template <bool VEC, int N>
+__device__ __forceinline__ f32x4 nnf_bloadn(rsrc_t rs, int voff, int soff) {
+    if constexpr (N == 4) {
+        return nnf_bload4<VEC>(rs, voff, soff);
+    } else {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (VEC) {
+            const f32x2 p = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0));
+            v[0] = p[0];
+            v[1] = p[1];
+        } else {
+            v[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
+            v[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff + 4, soff, 0));
+        }
+        return v;
+    }
+}
 
 template <int BM>
 __device__ __forceinline__ void mu_elem(float x, float p, float beta, float& r1, float& r2) {
@@ -68,8 +94,13 @@ __device__ __forceinline__ void mu_elem(float x, float p, float beta, float& r1,
 // and the F_A image's extra tile), their numerator rows are lane-local dot products with R, reduced over the four row
 // groups at the end.  For rank 50 that is 48 + 48 MFMAs + 64 FMAs per 16 x 64 block instead of 56 + 64 MFMAs (fp32 MFMA and
 // fp32 FMA share one pipe: 2048 flops in 32 cycles either way), and 40 fewer registers: no spills at two workgroups per CU.
+// MT > 4 (ranks 65 .. 128): a wave takes NC = 2 column tiles (32 columns, a workgroup 128) instead of four, which halves the
+// accumulators and the resident fragments -- at MT = 8 the general-beta form holds 64 + 64 + 64 registers of them instead of
+// 3 x 128 -- so that BOTH forms keep the fragments in registers and LDS holds the chunk images only (16 KiB per rank tile:
+// 128 KiB at MT = 8, one workgroup per CU).
+#define MU_RIGHT_NC(MT) ((MT) > 4 ? 2 : 4)
 template <int MT, int REM, int BM, bool VEC>
-__global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_right_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+__global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) void nnf_mu_right_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
                                                               const float* __restrict__ Ut, int64_t ldu,
                                                               const float* __restrict__ V, int64_t ldv, int r, float beta,
                                                               float* __restrict__ snum, float* __restrict__ sden,
@@ -77,10 +108,12 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
                                                               int a_vec_ok) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(REM == 0 || BM == BM_KL, "leftover ranks on the VALU pipe: KL form only");
+    static_assert(REM == 0 || MT <= 4, "leftover ranks on the VALU pipe: up to three full tiles");
+    constexpr int NC = MU_RIGHT_NC(MT);                              // 16-column tiles per wave: columns jl + cc, cc < NC
     constexpr int MTA = MT + (REM > 0 ? 1 : 0);                      // tiles of the F_A image
     constexpr int NR = REM > 0 ? REM : 1;
     const int KS = REM > 0 ? 4 * MT : ((r + 3) >> 2);
-    constexpr bool REGF = (BM == BM_KL);                             // resident fragments in registers / in LDS
+    constexpr bool REGF = mu_frags_in_regs(MT, BM == BM_GEN);                           // resident fragments in registers / in LDS
     const bool tail4 = REM > 0 || KS > 4 * (MT - 1) + 2;
     f32x4* ldsVf = reinterpret_cast<f32x4*>(smem);                 // !REGF: [4][KS][64]: V[4s+g][jw+4jj..+3]
     f32x4* ldsA = ldsVf + (REGF ? 0 : (size_t)4 * KS * 64);          // [2][MTA*256]  F_A image of the Ut chunk
@@ -93,19 +126,19 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
     const int64_t i_begin = (int64_t)ks * rows_per_split;
     const int64_t i_end = (i_begin + rows_per_split < m) ? (i_begin + rows_per_split) : m;
     const int nchunk = (int)((i_end - i_begin + 63) >> 6);
-    const int64_t jw = (int64_t)cb * 256 + w * 64, jl = jw + 4 * jj;
+    const int64_t jw = (int64_t)cb * (64 * NC) + w * (16 * NC), jl = jw + NC * jj;
     const rsrc_t rs = nnf_make_rsrc(X + i_begin * ldx, (uint32_t)(((i_end - i_begin - 1) * ldx + n) * 4));
     const int voff = (jl < n) ? (int)(((int64_t)4 * g * ldx + jl) * 4) : (int)0x7ffffff0;
     const int ldx4 = (int)(ldx * 4);
 
-    auto v_row4 = [&](int k) {   // V[k][jl .. jl+3], zero beyond r x n
+    auto v_row4 = [&](int k) {   // V[k][jl .. jl+NC-1], zero beyond r x n
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (k < r && jl < n) {
             const float* p = V + (int64_t)k * ldv + jl;
             v[0] = p[0];
             if (jl + 1 < n) v[1] = p[1];
-            if (jl + 2 < n) v[2] = p[2];
-            if (jl + 3 < n) v[3] = p[3];
+            if (NC > 2 && jl + 2 < n) v[2] = p[2];
+            if (NC > 2 && jl + 3 < n) v[3] = p[3];
         }
         return v;
     };
@@ -118,6 +151,7 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
 #pragma unroll
         for (int rr = 0; rr < NR; ++rr) vrem[rr] = (REM > 0) ? v_row4(16 * MT + rr) : f32x4{0.f, 0.f, 0.f, 0.f};
     } else {
+        static_assert(REGF || NC == 4, "LDS-resident fragments: four column tiles per wave");
         for (int e = threadIdx.x; e < 4 * KS * 64; e += 256) {
             const int ww = e / (KS * 64), rem = e - ww * KS * 64, s_ = rem >> 6, L = rem & 63;
             const int k = 4 * s_ + (L >> 4);
@@ -137,7 +171,7 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
+        for (int cc = 0; cc < NC; ++cc) {
             num[mt][cc] = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (BM == BM_GEN) den[mt][cc] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -148,7 +182,7 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) xb[t][c] = nnf_bload4<VEC>(rs, voff, (16 * t + c) * ldx4);
+        for (int c = 0; c < 4; ++c) xb[t][c] = nnf_bloadn<VEC, NC>(rs, voff, (16 * t + c) * ldx4);
     const mu_stage stg = mu_stage_make(Ut, ldu, r, i_end);
     {
         f32x4 sa[MTA], sk[MT];
@@ -163,7 +197,7 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
     auto elementwise = [&](const f32x4 (&x)[4], const f32x4 (&accP)[4], int rowrem, f32x4 (&R1)[4],
                            f32x4 (&R2)[BM == BM_GEN ? 4 : 1]) {
 #pragma unroll
-        for (int cc = 0; cc < 4; ++cc)
+        for (int cc = 0; cc < NC; ++cc)
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 float r1, r2;
@@ -210,7 +244,7 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
                         }
                 } else {
 #pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) accP[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    for (int cc = 0; cc < NC; ++cc) accP[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
                 nnf_static_for<0, MT>([&](auto s4c) {
                     constexpr int s4 = decltype(s4c)::value;
@@ -219,13 +253,13 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
                     for (int c = 0; c < 4; ++c) {
                         if (mu_kstep_on<MT, true>(s4, c, KS, tail4)) {
 #pragma unroll
-                            for (int cc = 0; cc < 4; ++cc) accP[cc] = MFMA16(ak[s4][c], vfr[4 * s4 + c][cc], accP[cc]);
+                            for (int cc = 0; cc < NC; ++cc) accP[cc] = MFMA16(ak[s4][c], vfr[4 * s4 + c][cc], accP[cc]);
                         }
                     }
                 });
                 nnf_static_for<0, MT>([&](auto mt) { nnf_lds_read4<(mt * 4 + t) * 1024>(af[mt], ab); });
                 const int rowrem = rows_left - 16 * t - 4 * g;
-                f32x4 R1[4], R2[1];
+                f32x4 R1[4], R2[BM == BM_GEN ? 4 : 1];
                 elementwise(xb[t & 1], accP, rowrem, R1, R2);
                 if constexpr (REM > 0) {
 #pragma unroll
@@ -248,15 +282,18 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg)
 #pragma unroll
-                        for (int cc = 0; cc < 4; ++cc) num[mt][cc] = MFMA16(af[mt][reg], R1[cc][reg], num[mt][cc]);
+                        for (int cc = 0; cc < NC; ++cc) {
+                            num[mt][cc] = MFMA16(af[mt][reg], R1[cc][reg], num[mt][cc]);
+                            if constexpr (BM == BM_GEN) den[mt][cc] = MFMA16(af[mt][reg], R2[cc][reg], den[mt][cc]);
+                        }
                     if constexpr (t < 3) {
-                        nnf_lds_read4_after<((t + 1) * MT + mt) * 1024>(ak[mt], kb, num[mt][3]);
+                        nnf_lds_read4_after<((t + 1) * MT + mt) * 1024>(ak[mt], kb, (BM == BM_GEN ? den : num)[mt][NC - 1]);
                         if constexpr (mt == UVT)
                             nnf_static_for<0, REM>([&](auto rr) { nnf_lds_read4<(MT * 4 + t + 1) * 1024 + rr * 16>(uv[rr], ub); });
                     }
                 });
 #pragma unroll
-                for (int c = 0; c < 4; ++c) xb[t & 1][c] = nnf_bload4<VEC>(rs, voff, soff_q + (16 * (t + 2) + c) * ldx4);
+                for (int c = 0; c < 4; ++c) xb[t & 1][c] = nnf_bloadn<VEC, NC>(rs, voff, soff_q + (16 * (t + 2) + c) * ldx4);
                 // next chunk's images: A loaded at the top of the chunk and written here in group 1, K loaded in group 2 and
                 // written after group 3 -- the fences between the groups keep the two staging sets from being live together
                 if constexpr (t == 1) stageA_store<MTA>(ldsA + (size_t)((q + 1) & 1) * MTA * 256, sa);
@@ -312,7 +349,7 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
                         if constexpr (BM == BM_GEN) den[mt][cc] = MFMA16(af[mt][reg], R2[cc][reg], den[mt][cc]);
                     }
 #pragma unroll
-            for (int c = 0; c < 4; ++c) xb[t & 1][c] = nnf_bload4<VEC>(rs, voff, soff_q + (16 * (t + 2) + c) * ldx4);
+            for (int c = 0; c < 4; ++c) xb[t & 1][c] = nnf_bloadn<VEC, NC>(rs, voff, soff_q + (16 * (t + 2) + c) * ldx4);
             if (t == 1) stageA_store<MTA>(ldsA + (size_t)((q + 1) & 1) * MTA * 256, sa);
             if (t == 2) stageK_bload<MT>(stg, i_end, i_begin + 64 * (int64_t)(q + 1), sk);
             MU_STEP_FENCE();
@@ -330,11 +367,17 @@ __global__ __launch_bounds__(256, (BM == BM_KL ? MU_WG_PER_CU : 1)) void nnf_mu_
             for (int reg = 0; reg < 4; ++reg) {
                 const int rk = 16 * mt + 4 * g + reg;
                 if (rk < r) {
-                    *reinterpret_cast<f32x4*>(sn + (int64_t)rk * ldp + jl) =
-                        f32x4{num[mt][0][reg], num[mt][1][reg], num[mt][2][reg], num[mt][3][reg]};
-                    if constexpr (BM == BM_GEN)
-                        *reinterpret_cast<f32x4*>(sd + (int64_t)rk * ldp + jl) =
-                            f32x4{den[mt][0][reg], den[mt][1][reg], den[mt][2][reg], den[mt][3][reg]};
+                    if constexpr (NC == 4) {
+                        *reinterpret_cast<f32x4*>(sn + (int64_t)rk * ldp + jl) =
+                            f32x4{num[mt][0][reg], num[mt][1][reg], num[mt][2][reg], num[mt][3][reg]};
+                        if constexpr (BM == BM_GEN)
+                            *reinterpret_cast<f32x4*>(sd + (int64_t)rk * ldp + jl) =
+                                f32x4{den[mt][0][reg], den[mt][1][reg], den[mt][2][reg], den[mt][3][reg]};
+                    } else {   // (jl is even and ldp a multiple of 4: the pair is 8-byte aligned and inside the slab row)
+                        *reinterpret_cast<f32x2*>(sn + (int64_t)rk * ldp + jl) = f32x2{num[mt][0][reg], num[mt][1][reg]};
+                        if constexpr (BM == BM_GEN)
+                            *reinterpret_cast<f32x2*>(sd + (int64_t)rk * ldp + jl) = f32x2{den[mt][0][reg], den[mt][1][reg]};
+                    }
                 }
             }
     }
@@ -373,7 +416,7 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
     constexpr int MTA = MT + (REM > 0 ? 1 : 0);                      // tiles of the F_A image
     constexpr int NR = REM > 0 ? REM : 1;
     const int KS = REM > 0 ? 4 * MT : ((r + 3) >> 2);
-    constexpr bool REGF = (BM != BM_GEN);                            // resident fragments in registers / in LDS
+    constexpr bool REGF = mu_frags_in_regs(MT, BM == BM_GEN);                          // resident fragments in registers / in LDS
     const bool tail4 = REM > 0 || KS > 4 * (MT - 1) + 2;
     float csum = 0.f;                                                // BM_FROB: this lane's share of sum (X - UV)^2
     f32x4* ldsUf = reinterpret_cast<f32x4*>(smem);                 // !REGF: [4][KS][64]: comps nt: Ut[4s+g][i0w+16nt+ii]
@@ -566,7 +609,7 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
                 });
                 nnf_static_for<0, MT>([&](auto mt) { nnf_lds_read4<(mt * 4 + t) * 1024>(af[mt], ab); });
                 const int colrem = cols_left - 16 * t - 4 * g;
-                f32x4 R1[4], R2[1];
+                f32x4 R1[4], R2[BM == BM_GEN ? 4 : 1];
                 elementwise(xb[t & 1], accP, colrem, R1, R2);
                 if constexpr (REM > 0) {
 #pragma unroll
@@ -585,9 +628,12 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
 #pragma unroll
                     for (int reg = 0; reg < 4; ++reg)
 #pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) num[mt][nt] = MFMA16(af[mt][reg], R1[nt][reg], num[mt][nt]);
+                        for (int nt = 0; nt < NT; ++nt) {
+                            num[mt][nt] = MFMA16(af[mt][reg], R1[nt][reg], num[mt][nt]);
+                            if constexpr (BM == BM_GEN) den[mt][nt] = MFMA16(af[mt][reg], R2[nt][reg], den[mt][nt]);
+                        }
                     if constexpr (t < 3) {
-                        nnf_lds_read4_after<((t + 1) * MT + mt) * 1024>(ak[mt], kb, num[mt][NT - 1]);
+                        nnf_lds_read4_after<((t + 1) * MT + mt) * 1024>(ak[mt], kb, (BM == BM_GEN ? den : num)[mt][NT - 1]);
                         if constexpr (mt == UVT)
                             nnf_static_for<0, REM>([&](auto rr) { nnf_lds_read4<(MT * 4 + t + 1) * 1024 + rr * 16>(vv[rr], ub); });
                     }
@@ -762,8 +808,13 @@ __global__ __launch_bounds__(256, MU_LEFT_WGPC(MT, REM, BM)) void nnf_mu_left_ke
     // the host picks the mix that fills whole rounds of resident workgroups (launch_mu_left)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = (int)blockIdx.x;
-    if (b < n_hi)
-        nnf_mu_left_body<MT, REM, BM, VEC, 4>(X, m, n, ldx, Ut, ldu, V, ldv, r, beta, den_vec, gamma, Ut_out, lduo, a_vec_ok,
+    if constexpr (MU_LEFT_ROWS128(MT, BM)) {
+        // ranks 65 .. 128, general beta: 128-row workgroups only (two row tiles per wave: 16 MT accumulator registers per set
+        // instead of 32 MT, and half the resident fragments -- this form holds its fragments in registers as well)
+        nnf_mu_left_body<MT, REM, BM, VEC, 2>(X, m, n, ldx, Ut, ldu, V, ldv, r, beta, den_vec, gamma, Ut_out, lduo, a_vec_ok,
+                                              (int64_t)b * 128, smem, ex);
+    } else if (MT <= 4 && b < n_hi)   // (MT > 4: four row tiles per wave do not fit the register file -- n_hi is 0)
+        nnf_mu_left_body<MT, REM, BM, VEC, MT <= 4 ? 4 : 3>(X, m, n, ldx, Ut, ldu, V, ldv, r, beta, den_vec, gamma, Ut_out, lduo, a_vec_ok,
                                               (int64_t)b * 256, smem, ex);
     else if (b < n_hi + n_mid)
         nnf_mu_left_body<MT, REM, BM, VEC, 3>(X, m, n, ldx, Ut, ldu, V, ldv, r, beta, den_vec, gamma, Ut_out, lduo, a_vec_ok,

@@ -401,10 +401,12 @@ class Engine:
         return status
 
     # ---- MU / beta-divergence -----------------------------------------------------------------------
-    MU_FUSED_MAX_RANK = 64   # the fused two-MFMA kernels are built for r <= 64 (beta = 2 has no limit: Gram form)
+    MU_FUSED_MAX_RANK = 64   # the fused COST forms (mu_left(cost_out=...), mu_left_num) are built for r <= 64
+    MU_FUSED_UPDATE_MAX_RANK = 128   # the fused two-MFMA updates: r <= 128 for every beta (beta = 2 has no limit: Gram form)
 
     def _mu_large_rank(self, X, Ut, V, beta, side):
-        """r > 64 (beta != 2) or r > 128 (any beta; the model then builds up over rank chunks inside R1): one pass writes the element-wise operands R1 = X.*(UV)^(beta-2), R2 = (UV)^(beta-1)
+        """r > 128 (any beta; the model then builds up over rank chunks inside R1; callable at any rank, which is how
+        tools/time_mu_rank.py times it against the fused kernels): one pass writes the element-wise operands R1 = X.*(UV)^(beta-2), R2 = (UV)^(beta-1)
         (m x n device scratch each), then the numerator / denominator are plain X H^T ('left') or W^T X ('right') products.
         Returns (num, den or None, den_vec or None) like mu_right_accum."""
         m, n = X.shape
@@ -439,7 +441,7 @@ class Engine:
                                                         r, _ptr(O), _ld(O), _ptr(cost_out), self._stream()),
                        "nnf_mu_left_kl_cost_f32")
             return O
-        if (r > self.MU_FUSED_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
+        if (r > self.MU_FUSED_UPDATE_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
             num, den, dvec = self._mu_large_rank(X, Ut, V, beta, "left")
             return self.mu_apply(Ut, num, den, dvec, beta, out=out)
         O = out if out is not None else torch.empty_like(Ut)
@@ -452,7 +454,7 @@ class Engine:
         _chk2d(X, "mu X"), _chk2d(Ut, "mu Ut"), _chk2d(V, "mu V")
         m, n = X.shape
         r = Ut.shape[0]
-        if (r > self.MU_FUSED_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
+        if (r > self.MU_FUSED_UPDATE_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
             num, den, dvec = self._mu_large_rank(X, Ut, V, beta, "right")
             return self.mu_apply(V, num, den, dvec, beta, out=out)
         O = out if out is not None else torch.empty_like(V)
@@ -467,7 +469,7 @@ class Engine:
         _chk2d(X, "mu X"), _chk2d(Ut, "mu Ut"), _chk2d(V, "mu V")
         m, n = X.shape
         r = Ut.shape[0]
-        if (r > self.MU_FUSED_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
+        if (r > self.MU_FUSED_UPDATE_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
             return self._mu_large_rank(X, Ut, V, beta, "right")
         num = torch.empty((r, n), dtype=torch.float32, device=X.device)
         den = torch.empty((r, n), dtype=torch.float32, device=X.device) if float(beta) != 1.0 else None

@@ -1,7 +1,9 @@
 """beta-divergence multiplicative updates on the MI355X engine -- drop-in for nn_fac/update_rules/mu.py:18-97.
 
 ``mu_betadivmin(U, V, M, beta)`` and ``switch_alternate_mu(data, U, V, beta, matrix)`` keep the reference signatures;
-the fused kernels (``nnf_mu_left_f32`` / ``nnf_mu_right_f32``) stream M once and never materialise U@V.
+the fused kernels (``nnf_mu_left_f32`` / ``nnf_mu_right_f32``) stream M once and never materialise U@V, for every beta up
+to rank 128 (no data-sized temporary); above 128 the engine composes the update from the ratio pass and plain contractions
+(m x n operands in device memory), beta = 2 runs the Gram form at any rank.
 """
 import torch
 
