@@ -28,6 +28,8 @@ from .utils import initialize_factors as init_factors
 from . import engine as _engine
 from ._convert import device_of, to_dev, to_dev_t, like_input
 from . import dist as _dist
+from . import _outer_loop as _loop
+from ._outer_loop import _SolveTimedOut, _IdentityUnreliable, _IdentityNearStop, _GuessMissed  # noqa: F401
 
 
 def nmf(data, rank, init="random", U_0=None, V_0=None, n_iter_max=100, tol=1e-8,
@@ -69,9 +71,8 @@ def compute_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8,
     X = to_dev(data, dev)
     Ut = to_dev_t(U_in, dev).clone()
     V = to_dev(V_in, dev).clone()
-    cost_fct_vals = []
-    tic = time.time()
-    toc = []
+    retired = _loop.Retired(tol, verbose=verbose, sweep_log=sweep_log, switch_message=(
+        '(cost evaluation switched to the pass over the data; last value {} re-evaluated: {})'))
 
     if sparsity_coefficients is None:
         sparsity_coefficients = [None, None]
@@ -82,45 +83,12 @@ def compute_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8,
 
     ws = _StepBuffers(X, Ut.shape[0])
 
-    def retired(iteration, cost, sweeps):
-        """Host side of one finished iteration (nmf.py:315-324); True = the stopping test fired."""
-        if sweep_log is not None:
-            sweep_log.extend(sweeps)
-        toc.append(time.time() - tic)
-        cost_fct_vals.append(cost)
-
-        if verbose:
-            if iteration == 0:
-                print('Normalized cost function value={}'.format(cost))
-            else:
-                if cost_fct_vals[-2] - cost_fct_vals[-1] > 0:
-                    print('Normalized cost function value={}, variation={}.'.format(
-                        cost_fct_vals[-1], cost_fct_vals[-2] - cost_fct_vals[-1]))
-                else:
-                    print('\033[91m' + 'Normalized cost function value={}, variation={}.'.format(
-                        cost_fct_vals[-1], cost_fct_vals[-2] - cost_fct_vals[-1]) + '\033[0m')
-
-        if iteration > 0 and abs(cost_fct_vals[-2] - cost_fct_vals[-1]) < tol:
-            if verbose:
-                print('Converged in {} iterations.'.format(iteration))
-            return True
-        return False
-
-    def revise_last(cost):
-        # the loop switched from the Gram-identity cost to the streaming kernel (run_steps): the last value is re-evaluated the
-        # same way, so that the variation printed next -- and the stopping test -- compare two costs of one kind
-        if verbose:
-            print('(cost evaluation switched to the pass over the data; last value {} re-evaluated: {})'.format(
-                cost_fct_vals[-1], cost))
-        cost_fct_vals[-1] = cost
-    retired.revise_last = revise_last
-
     Ut, V = run_steps(eng, ws, X, rank, Ut, V, n_iter_max, update_rule, beta, sparsity_coefficients, fixed_modes,
                       normalize, deterministic, retired, group=group, tol=tol)
 
     U_out, V_out = like_input(Ut.t(), U_in), like_input(V, V_in)
     if return_costs:
-        return U_out, V_out, cost_fct_vals, toc
+        return U_out, V_out, retired.cost_fct_vals, retired.toc
     return U_out, V_out
 
 
@@ -136,7 +104,7 @@ def one_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta,
                                        fixed_modes, normalize, deterministic)
     host = ws.block.cpu()
     cost = float(host[16])
-    _raise_on_status(host, nstat)
+    _loop.check_status(host, nstat)
     return like_input(Ut2.t(), U_in), like_input(V2, V_in), cost
 
 
@@ -144,12 +112,11 @@ def one_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta,
 PIPELINE_DEPTH = 1   # outer iterations enqueued ahead of the one whose cost the host is looking at
 
 
-class _StepBuffers:
+class _StepBuffers(_loop.StatusRing):
     """Device scratch reused across iterations (cross terms, Grams, status words)."""
 
     def select(self, slot):
-        self.slot = slot
-        self.block = self.blocks[slot]
+        super().select(slot)
         self.cost = self.block[16:17]
 
     def __init__(self, X, r, dtype=torch.float32):
@@ -168,22 +135,17 @@ class _StepBuffers:
         # one block read back per iteration: HALS status of the first / second solve at [0:8] / [8:16], cost at [16].
         # A ring of PIPELINE_DEPTH + 1 blocks with pinned host mirrors: run_steps enqueues iteration i+1 before it reads
         # the block of iteration i, so the device never waits for the host between iterations.
-        self.blocks = torch.zeros((PIPELINE_DEPTH + 2, 24), dtype=torch.float64, device=X.device)
-        self.host = torch.zeros((PIPELINE_DEPTH + 2, 24), dtype=torch.float64)
-        if X.is_cuda:
-            self.host = self.host.pin_memory()
-        self.select(0)
+        self.init_ring(PIPELINE_DEPTH + 2, 24, X.device)
         self.guess_u = _dist.SweepGuess()
         self.guess_v = _dist.SweepGuess()
         # Row-sharded U-side solve with the device-side stopping decision (dist.sharded_hals_solve_async): on by default over
-        # RCCL, NNF_SHARDED_ASYNC=0/1 forces it (dist.opt_in).  A missed guess costs a pipeline drain + a redone iteration, and the sweep counts of the first
-        # outer iterations jump by tens (33, 52, 67, 38, ... at config B), so it is engaged only once two consecutive solves
-        # differ by <= 4 sweeps (`async_ready`).  Validated for correctness (gloo world-size-2 tests, one-GPU kernel test);
+        # RCCL, NNF_SHARDED_ASYNC=0/1 forces it (dist.opt_in).  It is engaged only once two consecutive solves differ by <= 4
+        # sweeps (`async_ready`, _outer_loop.note_sweep_count).  Validated for correctness (gloo world-size-2 tests, one-GPU kernel test);
         # its gain needs one process per GPU to show -- with two ranks time-slicing ONE GPU (the only rehearsal available
         # here) the unsynchronised ranks starve each other's persistent V-side solves -- hence off over gloo.
         self.async_sharded = None         # decided by run_steps from the group (dist.opt_in)
         self.async_ready = False
-        self.last_u_count = None
+        self.last_count = None
         self.sync_next = False            # row-sharded: the next step uses the host-synchronous U-side protocol (after a redo)
         self.last_step_async = False
         self.async_hits = self.async_misses = 0
@@ -206,7 +168,7 @@ def _gram_on_side(ws, eng, A, out):
     Gram (V V^T: r x n) goes to the side stream: the Gram of the long one (U^T U, 20 MB at config B) took 82 us there next to
     W^T X instead of 5.4 us alone and cost that kernel 5 % (profiles/r02_B_kernel_stats.txt) -- it is launched in line, in
     front of W^T X (`inline=True`)."""
-    side = getattr(ws, "side_stream", None)
+    side = ws.side_stream
     if side is None or not isinstance(eng, _engine.Engine):
         eng.gram(A, out=out)
         return None
@@ -221,42 +183,6 @@ def _gram_on_side(ws, eng, A, out):
 def _sync(dev):
     if torch.device(dev).type == "cuda":
         torch.cuda.synchronize(dev)
-
-
-class _SolveTimedOut(Exception):
-    """A persistent HALS solve gave up waiting for its other workgroups (status word 1)."""
-
-
-class _IdentityUnreliable(Exception):
-    """HALS cost through the Gram identity (nnf_nmf_gram_cost_f32): the kernel's own error estimate is above 5e-4 of the
-    cost -- the residual is too small next to ||X||^2 for fp32 cross terms (an almost exact fit).  The iteration is redone
-    with the streaming cost kernel, and so is the rest of the run."""
-
-
-class _IdentityNearStop(_IdentityUnreliable):
-    """Two consecutive identity costs differ by the caller's `tol` give or take their error estimates."""
-
-
-class _GuessMissed(Exception):
-    """Row-sharded run: the blind chunk of the device-side protocol did not contain the stopping sweep in its snapshot window
-    (status words 3 / 4 of nnf_hals_stop_restore_f32): the iteration is redone with the host-synchronous protocol."""
-
-
-def _raise_on_status(host, nstat, timeout_ok=False, nranks=0):
-    """`nranks` > 0: a row-sharded run -- the error words are read from the copies that travelled with the cost's all-reduce
-    (dist.allreduce_cost_), so every rank sees the same code for the same iteration and takes the same branch: a time-out
-    is a rank-local event (the replicated V-side solve of ONE rank found the chip shared), and a rank that fell back to
-    chunked solves alone would issue a different sequence of collectives than its peers (a hang over RCCL)."""
-    for i in range(nstat):
-        code = _dist.agreed_code(host, i, nranks) if nranks else int(host[8 * i + _engine.ST_ERR])
-        if code == 2:
-            raise err.ZeroColumnWhenUnautorized("A column of U is zero with nonzero condition")
-        if code in (_dist.ERR_BEFORE_WINDOW, _dist.ERR_NOT_STOPPED):
-            raise _GuessMissed()
-        if code != 0:
-            if timeout_ok:
-                raise _SolveTimedOut()
-            raise err.EngineError("hals grid barrier timed out; result invalid")
 
 
 def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coefficients, fixed_modes, normalize,
@@ -322,96 +248,46 @@ def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coeff
     # (row-sharded: the kernel's sum covers this rank's rows; one scalar all-reduce before the block goes to the host)
     fused_mu = (cuda and update_rule == "mu" and float(beta) == 1.0 and 0 not in fixed_modes
                 and isinstance(eng, _engine.Engine) and Ut.shape[0] <= eng.MU_FUSED_MAX_RANK)
-    depth = PIPELINE_DEPTH + (1 if (overlap or fused_mu) else 0)
-    assert ws.blocks.shape[0] > depth
-    pending = []          # steps not yet handed to `retired`: dicts {it, slot, Ut, V, nstat, ev}
-    result = (Ut, V)
-    stop = False
     main = torch.cuda.current_stream(X.device) if cuda else None
+    nranks = _dist.world(group) if _dist.is_sharded(group) else 0
+    guard = _loop.IdentityGuard(tol)
+    owed = None           # overlap / fused_mu: the step whose cost has not been launched yet
+    costed = None         # overlap: the step whose cost was launched during the previous step
 
     def cost_of(step, stream):
         """Launch the cost of `step` (+ the copy of its status block to the host) on `stream`."""
-        block = ws.blocks[step["slot"]]
+        block = ws.blocks[step.slot]
+        Ut_s, V_s = step.result
         with torch.cuda.stream(stream):
             if stream is not main:
                 stream.wait_event(main.record_event())       # factors, status words of `step`: all enqueued on main
             if fused_mu:
                 # the last step's cost from the SAME kernel as every other cost of the run (an update whose output is
                 # dropped): a run stopped early and a run of exactly that many iterations give bitwise equal costs
-                eng.mu_left(X, step["Ut"], step["V"], beta, cost_out=block[16:17])
+                eng.mu_left(X, Ut_s, V_s, beta, cost_out=block[16:17])
                 _dist.allreduce_cost_(block, group)
             else:
-                _step_cost(ws.cost_eng if stream is not main else eng, X, step["Ut"], step["V"], update_rule, beta,
+                _step_cost(ws.cost_eng if stream is not main else eng, X, Ut_s, V_s, update_rule, beta,
                            sparsity_coefficients, block, group)
-            ws.host[step["slot"]].copy_(block, non_blocking=True)
-            step["ev"] = stream.record_event()
+            ws.host[step.slot].copy_(block, non_blocking=True)
+            step.event = stream.record_event()
 
-    last = None           # (cost, error estimate) of the last retired iterate while both came from the identity
-
-    def retire():
-        nonlocal result, stop, last
-        step = pending[0]
-        if step["ev"] is not None:
-            step["ev"].synchronize()
-        host = ws.host[step["slot"]]
-        _raise_on_status(host, step["nstat"], timeout_ok=not getattr(ws, "safe_solve", False),
-                         nranks=_dist.world(group) if _dist.is_sharded(group) else 0)
-        if step.get("ident"):
-            if float(host[20]) != 0.0:
-                raise _IdentityUnreliable()
-            c, e = float(host[19]), float(host[21])
-            if tol is not None and tol > 0 and last is not None and abs(last[0] - c) < tol + e + last[1]:
-                raise _IdentityNearStop()
-            last = (c, e)
-        pending.pop(0)                     # (a step that timed out stays at the head: run_steps resumes from it)
-        result = (step["Ut"], step["V"])
-        if group is not None and update_rule == "hals" and step["nstat"] >= 1 and 0 not in fixed_modes:
-            cnt_u = int(host[_engine.ST_CNT]) - 1
-            ws.async_ready = ws.last_u_count is not None and abs(cnt_u - ws.last_u_count) <= 4
-            ws.last_u_count = cnt_u
-        if step.get("async_u"):            # row-sharded, device-side protocol: centre the next blind chunk on this count
-            ws.async_hits += 1
-            ws.guess_u.value = max(8, min(int(host[_engine.ST_CNT]) - 1 + 4, ws.guess_u.max_chunk))
-        stop = bool(retired(step["it"], float(host[19 if step.get("ident") else 16]),
-                            [int(host[8 * i + _engine.ST_CNT]) - 1 for i in range(step["nstat"])]))
-
-    def drain():
-        if cuda:
-            main.synchronize()
-            if ws.cost_stream is not None:
-                ws.cost_stream.synchronize()
-
-    def fall_back():
-        """A persistent solve timed out: its workgroups were not all resident at once (another process's kernels hold CUs --
-        on a GPU this process owns alone that does not happen).  Everything in flight is dropped, and the loop resumes from
-        the last retired factors with every HALS solve going through the chunked fixed-count launches of dist.py -- no
-        workgroup of those waits for another, the stopping rule is applied between chunks (bitwise the same factors,
-        tests/test_dist_gloo.py) -- and the cost inside the step.  Slower (one host round trip per chunk), never wrong."""
-        nonlocal overlap, depth, owed, costed, stop
-        drain()
-        pending.clear()
-        ws.safe_solve = True
-        overlap, depth, owed, costed = False, PIPELINE_DEPTH, None, None
-        warnings.warn("nn_fac_amd: a persistent HALS solve timed out waiting for its workgroups (GPU shared with another "
-                      "process?); falling back to chunked launches for the rest of this run")
-
-    owed = None           # overlap: the step whose cost has not been launched yet
-    costed = None         # overlap: the step whose cost was launched during the previous step
-    iteration = 0
-    while iteration < n_iter:
+    def enqueue(iteration, factors):
+        nonlocal owed, costed
+        Ut, V = factors
         ws.select(iteration % ws.blocks.shape[0])
         hooks = {}
         if fused_mu and owed is not None:
-            hooks["mu_cost_out"] = ws.blocks[owed["slot"]][16:17]        # cost of the previous step, by-product of this left update
+            hooks["mu_cost_out"] = ws.blocks[owed.slot][16:17]        # cost of the previous step, by-product of this left update
         if overlap and owed is not None:
             hooks["before_v_solve"] = lambda prev=owed: cost_of(prev, ws.cost_stream)
         if overlap and costed is not None:
             # the cost launched during the previous step must be out of the way before this step's U-side solve
-            hooks["before_u_solve"] = lambda ev=costed["ev"]: main.wait_event(ev)
+            hooks["before_u_solve"] = lambda ev=costed.event: main.wait_event(ev)
         Ut, V, nstat = _one_nmf_step_dev(eng, ws, X, rank, Ut, V, update_rule, beta, sparsity_coefficients,
                                          fixed_modes, normalize, deterministic, group=group,
                                          skip_cost=overlap or fused_mu or ident, **hooks)
-        step = dict(it=iteration, slot=ws.slot, Ut=Ut, V=V, nstat=nstat, ev=None, async_u=ws.last_step_async, ident=ident)
+        step = _loop.Step(iteration, ws.slot, (Ut, V), nstat, async_solve=ws.last_step_async, ident=ident)
         ws.sync_next = False
         if ident:
             # words 19..21 of the block: {cost, 1 = not reliable, error estimate}; the V update's operands are still in place
@@ -420,71 +296,80 @@ def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coeff
             _add_sparsity_terms(Ut, V, sparsity_coefficients, ws.block[19:20], group)
             _dist.allreduce_errs_(ws.block, group)
             ws.host[ws.slot].copy_(ws.block, non_blocking=True)
-            step["ev"] = main.record_event()
+            step.event = main.record_event()
         elif fused_mu:
             if owed is not None:          # its cost has just been enqueued with this step's left update
-                _dist.allreduce_cost_(ws.blocks[owed["slot"]], group)
-                ws.host[owed["slot"]].copy_(ws.blocks[owed["slot"]], non_blocking=True)
-                owed["ev"] = main.record_event()
+                _dist.allreduce_cost_(ws.blocks[owed.slot], group)
+                ws.host[owed.slot].copy_(ws.blocks[owed.slot], non_blocking=True)
+                owed.event = main.record_event()
             owed = step
         elif overlap:
             costed = owed
             owed = step
         elif cuda:
             ws.host[ws.slot].copy_(ws.block, non_blocking=True)
-            step["ev"] = main.record_event()
+            step.event = main.record_event()
         else:
             ws.host[ws.slot].copy_(ws.block)
-        pending.append(step)
-        iteration += 1
-        try:
-            if len(pending) > depth:
-                retire()
-                if stop:
-                    break
-            if iteration == n_iter:
-                if (overlap or fused_mu) and not stop and owed is not None and owed["ev"] is None:
-                    cost_of(owed, main)               # the last step has no V-side solve behind it to hide under
-                while pending and not stop:
-                    retire()
-        except _SolveTimedOut:
-            failed = pending[0]["it"]             # the step being retired is still at the head of the list
-            fall_back()
-            Ut, V = result                        # factors of the last iteration that retired cleanly
-            iteration = failed
-        except _IdentityUnreliable:
-            failed = pending[0]["it"]
-            drain()
-            pending.clear()
-            if last is not None and hasattr(retired, "revise_last"):
-                # whichever test failed: the iterate before it was costed by the identity -- re-evaluate it too, so that the
-                # stopping test never compares a cost of one kind with a cost of the other
-                scratch = torch.zeros_like(ws.block)
-                _step_cost(eng, X, result[0], result[1], update_rule, beta, sparsity_coefficients, scratch, group)
-                retired.revise_last(float(scratch[16]))
-            last = None
-            ws.direct_cost = True                 # this iteration again, and every later one, with the streaming cost kernel
-            ident = False
-            overlap = (ws.cost_stream is not None
-                       and (not _dist.is_sharded(group) or _dist.opt_in("NNF_SHARDED_OVERLAP", group)))
-            depth = PIPELINE_DEPTH + (1 if overlap else 0)
-            owed = costed = None
-            Ut, V = result
-            iteration = failed
-        except _GuessMissed:
-            failed = pending[0]["it"]
-            drain()
-            pending.clear()
-            owed = costed = None
-            ws.sync_next = True                   # redo this iteration with the exact, host-synchronous protocol
-            ws.async_misses += 1
-            Ut, V = result
-            iteration = failed
-    if cuda and (pending or overlap):     # dropped speculative iterations still use the shared scratch: let them drain
-        main.synchronize()
-        if overlap:
-            ws.cost_stream.synchronize()
-    return result
+        return step
+
+    def cost_of_the_last_step():
+        if (overlap or fused_mu) and owed is not None and owed.event is None:
+            cost_of(owed, main)               # the last step has no V-side solve behind it to hide under
+
+    def settle(step):
+        host = ws.host[step.slot]
+        _loop.check_status(host, step.nstat, nranks=nranks, can_fall_back=not ws.safe_solve)
+        if step.ident:
+            guard.check(float(host[20]), float(host[19]), float(host[21]))
+        if group is not None and update_rule == "hals" and step.nstat >= 1 and 0 not in fixed_modes:
+            _loop.note_sweep_count(ws, ws.guess_u, int(host[_engine.ST_CNT]) - 1, step.async_solve)
+        return float(host[19 if step.ident else 16]), _loop.sweep_counts(host, step.nstat)
+
+    def overlap_again():
+        """Everything in flight was dropped: no cost is owed, and the depth follows the overlap."""
+        nonlocal owed, costed
+        owed = costed = None
+        loop.depth = PIPELINE_DEPTH + (1 if (overlap or fused_mu) else 0)
+
+    def fall_back(factors):
+        """A persistent solve timed out: its workgroups were not all resident at once (another process's kernels hold CUs --
+        on a GPU this process owns alone that does not happen).  Everything in flight is dropped, and the loop resumes from
+        the last retired factors with every HALS solve going through the chunked fixed-count launches of dist.py -- no
+        workgroup of those waits for another, the stopping rule is applied between chunks (bitwise the same factors,
+        tests/test_dist_gloo.py) -- and the cost inside the step.  Slower (one host round trip per chunk), never wrong."""
+        nonlocal overlap
+        ws.safe_solve = True
+        overlap = False
+        overlap_again()
+        warnings.warn("nn_fac_amd: a persistent HALS solve timed out waiting for its workgroups (GPU shared with another "
+                      "process?); falling back to chunked launches for the rest of this run")
+
+    def leave_identity(factors):
+        """This iteration again, and every later one, with the streaming cost kernel."""
+        nonlocal ident, overlap
+
+        def direct_cost():
+            scratch = torch.zeros_like(ws.block)
+            _step_cost(eng, X, factors[0], factors[1], update_rule, beta, sparsity_coefficients, scratch, group)
+            return float(scratch[16])
+        guard.switch(retired, direct_cost)
+        ws.direct_cost = True
+        ident = False
+        overlap = (ws.cost_stream is not None
+                   and (not _dist.is_sharded(group) or _dist.opt_in("NNF_SHARDED_OVERLAP", group)))
+        overlap_again()
+
+    def guess_missed(factors):
+        overlap_again()
+        ws.sync_next = True                   # redo this iteration with the exact, host-synchronous protocol
+        ws.async_misses += 1
+
+    loop = _loop.Pipeline(enqueue, settle, retired, [s for s in (main, ws.cost_stream) if s is not None],
+                          depth=PIPELINE_DEPTH + (1 if (overlap or fused_mu) else 0), before_flush=cost_of_the_last_step)
+    assert ws.blocks.shape[0] > loop.depth
+    loop.redo = {_SolveTimedOut: fall_back, _IdentityUnreliable: leave_identity, _GuessMissed: guess_missed}
+    return loop.run(n_iter, (Ut, V))
 
 
 # inner-solve settings of one_nmf_step (nmf.py:415-419,440-444: maxiter=100, delta=0.01).  bench.py's fixed-work line
@@ -641,7 +526,7 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
             else:
                 Ut = _hals_call(eng, ws.VMt, ws.G, Ut_in, sparsity_coefficients[0], normalize[0], deterministic, timer,
                                 ws.block[8 * nstat:8 * nstat + 8],
-                                safe=ws.guess_u if getattr(ws, "safe_solve", False) else None, guess=ws.guess_u)
+                                safe=ws.guess_u if ws.safe_solve else None, guess=ws.guess_u)
             nstat += 1
         else:
             if mu_cost_out is not None:                 # + beta_divergence(X, U_in V_in, 1): the previous iteration's cost
@@ -655,18 +540,14 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
             if not deterministic:
                 _sync(dev)
                 t0 = time.time()
-            ws.g64_ok = getattr(ws, "G64", None) is not None and isinstance(eng, _engine.Engine)
+            ws.g64_ok = ws.G64 is not None and isinstance(eng, _engine.Engine)
             if ws.g64_ok:
                 eng.gram(Ut, out=ws.G2, out64=ws.G64)   # UtU  (nmf.py:432) -- in line: see _gram_on_side; + its fp64 sums
             else:
                 eng.gram(Ut, out=ws.G2)
             eng.xty(X, Ut, out=ws.UtM)                  # UtM  (nmf.py:433)
             if sharded:                                 # sum over the row blocks: r x n and r x r over xGMI, one collective
-                if getattr(ws, "v_terms", None) is not None:
-                    _dist.allreduce_(ws.v_terms, group)
-                else:
-                    _dist.allreduce_(ws.G2, group)
-                    _dist.allreduce_(ws.UtM, group)
+                _dist.allreduce_(ws.v_terms, group)
                 if ws.g64_ok:                           # the fp64 sums of the Gram for the identity cost: r x r doubles
                     _dist.allreduce_(ws.G64, group)
             if not deterministic:
@@ -675,7 +556,7 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
             if before_v_solve is not None:
                 before_v_solve()
             V = _hals_call(eng, ws.UtM, ws.G2, V_in, sparsity_coefficients[1], normalize[1], deterministic, timer,
-                           ws.block[8 * nstat:8 * nstat + 8], safe=ws.guess_v if getattr(ws, "safe_solve", False) else None,
+                           ws.block[8 * nstat:8 * nstat + 8], safe=ws.guess_v if ws.safe_solve else None,
                            group=group if sharded else None, guess=ws.guess_v)
             nstat += 1
         else:

@@ -33,6 +33,7 @@ from .utils import initialize_factors as init_factors
 from . import engine as _engine
 from ._convert import device_of, to_dev, to_dev_t, like_input
 from .update_rules.nnls import sweep_budget
+from . import _outer_loop as _loop
 
 
 def ntd(tensor, ranks, init="random", core_0=None, factors_0=[], n_iter_max=100, tol=1e-6,
@@ -76,7 +77,7 @@ def ntd(tensor, ranks, init="random", core_0=None, factors_0=[], n_iter_max=100,
                        verbose=verbose, return_costs=return_costs, deterministic=deterministic, seed=seed)
 
 
-class _NtdState:
+class _NtdState(_loop.StatusRing):
     """Device-resident tensor, its squared norm, (MU only) the materialised unfoldings, and the per-step status block."""
 
     def __init__(self, eng, T):
@@ -93,15 +94,7 @@ class _NtdState:
         # pinned host mirrors: compute_ntd enqueues iteration i+1 before it looks at the block of iteration i
         self.pg_at = 8 * self.nway
         self.cost_at = self.pg_at + 6
-        self.blocks = torch.zeros((2, self.cost_at + 2), dtype=torch.float64, device=T.device)
-        self.host = torch.zeros((2, self.cost_at + 2), dtype=torch.float64)
-        if T.is_cuda:
-            self.host = self.host.pin_memory()
-        self.select(0)
-
-    def select(self, slot):
-        self.slot = slot
-        self.block = self.blocks[slot]
+        self.init_ring(2, self.cost_at + 2, T.device)
 
     def unfolded_t(self, mode):
         """tl.unfold(T, mode)^T as a contiguous (prod(other dims)) x I_mode matrix (MU path).  The last mode is a view of T;
@@ -399,51 +392,14 @@ def compute_ntd(tensor_in, ranks, core_in, factors_in, n_iter_max=100, tol=1e-6,
         normalize[-1] = False
     if not normalize[-1] and (mode_core_norm is not None and mode_core_norm >= 0 and mode_core_norm < nb_modes):
         print("The core was asked NOT to be normalized, but mode_core_norm was set to a valid norm. Is this a mistake?")
-    cost_fct_vals, toc = [], []
-    tic = time.time()
+    retired = _loop.Retired(tol, verbose=verbose, sweep_log=sweep_log)
     if update_rule not in ("hals", "mu"):
         raise err.InvalidArgumentValue(f"The update rule provided is not valid. Please choose between 'hals' and 'mu' (Got {update_rule}).")
     cuda = st.T.is_cuda
     main = torch.cuda.current_stream(st.T.device) if cuda else None
-    pending, stop = [], False
-    result = (core, Ft)
 
-    def retire():
-        """Host side of one finished iteration (ntd.py:410-428), one iteration behind the device."""
-        nonlocal result, stop
-        iteration, slot, core_i, Ft_i, nstat, ev = pending.pop(0)
-        if ev is not None:
-            ev.synchronize()
-        host = st.host[slot]
-        cost = float(host[st.cost_at])
-        for i in range(nstat):
-            if int(host[8 * i + _engine.ST_ERR]) != 0:
-                raise err.EngineError("hals grid barrier timed out; result invalid")
-        if sweep_log is not None:
-            sweep_log.extend(int(host[8 * i + _engine.ST_CNT]) - 1 for i in range(nstat))
-        if update_rule == "hals" and int(host[st.pg_at + 5]) != 0:
-            raise err.EngineError("NTD core update: grid barrier timed out; result invalid")
-        if pg_log is not None and update_rule == "hals":
-            pg_log.append(int(host[st.pg_at]))
-        result = (core_i, Ft_i)
-        toc.append(time.time() - tic)
-        cost_fct_vals.append(cost)
-        if verbose:
-            if iteration == 0:
-                print('Normalized cost function value={}'.format(cost))
-            else:
-                if cost_fct_vals[-2] - cost_fct_vals[-1] > 0:
-                    print('Normalized cost function value={}, variation={}.'.format(
-                        cost_fct_vals[-1], cost_fct_vals[-2] - cost_fct_vals[-1]))
-                else:
-                    print('\033[91m' + 'Normalized cost function value={}, variation={}.'.format(
-                        cost_fct_vals[-1], cost_fct_vals[-2] - cost_fct_vals[-1]) + '\033[0m')
-        if iteration > 0 and abs(cost_fct_vals[-2] - cost_fct_vals[-1]) < tol:
-            if verbose:
-                print('Converged in {} iterations.'.format(iteration))
-            stop = True
-
-    for iteration in range(n_iter_max):
+    def enqueue(iteration, model):
+        core, Ft = model
         st.select(iteration % 2)
         nstat = 0
         if update_rule == "hals":
@@ -452,20 +408,23 @@ def compute_ntd(tensor_in, ranks, core_in, factors_in, n_iter_max=100, tol=1e-6,
         else:
             core, Ft = _one_ntd_step_mu_dev(st, core, Ft, beta, fixed_modes, normalize, mode_core_norm)
         st.host[st.slot].copy_(st.block, non_blocking=cuda)
-        pending.append((iteration, st.slot, core, Ft, nstat, main.record_event() if cuda else None))
-        if len(pending) > 1:
-            retire()
-            if stop:
-                break
-    while pending and not stop:
-        retire()
-    if cuda and pending:
-        main.synchronize()
-    core, Ft = result
+        return _loop.Step(iteration, st.slot, (core, Ft), nstat, event=main.record_event() if cuda else None)
+
+    def settle(step):
+        """The block of one finished iteration (ntd.py:410-428), one iteration behind the device."""
+        host = st.host[step.slot]
+        _loop.check_status(host, step.nstat)
+        if update_rule == "hals" and int(host[st.pg_at + 5]) != 0:
+            raise err.EngineError("NTD core update: grid barrier timed out; result invalid")
+        if pg_log is not None and update_rule == "hals":
+            pg_log.append(int(host[st.pg_at]))
+        return float(host[st.cost_at]), _loop.sweep_counts(host, step.nstat)
+
+    core, Ft = _loop.Pipeline(enqueue, settle, retired, [main] if cuda else []).run(n_iter_max, (core, Ft))
     core_out = like_input(core, core_in)
     factors = [like_input(f.t(), factors_in[i]) for i, f in enumerate(Ft)]
     if return_costs:
-        return core_out, factors, cost_fct_vals, toc
+        return core_out, factors, retired.cost_fct_vals, retired.toc
     return core_out, factors
 
 
@@ -484,9 +443,7 @@ def one_ntd_step(tensor, ranks, in_core, in_factors, norm_tensor,
     core, Ft, nstat = _one_ntd_step_dev(st, core, Ft, sparsity_coefficients, fixed_modes, normalize, mode_core_norm,
                                         alpha, delta)
     host = st.block.cpu()
-    for i in range(nstat):
-        if int(host[8 * i + _engine.ST_ERR]) != 0:
-            raise err.EngineError("hals grid barrier timed out; result invalid")
+    _loop.check_status(host, nstat)
     return like_input(core, in_core), [like_input(f.t(), in_factors[i]) for i, f in enumerate(Ft)], float(host[st.cost_at])
 
 

@@ -33,6 +33,8 @@ from . import engine as _engine
 from ._convert import device_of, to_dev, to_dev_t, like_input
 from .update_rules.nnls import sweep_budget
 from . import dist as _dist
+from . import _outer_loop as _loop
+from ._outer_loop import _IdentityUnreliable, _IdentityNearStop, _GuessMissed  # noqa: F401
 
 
 def ntf(tensor, rank, init="random", factors_0=[], n_iter_max=100, tol=1e-8,
@@ -59,7 +61,7 @@ def ntf(tensor, rank, init="random", factors_0=[], n_iter_max=100, tol=1e-8,
                        verbose=verbose, return_costs=return_costs)
 
 
-class _NtfState:
+class _NtfState(_loop.StatusRing):
     """Device-resident tensor, its squared norm and (MU only) the materialised unfoldings.
 
     With `group` (torch.distributed process group) T is this rank's block of the LEADING mode and the mode-0
@@ -83,10 +85,10 @@ class _NtfState:
         self.guess0 = _dist.SweepGuess()
         # leading-mode-sharded runs: the mode-0 solve with the device-side stopping decision (dist.sharded_hals_solve_async),
         # as in the NMF step -- engaged once two consecutive solves differ by <= 4 sweeps, a missed guess redoes the
-        # iteration with the host-synchronous protocol (run_ntf_steps)
+        # iteration with the host-synchronous protocol (run_ntf_steps, _outer_loop.note_sweep_count)
         self.async_sharded = _dist.is_sharded(group) and _dist.opt_in("NNF_SHARDED_ASYNC", group)
         self.async_ready = self.sync_next = self.last_step_async = False
-        self.last_cnt0 = None
+        self.last_count = None
         self.async_hits = self.async_misses = 0
         self._unf = {}
         self.direct_cost = False           # set for the rest of a run once the Gram-identity cost was found unreliable
@@ -94,15 +96,7 @@ class _NtfState:
         # per-iteration status: one HALS status block per mode, then {cost, 1 = identity cost not reliable, its error
         # estimate} at [8 * nway ...]; a ring with pinned host mirrors (run_ntf_steps)
         self.cost_at = 8 * self.nway
-        self.blocks = torch.zeros((3, self.cost_at + 8), dtype=torch.float64, device=T.device)
-        self.host = torch.zeros((3, self.cost_at + 8), dtype=torch.float64)
-        if T.is_cuda:
-            self.host = self.host.pin_memory()
-        self.select(0)
-
-    def select(self, slot):
-        self.slot = slot
-        self.block = self.blocks[slot]
+        self.init_ring(3, self.cost_at + 8, T.device)
 
     def view3(self, mode, Ft):
         """Order-N tensors through the 3-way kernels: mode `mode` of T (I_0 x ... x I_{N-1}, C order) is mode m3 of a 3-way
@@ -355,43 +349,11 @@ def run_ntf_steps(st, rank, Ft, n_iter, update_rule, beta, sparsity_coefficients
     `retired.revise_last`, so that the stopping test only ever compares two costs of the same kind."""
     cuda = st.T.is_cuda
     main = torch.cuda.current_stream(st.T.device) if cuda else None
-    pending, result, stop = [], Ft, False
     ident = _identity_cost_applies(st, update_rule, fixed_modes)
-    last = None           # (cost, estimate) of the last retired iterate, normalised, while both came from the identity
-
-    def retire():
-        nonlocal result, stop, last
-        step = pending[0]
-        step["ev"].synchronize()
-        host = st.host[step["slot"]]
-        for i in range(step["nstat"]):
-            code = int(host[8 * i + _engine.ST_ERR])
-            if code in (_dist.ERR_BEFORE_WINDOW, _dist.ERR_NOT_STOPPED) and step["async0"]:
-                raise _GuessMissed()
-            if code != 0:
-                raise err.EngineError("hals grid barrier timed out; result invalid")
-        if step["ident"]:
-            if float(host[st.cost_at + 1]) != 0.0:
-                raise _IdentityUnreliable()
-            c, e = float(host[st.cost_at]) / norm2_host, float(host[st.cost_at + 2]) / norm2_host
-            if tol is not None and tol > 0 and last is not None and abs(last[0] - c) < tol + e + last[1]:
-                raise _IdentityNearStop()
-            last = (c, e)
-        pending.pop(0)
-        result = step["Ft"]
-        if _dist.is_sharded(st.group) and update_rule == "hals" and 0 not in fixed_modes and step["nstat"] >= 1:
-            cnt0 = int(host[_engine.ST_CNT]) - 1                  # the sharded mode-0 solve is the first status block
-            st.async_ready = st.last_cnt0 is not None and abs(cnt0 - st.last_cnt0) <= 4
-            st.last_cnt0 = cnt0
-            if step["async0"]:                                    # centre the next blind chunk on this count
-                st.async_hits += 1
-                st.guess0.value = max(8, min(cnt0 + 4, st.guess0.max_chunk))
-        stop = bool(retired(step["it"], float(host[st.cost_at]) / norm2_host,
-                            [int(host[8 * i + _engine.ST_CNT]) - 1 for i in range(step["nstat"])]))
-
+    guard = _loop.IdentityGuard(tol)
     norm2_host = float(st.norm2)       # (one read, before the loop: the blocks carry the un-normalised cost)
-    iteration = 0
-    while iteration < n_iter:
+
+    def enqueue(iteration, Ft):
         st.select(iteration % st.blocks.shape[0])
         st.last_step_async = False
         Ft, nstat = _one_ntf_step_dev(st, rank, Ft, update_rule, beta, sparsity_coefficients, fixed_modes, normalize,
@@ -399,67 +361,43 @@ def run_ntf_steps(st, rank, Ft, n_iter, update_rule, beta, sparsity_coefficients
         #                    iteration: every cost of a run comes from the same kernel, whatever n_iter_max -- bitwise repeatable)
         st.sync_next = False
         st.host[st.slot].copy_(st.block, non_blocking=cuda)
-        pending.append(dict(it=iteration, slot=st.slot, Ft=Ft, nstat=nstat, async0=st.last_step_async, ident=ident,
-                            ev=main.record_event() if cuda else _NoEvent()))
-        iteration += 1
-        try:
-            if len(pending) > 1:
-                retire()
-                if stop:
-                    break
-            if iteration == n_iter:
-                while pending and not stop:
-                    retire()
-        except _GuessMissed:
-            # the blind chunk of the device-side protocol missed the stopping sweep: drop what is in flight and redo this
-            # iteration with the exact, host-synchronous protocol (every rank takes this branch: the status is a function
-            # of all-reduced sums)
-            failed = pending[0]["it"]
-            if cuda:
-                main.synchronize()
-            pending.clear()
-            st.sync_next = True
-            st.async_misses += 1
-            Ft = result
-            iteration = failed
-        except _IdentityUnreliable:
-            # this iteration again, and every later one, with the pass over T (every rank: the words are replicated)
-            failed = pending[0]["it"]
-            main.synchronize()
-            pending.clear()
-            st.direct_cost, ident = True, False
-            Ft = result
-            iteration = failed
-            if last is not None and hasattr(retired, "revise_last"):
-                # whichever test failed, the iterate before it was costed by the identity: re-evaluate it too -- the stopping test
-                # then compares two costs of the same kind.  Its pass leaves the partial product the repeated iteration starts
-                # from (st.partial finds it)
-                tree = (st.nway == 3 and math.isinf(alpha) and 0 not in fixed_modes and 1 not in fixed_modes
-                        and hasattr(st.eng, "mttkrp3_from_partial"))
-                words = torch.zeros(3, dtype=torch.float64, device=st.T.device)
-                _ntf_cost(st.eng, st, Ft, update_rule, beta, sparsity_coefficients, words, fuse_next=tree, host_norm=True)
-                retired.revise_last(float(words[0]) / norm2_host)
-            last = None
-    if cuda and pending:
-        main.synchronize()
-    return result
+        return _loop.Step(iteration, st.slot, Ft, nstat, event=main.record_event() if cuda else None,
+                          async_solve=st.last_step_async, ident=ident)
 
+    def settle(step):
+        host = st.host[step.slot]
+        _loop.check_status(host, step.nstat)
+        cost = float(host[st.cost_at]) / norm2_host
+        if step.ident:
+            guard.check(float(host[st.cost_at + 1]), cost, float(host[st.cost_at + 2]) / norm2_host)
+        if _dist.is_sharded(st.group) and update_rule == "hals" and 0 not in fixed_modes and step.nstat >= 1:
+            # (the sharded mode-0 solve is the first status block)
+            _loop.note_sweep_count(st, st.guess0, int(host[_engine.ST_CNT]) - 1, step.async_solve)
+        return cost, _loop.sweep_counts(host, step.nstat)
 
-class _GuessMissed(Exception):
-    """Leading-mode-sharded run: the device-side stopping decision of the mode-0 solve missed (status 3 / 4)."""
+    def guess_missed(Ft):
+        # the blind chunk of the device-side protocol missed the stopping sweep: redo this iteration with the exact,
+        # host-synchronous protocol (every rank takes this branch: the status is a function of all-reduced sums)
+        st.sync_next = True
+        st.async_misses += 1
 
+    def leave_identity(Ft):
+        # this iteration again, and every later one, with the pass over T (every rank: the words are replicated)
+        nonlocal ident
+        st.direct_cost, ident = True, False
 
-class _IdentityUnreliable(Exception):
-    """The Gram-identity cost's own error estimate is above 5e-4 of the cost (an almost exact fit)."""
+        def direct_cost():
+            # its pass leaves the partial product the repeated iteration starts from (st.partial finds it)
+            tree = (st.nway == 3 and math.isinf(alpha) and 0 not in fixed_modes and 1 not in fixed_modes
+                    and hasattr(st.eng, "mttkrp3_from_partial"))
+            words = torch.zeros(3, dtype=torch.float64, device=st.T.device)
+            _ntf_cost(st.eng, st, Ft, update_rule, beta, sparsity_coefficients, words, fuse_next=tree, host_norm=True)
+            return float(words[0]) / norm2_host
+        guard.switch(retired, direct_cost)
 
-
-class _IdentityNearStop(_IdentityUnreliable):
-    """Two consecutive identity costs differ by `tol` give or take their error estimates: the stopping test needs better."""
-
-
-class _NoEvent:
-    def synchronize(self):
-        pass
+    loop = _loop.Pipeline(enqueue, settle, retired, [main] if cuda else [])
+    loop.redo = {_GuessMissed: guess_missed, _IdentityUnreliable: leave_identity}
+    return loop.run(n_iter, Ft)
 
 
 def compute_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8,
@@ -481,41 +419,13 @@ def compute_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8,
     if normalize is None or len(normalize) != nb_modes:
         print("Irrelevant number of normalization booleans (different from the number of modes), they have been set to False.")
         normalize = [False for i in range(nb_modes)]
-    cost_fct_vals, toc = [], []
-    tic = time.time()
-
-    def retired(iteration, cost, sweeps):
-        """Host side of one finished iteration (ntf.py:325-340); True = the stopping test fired."""
-        if sweep_log is not None:
-            sweep_log.extend(sweeps)
-        toc.append(time.time() - tic)
-        cost_fct_vals.append(cost)
-        if verbose:
-            if iteration == 0:
-                print('Normalized cost function value={}'.format(cost))
-            else:
-                if cost_fct_vals[-2] - cost_fct_vals[-1] > 0:
-                    print('Normalized cost function value={}, variation={}.'.format(
-                        cost_fct_vals[-1], cost_fct_vals[-2] - cost_fct_vals[-1]))
-                else:
-                    print('\033[91m' + 'Normalized cost function value={}, variation={}.'.format(
-                        cost_fct_vals[-1], cost_fct_vals[-2] - cost_fct_vals[-1]) + '\033[0m')
-        if iteration > 0 and abs(cost_fct_vals[-2] - cost_fct_vals[-1]) < tol:
-            if verbose:
-                print('Converged in {} iterations.'.format(iteration))
-            return True
-        return False
-
-    def revise_last(cost):
-        cost_fct_vals[-1] = cost
-    retired.revise_last = revise_last
-
+    retired = _loop.Retired(tol, verbose=verbose, sweep_log=sweep_log)
     Ft = run_ntf_steps(st, rank, Ft, n_iter_max, update_rule, beta, sparsity_coefficients, fixed_modes, normalize,
                        alpha, delta, retired, tol=tol)
     # the reference returns np.array(factors), which needs equal mode sizes on NumPy >= 1.24; a list always works
     factors = [like_input(f.t(), factors_in[i]) for i, f in enumerate(Ft)]
     if return_costs:
-        return factors, cost_fct_vals, toc
+        return factors, retired.cost_fct_vals, retired.toc
     return factors
 
 
