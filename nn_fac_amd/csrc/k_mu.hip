@@ -185,7 +185,9 @@ static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int
         const int rc = nnf_launch_rowsum(cur, Ut, ldu, r, m, num_out ? den_vec_out : dvec, st);
         if (rc != NNF_OK) return rc;
     }
-    const int64_t ws_max = (int64_t)(cur.remaining() / 4) / (slab_elems * nacc);
+    int64_t ws_max = (int64_t)(cur.remaining() / 4) / (slab_elems * nacc);
+    // (two slab sets: the second starts on the cursor's 256-byte boundary, which a set of r * ldp * nsplit floats need not end on)
+    while (nacc == 2 && ws_max >= 1 && nnf_rup(ws_max * slab_elems * 4, 256) + ws_max * slab_elems * 4 > (int64_t)cur.remaining()) --ws_max;
     if (ws_max < 1) return NNF_ERR_WORKSPACE;
     if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
     int64_t rps = nnf_rup(nnf_cdiv(m, nsplit), 64);

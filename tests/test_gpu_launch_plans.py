@@ -8,6 +8,12 @@ against the library's own report (NNF_PLAN_DEBUG), and test_plan_values checks e
 on the device, entry by entry, with the output pre-filled with NaN and the workspace slabs left over from a call on other
 data.
 
+The MU rows run up to rank 128: the kernels of five to eight rank tiles have launch forms of their own (128-row workgroups only,
+or a 192 / 128-row mix over rounds of at most 12 tiles; 128-column workgroups in the right update), and REQUIRED_BIG names what
+the rows with mt >= 5 must reach without the help of the rows below.  `mu_accum` is the accumulate-only form of the right update
+(nnf_mu_right_accum_f32): the same plans, the slabs reduced into num / den.  tests/test_mu_plan_table.py checks the MU rows
+against a Python restatement of the two launchers without a device.
+
 One branch is not reachable and has no case: launch_xht refuses the tail when 8 * extra > T, but a tail of four or more
 shares already needs extra <= 4 * (slots / parts) <= slots, and a one-round T is more than 8 * slots.
 """
@@ -47,6 +53,16 @@ def _halved(rows, ld):
 def _m_of(T, ragged=5):
     """A row count with cdiv(m, 16) == T and a ragged last tile."""
     return 16 * T - ragged
+
+
+def mu_right_prologue(r, m, beta):
+    """Workspace bytes launch_mu_right takes before its slabs: r doubles, for beta = 1 the r x np partials of the row sums of
+    Ut when m has np = min(m / 8192, 64) > 1 pieces, every block on the cursor's 256-byte alignment."""
+    off = r * 8
+    pieces = min(m // 8192, 64)
+    if beta == 1.0 and pieces > 1:
+        off = 256 * _cdiv(off, 256) + r * pieces * 8
+    return 256 * _cdiv(off, 256)
 
 
 def plan_cases(C):
@@ -154,6 +170,94 @@ def plan_cases(C):
         add(f"mu_left_gen_{form}", "mu_left", _m_of(T), 72, 50, dict(bm="GEN", form=form, mt=4, rem=0), beta=0.5)
     add("mu_left_frob_cp3", "cp3_partial_cost", 300 * 40, 70, 20, dict(bm="FROB"))
 
+    # ---- ranks 65 .. 128 (MT = 5 .. 8 rank tiles), left update.  KL at MT >= 6: one workgroup per CU, no 256-row workgroups;
+    # T <= 8 slots: 128-row workgroups; else W3 = whole rounds of at most 12 tiles: T <= 8 W3: 128-row workgroups again
+    # (rows128), else W3 workgroups of which cdiv(T - 8 W3, 4) take 192 rows.  Ranks 97 .. 100 on aligned X: six tiles + four
+    # leftover ranks ----
+    def left(name, T, n, r, form, mt, rem, vec, beta, grid=None, n_mid=0, ld=None):
+        m = _m_of(T)
+        add(name, "mu_left", m, n, r, dict(bm="KL" if beta == 1.0 else "GEN", form=form, mt=mt, rem=rem, vec=vec,
+                                           grid=_cdiv(m, 128) if grid is None else grid, n_hi=0, n_mid=n_mid), beta=beta, ld=ld)
+
+    s = C
+
+    def left_edges(tag, r, mt, rem, vec, full):
+        n, ld = (72, None) if vec else (70, 71)
+        if full:
+            left(f"mu_left_{tag}_small", 8 * s, n, r, "small", mt, rem, vec, 1.0, ld=ld)
+        left(f"mu_left_{tag}_mid_one", 8 * s + 1, n, r, "mid", mt, rem, vec, 1.0, grid=s, n_mid=1, ld=ld)
+        if full:
+            left(f"mu_left_{tag}_mid_one_full", 8 * s + 4, n, r, "mid", mt, rem, vec, 1.0, grid=s, n_mid=1, ld=ld)   # no spare tile
+        left(f"mu_left_{tag}_mid_all", 12 * s, n, r, "mid", mt, rem, vec, 1.0, grid=s, n_mid=s, ld=ld)   # no 128-row workgroup
+        left(f"mu_left_{tag}_rows128_lo", 12 * s + 1, n, r, "rows128", mt, rem, vec, 1.0, ld=ld)
+        left(f"mu_left_{tag}_rows128_hi", 16 * s, n, r, "rows128", mt, rem, vec, 1.0, ld=ld)
+        left(f"mu_left_{tag}_two_rounds", 16 * s + 1, n, r, "mid", mt, rem, vec, 1.0, grid=2 * s, n_mid=1, ld=ld)
+        if full:
+            left(f"mu_left_{tag}_three_rounds", 24 * s + 1, n, r, "mid", mt, rem, vec, 1.0, grid=3 * s, n_mid=1, ld=ld)
+
+    for r, mt, rem in [(96, 6, 0), (100, 6, 4), (112, 7, 0), (128, 8, 0)]:
+        left_edges(f"r{r}", r, mt, rem, 1, True)
+    left_edges("r100_unaligned", 100, 7, 0, 0, False)
+    left_edges("r128_unaligned", 128, 8, 0, 0, False)
+    # the six-tiles-and-four form holds for ranks 97 .. 100 only (rank 96 above: mt=6 rem=0)
+    left("mu_left_r97_mid_one", 8 * s + 1, 72, 97, "mid", 6, 4, 1, 1.0, grid=s, n_mid=1)
+    left("mu_left_r101_mid_one", 8 * s + 1, 72, 101, "mid", 7, 0, 1, 1.0, grid=s, n_mid=1)
+    left("mu_left_r101_rows128_lo", 12 * s + 1, 72, 101, "rows128", 7, 0, 1, 1.0)
+    # KL at MT = 5: two workgroups per CU, 128 rows each whatever the height
+    for r in (65, 80):
+        left(f"mu_left_r{r}_small", 8 * 2 * C, 72, r, "small", 5, 0, 1, 1.0)
+        left(f"mu_left_r{r}_rows128", 8 * 2 * C + 1, 72, r, "rows128", 5, 0, 1, 1.0)
+    # general beta: one workgroup per CU, 128 rows each
+    for r, mt in [(65, 5), (128, 8)]:
+        left(f"mu_left_r{r}_gen_small", 8 * C, 72, r, "small", mt, 0, 1, 0.5)
+        left(f"mu_left_r{r}_gen_rows128", 8 * C + 1, 72, r, "rows128", mt, 0, 1, 0.5)
+    left("mu_left_r128_gen_unaligned", 8 * C + 1, 70, 128, "rows128", 8, 0, 0, 0.5, ld=71)
+
+    # ---- ranks 65 .. 128, right update and its accumulate-only form: 128 columns per workgroup, one workgroup per CU in both
+    # beta forms: nsplit = C / cdiv(n, 128) ----
+    def right(name, m, n, r, beta, bound, nsplit, rps=None, kernel="mu_right", vec=1, rem=0, **kw):
+        rps = 64 * _cdiv(_cdiv(m, nsplit), 64) if rps is None else rps
+        add(name, kernel, m, n, r, dict(bm="KL" if beta == 1.0 else "GEN", bound=bound, nsplit=_cdiv(m, rps), rps=rps,
+                                        mt=(r + (0 if rem else 15)) // 16, rem=rem, vec=vec), beta=beta, **kw)
+
+    n_big = 128 * C + 200                   # more 128-column blocks than CUs: one split
+    # the fewest rows (in 64s) with (rows + 128) rows of X outside 32-bit offsets: halved once; 64 fewer: one split as it is
+    rows_off = 64 * _cdiv(_cdiv(0x7fff0000, 4 * n_big) - 128, 64)
+    m_off = rows_off - 37
+    assert _halved(m_off, n_big) == 64 * _cdiv(rows_off // 2, 64) and _halved(m_off - 64, n_big) == rows_off - 64
+    for r in (65, 128):
+        for beta in (1.0, 0.5 if r == 65 else 1.5):
+            tag = f"mu_right_r{r}_{'kl' if beta == 1.0 else 'gen'}"
+            nacc = 1 if beta == 1.0 else 2
+            right(f"{tag}_occupancy", 20000, 2000, r, beta, "occupancy", C // 16)
+            right(f"{tag}_min_rows", 1000, 1000, r, beta, "min_rows", _cdiv(1000, 64))            # C / 8 > 16 splits of 64 rows
+            # room for ten slabs (general beta: ten pairs, the second set behind the cursor's 256-byte alignment)
+            slabs = 10 * r * 2000 * 4
+            right(f"{tag}_workspace", 20000, 2000, r, beta, "workspace", 10,
+                  ws=mu_right_prologue(r, 20000, beta) + (nacc - 1) * 256 * _cdiv(slabs, 256) + slabs)
+            right(f"{tag}_one_split", 3000, n_big, r, beta, "occupancy", 1)
+            right(f"{tag}_offset32", m_off, n_big, r, beta, "offset32", None, rps=_halved(m_off, n_big))
+    right("mu_right_r128_kl_one_split_last", m_off - 64, n_big, 128, 1.0, "occupancy", 1)
+    # as many 64-row chunks as splits: still the occupancy bound
+    right("mu_right_r128_kl_occupancy_edge", 64 * (C // 16) - 10, 2000, 128, 1.0, "occupancy", C // 16, rps=64)
+    # four bytes short of ten slabs behind the row sums' partials: nine
+    right("mu_right_r128_kl_workspace_short", 20000, 2000, 128, 1.0, "workspace", 9,
+          ws=mu_right_prologue(128, 20000, 1.0) + 10 * 128 * 2000 * 4 - 4)
+    # ten pairs of rank-65 slabs to the byte: the second set starts 128 bytes further, nine pairs fit
+    assert (10 * 65 * 2000 * 4) % 256 == 128
+    right("mu_right_r65_gen_workspace_tight", 20000, 2000, 65, 0.5, "workspace", 9, ws=mu_right_prologue(65, 20000, 0.5) + 2 * 10 * 65 * 2000 * 4)
+    right("mu_right_r96_kl_occupancy", 20000, 2000, 96, 1.0, "occupancy", C // 16)            # six and seven rank tiles
+    right("mu_right_r112_gen_occupancy", 20000, 2000, 112, 0.5, "occupancy", C // 16)
+    right("mu_right_r128_kl_unaligned", 20000, 2000, 128, 1.0, "occupancy", C // 16, vec=0, ld=2001)
+    right("mu_right_r65_gen_unaligned", 20000, 2000, 65, 0.5, "occupancy", C // 16, vec=0, ld=2001)
+    # nnf_mu_right_accum_f32: the same plans, the slabs reduced into num / den instead of the finished update
+    right("mu_accum_r50_kl", 20000, 2000, 50, 1.0, "occupancy", 2 * C // 8, kernel="mu_accum", rem=2)
+    right("mu_accum_r50_gen", 20000, 2000, 50, 0.5, "occupancy", C // 8, kernel="mu_accum")
+    right("mu_accum_r100_kl", 20000, 2000, 100, 1.0, "occupancy", C // 16, kernel="mu_accum")
+    right("mu_accum_r100_gen", 20000, 2000, 100, 1.5, "occupancy", C // 16, kernel="mu_accum")
+    right("mu_accum_r100_gen_workspace", 20000, 2000, 100, 0.5, "workspace", 10, kernel="mu_accum",
+          ws=mu_right_prologue(100, 20000, 0.5) + 2 * 10 * 100 * 2000 * 4)
+
     # ---- Gram (launch_gram, launch_gram_blocks) ----
     add("gram_small", "gram", 1000, None, 50, dict(form="small"))
     add("gram_single_rank100", "gram", 1000, None, 100, dict(form="single", bound="short"))
@@ -189,6 +293,22 @@ REQUIRED = {("xht", "form"): {"lds", "small", "round32", "round43", "rounds", "t
             ("mu_right", "bound"): {"occupancy", "workspace", "offset32"},
             ("mu_right", "bm"): {"KL", "GEN"},
             ("cost", "NN"): {"4", "8"}, ("cost", "vdb"): {"0", "1"}, ("cost", "VEC"): {"0", "1"}}
+# what the cases at ranks 65 .. 128 (report lines with mt >= 5) must reach on their own
+REQUIRED_BIG = {("mu_left", "mt"): set("5678"), ("mu_right", "mt"): set("5678"),
+                ("mu_left", "form"): {"small", "mid", "rows128"}, ("mu_left", "rem"): {"0", "4"},
+                ("mu_left", "bm"): {"KL", "GEN"}, ("mu_right", "bm"): {"KL", "GEN"},
+                ("mu_left", "vec"): {"0", "1"}, ("mu_right", "vec"): {"0", "1"},
+                ("mu_right", "bound"): {"occupancy", "min_rows", "workspace", "offset32"}}
+TAG_KEYS = ("form", "bound", "bm", "NN", "vdb", "VEC", "tiling", "mt", "rem", "vec")
+
+
+def note_plan(seen, seen_big, launcher, kv):
+    """Adds the tags of one report line to `seen`, and to `seen_big` when the line is a MU plan of five or more rank tiles."""
+    for key in TAG_KEYS:
+        if key in kv:
+            seen[(launcher, key)].add(str(kv[key]))
+            if launcher in ("mu_left", "mu_right") and int(kv["mt"]) >= 5:
+                seen_big[(launcher, key)].add(str(kv[key]))
 
 
 def _cus():
@@ -214,6 +334,32 @@ def make_inputs(case, seed, dev="cuda"):
     Ut = torch.rand(r, m, device=dev, generator=g) + 0.05
     V = torch.rand(r, n, device=dev, generator=g) + 0.05
     return {"X": X, "Ut": Ut, "V": V}
+
+
+def mu_right_terms_fp64(X, Ut, V, beta):
+    """(num, den) of the right update in fp64, U^T (K^(beta-2) .* X) and U^T K^(beta-1) (beta = 1: den[k] = sum_i U[i, k], a
+    vector), summed over row blocks of at most 2^25 entries of X (an fp64 copy of the widest X at once is 4 GB)."""
+    V64 = V.double()
+    num = torch.zeros(V.shape, dtype=torch.float64, device=V.device)
+    den = torch.zeros(V.shape, dtype=torch.float64, device=V.device)
+    step = max(64, (1 << 25) // X.shape[1])
+    for i0 in range(0, X.shape[0], step):
+        U64, X64 = Ut[:, i0:i0 + step].double(), X[i0:i0 + step].double()
+        K = U64.t() @ V64
+        num += U64 @ (K ** (beta - 2) * X64)
+        if beta != 1:
+            den += U64 @ K ** (beta - 1)
+    return num, (Ut.double().sum(dim=1) if beta == 1 else den)
+
+
+def mu_accum_into(eng, inp, beta, num, den, dvec):
+    """nnf_mu_right_accum_f32 on caller-owned outputs (Engine.mu_right_accum allocates its own)."""
+    from nn_fac_amd.engine import _ld, _ptr
+    X, Ut, V = inp["X"], inp["Ut"], inp["V"]
+    st = eng.lib.nnf_mu_right_accum_f32(eng.ctx, _ptr(X), X.shape[0], X.shape[1], _ld(X), _ptr(Ut), _ld(Ut), _ptr(V), _ld(V),
+                                        Ut.shape[0], float(beta), _ptr(num), _ld(num), _ptr(den), _ld(den), _ptr(dvec),
+                                        eng._stream())
+    assert st == 0, st
 
 
 def gamma_beta(beta):
@@ -280,6 +426,8 @@ def run_case(eng, case, inp, out=None, cost_out=None):
         return eng.mu_left(inp["X"], inp["Ut"], inp["V"], case.beta, out=out, cost_out=cost_out)
     if k == "mu_right":
         return eng.mu_right(inp["X"], inp["Ut"], inp["V"], case.beta, out=out)
+    if k == "mu_accum":
+        return eng.mu_right_accum(inp["X"], inp["Ut"], inp["V"], case.beta)
     if k == "cost":
         return eng.betadiv(inp["X"], inp["Ut"], inp["V"], case.beta, out=out)
     if k == "cp3_partial_cost":
@@ -319,7 +467,7 @@ for name, case in cases.items():
     eng = P.engine_for(case)
     cost = torch.empty(1, dtype=torch.float64, device="cuda")
     P.run_case(eng, case, inp, cost_out=cost if case.kernel == "cp3_partial_cost" else None)
-    if case.kernel == "mu_left" and case.beta == 1.0:
+    if P.has_fused_cost(case):
         P.run_case(eng, case, inp, cost_out=cost)
     torch.cuda.synchronize()
     del inp
@@ -350,7 +498,12 @@ def reported(built_lib):
 
 
 def _launcher_of(case):
-    return {"cost": "cost", "cp3_partial_cost": "mu_left"}.get(case.kernel, case.kernel)
+    return {"cost": "cost", "cp3_partial_cost": "mu_left", "mu_accum": "mu_right"}.get(case.kernel, case.kernel)
+
+
+def has_fused_cost(case):
+    """The KL left update has a second form that carries the cost, up to rank 64 (test_fused_kl_cost_rank_limit)."""
+    return case.kernel == "mu_left" and case.beta == 1.0 and case.r <= 64
 
 
 def test_plan_table(reported):
@@ -358,11 +511,11 @@ def test_plan_table(reported):
     a whole reaches every form and bound tag of the launchers."""
     cases = plan_cases(_cus())
     assert sorted(reported) == sorted(cases)
-    seen = collections.defaultdict(set)
+    seen, seen_big = collections.defaultdict(set), collections.defaultdict(set)
     bad = []
     for name, case in cases.items():
         lines = [kv for (l, kv) in reported[name] if l == _launcher_of(case)]
-        calls = 2 if case.kernel == "mu_left" and case.beta == 1.0 else 1
+        calls = 2 if has_fused_cost(case) else 1
         if len(lines) != calls:
             bad.append((name, "report lines", reported[name]))
             continue
@@ -376,9 +529,7 @@ def test_plan_table(reported):
             if klc.get("bm") != "KLC" or {k: v for k, v in klc.items() if k != "bm"} != {k: v for k, v in kv.items() if k != "bm"}:
                 bad.append((name, "KLC plan", klc, kv))
         for l, kvs in reported[name]:
-            for key in ("form", "bound", "bm", "NN", "vdb", "VEC", "tiling"):
-                if key in kvs:
-                    seen[(l, key)].add(kvs[key])
+            note_plan(seen, seen_big, l, kvs)
         if case.kernel == "xht" and int(kv["tail_parts"]) > 0:
             seen[("xht", "tail_parts")].add(kv["tail_parts"])
         if case.kernel == "cost":
@@ -386,9 +537,12 @@ def test_plan_table(reported):
     assert not bad, "\n".join(map(str, bad))
     for key, want in REQUIRED.items():
         assert want <= seen[key], (key, want - seen[key])
+    for key, want in REQUIRED_BIG.items():
+        assert want <= seen_big[key], ("mt >= 5", key, want - seen_big[key])
     assert {"4", "8", "16", "32"} <= seen[("xht", "tail_parts")]
     assert seen[("cost", "csplit")] == {"1", ">1"}
     print("reached:", {f"{l}.{k}": sorted(v) for (l, k), v in sorted(seen.items())})
+    print("reached at mt >= 5:", {f"{l}.{k}": sorted(v) for (l, k), v in sorted(seen_big.items())})
 
 
 # ---- values ----
@@ -422,6 +576,19 @@ def test_plan_values(name, built_lib):
         want = float(((T64 - torch.einsum("ri,rj,rk->ijk", *F)) ** 2).sum())
         assert abs(float(cost) - want) <= 1e-5 * want, (float(cost), want)
         return
+    if k == "mu_accum":
+        want_num, want_den = mu_right_terms_fp64(inp["X"], inp["Ut"], inp["V"], case.beta)
+        run_case(eng, case, other_data(case, inp))
+        num, den = (torch.full((case.r, case.n), float("nan"), device="cuda") for _ in range(2))
+        dvec = torch.full((case.r,), float("nan"), dtype=torch.float64, device="cuda")
+        mu_accum_into(eng, inp, case.beta, num, den, dvec)
+        assert_close(num, want_num, 2e-5, 1e-3, name + " num")
+        if case.beta == 1:      # den[k] in fp64 from fp32 entries: only the order of the m additions differs
+            assert float(((dvec - want_den).abs() / want_den).max()) <= 1e-12 and bool(torch.isnan(den).all())
+        else:
+            assert_close(den, want_den, 2e-5, 1e-3, name + " den")
+            assert bool(torch.isnan(dvec).all())
+        return
     if k == "xht":
         want = inp["V"].double() @ inp["X"].double().t()
     elif k == "xty":
@@ -430,6 +597,11 @@ def test_plan_values(name, built_lib):
         want = inp["A"].double() @ inp["A"].double().t()
     elif k == "mu_left":
         want = mu_left_fp64(inp["X"], inp["Ut"], inp["V"], case.beta)
+    elif case.r > 64:       # (the widest X: fp64 in row blocks)
+        num, den = mu_right_terms_fp64(inp["X"], inp["Ut"], inp["V"], case.beta)
+        ratio = num / (den[:, None] if case.beta == 1 else den)
+        want = torch.clamp(inp["V"].double() * ratio ** gamma_beta(case.beta), min=1e-12)
+        del num, den, ratio
     else:
         want = mu_right_fp64(inp["X"], inp["Ut"], inp["V"], case.beta)
     out = torch.empty(want.shape, dtype=torch.float32, device="cuda")
@@ -442,7 +614,7 @@ def test_plan_values(name, built_lib):
 
 
 # ---- the fused KL cost of the left update (nnf_mu_left_kl_cost_f32) ----
-KL_CASES = [nm for nm in CASE_NAMES if nm.startswith("mu_left") and plan_cases(256)[nm].beta == 1.0]
+KL_CASES = [nm for nm in CASE_NAMES if has_fused_cost(plan_cases(256)[nm])]
 
 
 @pytest.mark.parametrize("name", KL_CASES)

@@ -17,11 +17,17 @@ import nnfac_oracle as orc
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RANKS = [65, 80, 81, 96, 97, 100, 112, 113, 127, 128]      # both edges of every 16-rank tile from the fifth to the eighth
+# both edges of every 16-rank tile from the fifth to the eighth; both sides of the last tile's 2-or-4-step flag (r % 16 == 8 / 9:
+# 72 / 73, 88 / 89, 104 / 105, 120 / 121) and ranks that are no multiple of 4 (70, 126)
+RANKS = [65, 70, 72, 73, 80, 81, 88, 89, 96, 97, 100, 104, 105, 112, 113, 120, 121, 126, 127, 128]
+EDGE_RANKS = (65, 100, 128)
 BETAS = [0, 0.5, 1, 1.5, 3, 4]
 # (m, n, floats of NaN padding behind every row): aligned rows / n % 4 != 0 behind a 5-float padding / fewer than 16 rows /
 # fewer than 16 columns behind an aligned padding
 SHAPES = [(260, 132, 0), (150, 71, 5), (11, 203, 0), (203, 9, 7)]
+# at EDGE_RANKS: the 128-column workgroups and 32-column waves of the right kernel and the 64-column chunks of the left one, at
+# one, two and one-and-a-half 128-row workgroups; rows as they come (m = 70), padded to aligned rows (129), behind 7 floats (193)
+EDGE_SHAPES = [(m, n, {70: 0, 129: -n % 4, 193: 7}[m]) for m in (70, 129, 193) for n in (1, 31, 32, 33, 127, 128, 129)]
 
 
 @pytest.fixture(scope="module")
@@ -87,7 +93,7 @@ def abi_calls(eng, Xd, Utd, Vd, r, beta):
 def test_abi_takes_ranks_65_to_128(eng, r, beta):
     """Every entry point returns NNF_OK and matches an fp64 evaluation of mu.py:84-97 (outputs pre-filled with NaN; ragged
     shapes, unaligned rows, NaN in the padding between rows)."""
-    for m, n, pad in SHAPES:
+    for m, n, pad in SHAPES + (EDGE_SHAPES if r in EDGE_RANKS else []):
         X, U, V = problem(m, n, r, 1000 * r + m + n)
         Xd, Utd, Vd = padded(X, pad), padded(U.T.copy(), pad), padded(V, pad)
         rc, Uo, Vo, num, den, dvec = abi_calls(eng, Xd, Utd, Vd, r, beta)
@@ -103,6 +109,26 @@ def test_abi_takes_ranks_65_to_128(eng, r, beta):
         else:
             close(den.cpu().numpy(), U.T @ K ** (beta - 1.0), ("accum den", tag))
             assert torch.isnan(dvec).all()
+
+
+@pytest.mark.parametrize("r", [65, 100, 121])
+@pytest.mark.parametrize("beta", [1, 0.5])
+def test_factor_rows_beyond_the_rank_are_not_read(eng, r, beta):
+    """Ut and V as the first r rows of buffers with 16 ceil(r / 16) + 8 rows whose other rows hold NaN: the rank tiles are padded
+    with zeros, never with the rows that follow in memory.  All three entry points, bit for bit what exact-size factors give."""
+    for m, n, pad in [(260, 132, 0), (150, 71, 0)]:          # (aligned X: rank 100 as six tiles + four ranks; unaligned: seven tiles)
+        X, U, V = problem(m, n, r, 7 * r + m)
+        Xd = padded(X, pad)
+        exact = abi_calls(eng, Xd, dev(U.T), dev(V), r, beta)
+        rows = 16 * math.ceil(r / 16) + 8
+        Ub, Vb = nan_like(rows, m), nan_like(rows, n)
+        Ub[:r], Vb[:r] = dev(U.T), dev(V)
+        view = abi_calls(eng, Xd, Ub[:r], Vb[:r], r, beta)
+        assert exact[0] == view[0] == [0, 0, 0]
+        for a, b, what in zip(exact[1:4], view[1:4], ("left", "right", "accum num")):
+            assert torch.isfinite(b).all() and torch.equal(a, b), (what, m, n)
+        a, b = (exact[5], view[5]) if beta == 1 else (exact[4], view[4])
+        assert torch.isfinite(b).all() and torch.equal(a, b), ("accum den", m, n)
 
 
 @pytest.mark.parametrize("beta", [1, 0.5])
@@ -276,3 +302,110 @@ def test_two_calls_are_bitwise_equal(eng, beta):
     a, b = eng.mu_right_accum(X, Ut, V, beta), eng.mu_right_accum(X, Ut, V, beta)
     for x, y in zip(a, b):
         assert (x is None and y is None) or torch.equal(x, y)
+
+
+# ---- 32-bit offsets: the strides the launchers refuse, and the last ones they take ----
+LIM = 0x7fff0000
+
+
+def _last_stride(mt, length):
+    """(ok, bad): the largest row stride of the staged factor with 16 (MT + 1) ld 4 + 4 (length + 128) < LIM -- the chunk images
+    address MT + 1 tiles of 16 rows from one 32-bit offset -- and the next multiple of 4 above it."""
+    ok = (LIM - 4 * (length + 128) - 1) // (64 * (mt + 1))
+    assert 64 * (mt + 1) * ok + 4 * (length + 128) < LIM <= 64 * (mt + 1) * (ok + 1) + 4 * (length + 128)
+    return ok, 4 * (ok // 4 + 1)
+
+
+def _strided(buf, rows, cols, ld, values):
+    """`values` as a rows x cols view of row stride ld into the NaN-filled flat buffer."""
+    buf.fill_(float("nan"))
+    view = buf.as_strided((rows, cols), (ld, 1))
+    view.copy_(values)
+    return view
+
+
+def _wrappers_refuse(eng, names, X, Ut, V, beta):
+    from nn_fac_amd.engine import EngineError
+    for name in names:
+        with pytest.raises(EngineError, match=r"status -3 "):       # NNF_ERR_UNSUPPORTED: no composed route behind it
+            getattr(eng, name)(X, Ut, V, beta)
+
+
+@pytest.mark.parametrize("r", [64, 65, 128])
+@pytest.mark.parametrize("beta", [1, 0.5])
+def test_right_update_factor_stride_limit(eng, r, beta):
+    """nnf_mu_right_f32 and nnf_mu_right_accum_f32 stage Ut through LDS: the largest stride they take (and the largest that
+    keeps 16-byte loads) against fp64, the next multiple of 4 refused with NNF_ERR_UNSUPPORTED and nothing written.  The
+    wrappers raise: a stride of millions of floats under a factor a few hundred wide is no layout the drivers produce, and
+    the composed route (m x n scratch, two more passes) behind a refusal would hide it.  Device memory: the factor's buffer, 2.15 GB at
+    every rank (16 (MT + 1) rows of the limit stride, by its size; not read from the allocator's peak)."""
+    import test_gpu_launch_plans as plans
+    m, n, mt = 300, 72, -(-r // 16)
+    ok, bad = _last_stride(mt, m)
+    X, Ut0, V = _device_problem(m, n, r, 3 * r)
+    buf = torch.empty(16 * (mt + 1) * bad, device="cuda")       # (every row a chunk image could address: NaN, not foreign memory)
+    want_num, want_den = plans.mu_right_terms_fp64(X, Ut0, V, beta)
+    want = plans.mu_right_fp64(X, Ut0, V, beta)
+    for ld in sorted({ok, ok - ok % 4}):
+        Ut = _strided(buf, r, m, ld, Ut0)
+        rc, _, Vo, num, den, dvec = abi_calls(eng, X, Ut, V, r, beta)
+        assert rc == [0, 0, 0], (ld, rc)
+        plans.assert_close(Vo, want, 2e-5, 1e-3, ("right", ld))
+        plans.assert_close(num, want_num, 2e-5, 1e-3, ("accum num", ld))
+        if beta == 1:
+            assert float(((dvec - want_den).abs() / want_den).max()) <= 1e-12
+        else:
+            plans.assert_close(den, want_den, 2e-5, 1e-3, ("accum den", ld))
+    Ut = _strided(buf, r, m, bad, Ut0)
+    rc, Uo, Vo, num, den, dvec = abi_calls(eng, X, Ut, V, r, beta)
+    assert rc == [0, -3, -3], rc                       # (the left update reads Ut directly: no limit on ldu)
+    plans.assert_close(Uo, plans.mu_left_fp64(X, Ut0, V, beta), 2e-5, 1e-3, ("left", bad))
+    for t in (Vo, num, den, dvec):
+        assert torch.isnan(t).all()
+    _wrappers_refuse(eng, ("mu_right", "mu_right_accum"), X, Ut, V, beta)
+
+
+@pytest.mark.parametrize("r", [64, 65, 128])
+@pytest.mark.parametrize("beta", [1, 0.5])
+def test_left_update_factor_stride_limit(eng, r, beta):
+    """The same for nnf_mu_left_f32 and the stride of V.  Device memory as above."""
+    import test_gpu_launch_plans as plans
+    m, n, mt = 300, 72, -(-r // 16)
+    ok, bad = _last_stride(mt, n)
+    X, Ut, V0 = _device_problem(m, n, r, 5 * r)
+    buf = torch.empty(16 * (mt + 1) * bad, device="cuda")
+    want = plans.mu_left_fp64(X, Ut, V0, beta)
+    for ld in sorted({ok, ok - ok % 4}):
+        V = _strided(buf, r, n, ld, V0)
+        rc, Uo, _, _, _, _ = abi_calls(eng, X, Ut, V, r, beta)
+        assert rc == [0, 0, 0], (ld, rc)
+        plans.assert_close(Uo, want, 2e-5, 1e-3, ("left", ld))
+    V = _strided(buf, r, n, bad, V0)
+    rc, Uo, Vo, _, _, _ = abi_calls(eng, X, Ut, V, r, beta)
+    assert rc == [-3, 0, 0], rc                        # (the right update reads V directly: no limit on ldv)
+    assert torch.isnan(Uo).all()
+    plans.assert_close(Vo, plans.mu_right_fp64(X, Ut, V0, beta), 2e-5, 1e-3, ("right", bad))
+    _wrappers_refuse(eng, ("mu_left",), X, Ut, V, beta)
+
+
+@pytest.mark.parametrize("r,beta", [(64, 1), (65, 1), (100, 1), (128, 1), (128, 0.5)])
+def test_left_update_x_stride_limit(eng, r, beta):
+    """The left kernel addresses 64 rows of X from one 32-bit offset: 64 ldx 4 + 4 (n + 128) < LIM.  200 rows of a NaN-filled
+    buffer at the last stride taken (a multiple of 4: 16-byte loads) and the one below it against fp64, the next one refused.
+    Device memory: the buffer under X, 8.6 GB by its size."""
+    import test_gpu_launch_plans as plans
+    m, n = 200, 72
+    ok = (LIM - 4 * (n + 128) - 1) // 256
+    assert ok % 4 == 0 and 256 * ok + 4 * (n + 128) < LIM <= 256 * (ok + 1) + 4 * (n + 128)
+    X0, Ut, V = _device_problem(m, n, r, 7 * r)
+    buf = torch.empty(256 * (ok + 1), device="cuda")            # (whole 128-row workgroups)
+    want = plans.mu_left_fp64(X0, Ut, V, beta)
+    for ld in (ok - 1, ok):
+        X = _strided(buf, m, n, ld, X0)
+        rc = abi_calls(eng, X, Ut, V, r, beta)
+        assert rc[0][0] == 0, (ld, rc[0])
+        plans.assert_close(rc[1], want, 2e-5, 1e-3, ("left", ld))
+    X = _strided(buf, m, n, ok + 1, X0)
+    rc = abi_calls(eng, X, Ut, V, r, beta)
+    assert rc[0][0] == -3 and torch.isnan(rc[1]).all(), rc[0]
+    _wrappers_refuse(eng, ("mu_left",), X, Ut, V, beta)
