@@ -402,48 +402,29 @@ static int launch_seg(nnf_ctx* ctx, const float* T, int64_t nrows, int64_t ldrow
     return nnf_launch_reduce_slabs(slabs, (int)nsplit, slab_elems, r, nrows, ldp, out, ldo, st);
 }
 
+// plan (k_stream_plan.h; a refusal launches nothing), report, carve, launch, reduce
 template <int MT, bool VEC>
 static int launch_rows(nnf_ctx* ctx, const float* M, int64_t m, int64_t n, const float* Fa, int64_t lda, const float* Fb,
                        int64_t ldb, int64_t nb, int r, float* out, int64_t ldo, hipStream_t st) {
-    const int ncb = (int)nnf_cdiv(n, 256);
-    const int64_t ldp = nnf_rup(n, 4);
-    int64_t nsplit = 2 * (int64_t)ctx->num_cus / ncb;
-    const char* bound = "occupancy";      // (report only, NNF_PLAN_DEBUG)
-    if (nsplit < 1) nsplit = 1;
-    const int64_t max_split = nnf_cdiv(m, 64);
-    if (nsplit > max_split) { nsplit = max_split; bound = "rows"; }
     nnf_ws_cursor cur(ctx);
-    const int64_t slab_elems = (int64_t)r * ldp;
-    const int64_t ws_max = (int64_t)(cur.remaining() / 4) / slab_elems;
-    if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
-    int64_t rps = nnf_rup(nnf_cdiv(m, nsplit), 64);
-    while ((rps + 128) * n * 4 >= (int64_t)0x7fff0000) {
-        if (rps <= 64) return NNF_ERR_UNSUPPORTED;
-        rps = nnf_rup(rps / 2, 64);
-        bound = "offset32";
-    }
-    nsplit = nnf_cdiv(m, rps);
-    if (nsplit > ws_max) return NNF_ERR_WORKSPACE;
+    const nnf_split_plan pl = nnf_plan_rows(ctx->num_cus, m, n, r, cur.remaining());
+    if (pl.status != NNF_OK) return pl.status;
+    const bool kr_fast = nnf_rows_kr_fast(nb, MT, lda, ldb);
+    if (nnf_plan_debug()) nnf_report_rows(stderr, m, n, nb, r, MT, VEC, kr_fast, pl);
+    const int ncb = (int)nnf_cdiv(n, 256), nsplit = (int)pl.nsplit, grid = nnf_split_grid(nsplit, ncb);
+    const int64_t ldp = nnf_rup(n, 4), slab_elems = (int64_t)r * ldp, rps = pl.rows_per_split;
     float* slabs = (float*)cur.take((size_t)nsplit * slab_elems * 4);
-    if (!slabs) return NNF_ERR_WORKSPACE;
-    const int grid = 8 * (int)nnf_cdiv(nsplit, 8) * ncb;
+    if (!slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
     nnf_probe(ctx, NNF_PROBE_MTTKRP, 0, st);
-    // buffer-addressed Khatri-Rao generation: 31-bit byte offsets into both factors, at most one wrap inside four rows
-    const bool kr_fast = nb >= 4 && (int64_t)(16 * MT) * lda * 4 < (int64_t)0x7fff0000 && (int64_t)(16 * MT) * ldb * 4 < (int64_t)0x7fff0000;   // (padded rank rows: their offsets must not wrap either)
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] mttkrp_rows m=%lld n=%lld nb=%lld r=%d mt=%d VEC=%d krf=%d krdiv=%s nsplit=%lld rps=%lld bound=%s\n",
-                (long long)m, (long long)n, (long long)nb, r, MT, (int)VEC, (int)kr_fast, !kr_fast ? "slow" : nb >= 64 ? "carry" : "redivide",
-                (long long)nsplit, (long long)rps, bound);
     if (kr_fast)
         hipLaunchKernelGGL((nnf_mttkrp_rows_kernel<MT, VEC, true>), dim3(grid), dim3(256), 0, st, M, m, n, n, Fa, lda, Fb, ldb, nb,
-                           r, slabs, ldp, ncb, (int)nsplit, rps);
+                           r, slabs, ldp, ncb, nsplit, rps);
     else
         hipLaunchKernelGGL((nnf_mttkrp_rows_kernel<MT, VEC, false>), dim3(grid), dim3(256), 0, st, M, m, n, n, Fa, lda, Fb, ldb, nb,
-                           r, slabs, ldp, ncb, (int)nsplit, rps);
+                           r, slabs, ldp, ncb, nsplit, rps);
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_MTTKRP, 1, st);
-    return nnf_launch_reduce_slabs(slabs, (int)nsplit, slab_elems, r, n, ldp, out, ldo, st);
+    return nnf_launch_reduce_slabs(slabs, nsplit, slab_elems, r, n, ldp, out, ldo, st);
 }
 
 #define MTTKRP_MT(FN, VEC, ...)                       \

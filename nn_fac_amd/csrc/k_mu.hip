@@ -89,17 +89,13 @@ static __global__ __launch_bounds__(64) void nnf_rowsum_fin_kernel(const double*
     for (int i = 0; i < np; ++i) s += part[(int64_t)k * np + i];
     out[k] = s;
 }
-// rowsum of an r x K matrix into out[r] on stream st; scratch from the cursor only when the rows are long
-static int nnf_launch_rowsum(nnf_ws_cursor& cur, const float* A, int64_t lda, int r, int64_t K, double* out, hipStream_t st) {
-    int np = (int)(K / 8192);
-    if (np > 64) np = 64;
+// rowsum of an r x K matrix into out[r] on stream st; np = nnf_rowsum_pieces(K), part: r x np doubles when np > 1
+static int nnf_launch_rowsum(double* part, int np, const float* A, int64_t lda, int r, int64_t K, double* out, hipStream_t st) {
     if (np <= 1) {
         hipLaunchKernelGGL(nnf_rowsum_kernel, dim3(r, 1), dim3(256), 0, st, A, lda, K, out, K);
         NNF_CHECK_LAUNCH();
         return NNF_OK;
     }
-    double* part = (double*)cur.take((size_t)r * np * 8);
-    if (!part) return NNF_ERR_WORKSPACE;
     hipLaunchKernelGGL(nnf_rowsum_kernel, dim3(r, np), dim3(256), 0, st, A, lda, K, part, nnf_cdiv(K, (int64_t)np));
     NNF_CHECK_LAUNCH();
     hipLaunchKernelGGL(nnf_rowsum_fin_kernel, dim3((r + 63) / 64), dim3(64), 0, st, part, np, r, out);
@@ -133,22 +129,11 @@ static __global__ __launch_bounds__(256) void nnf_mu2_finish_kernel(const float*
 
 static float gamma_of(double beta) { return beta < 1.0 ? (float)(1.0 / (2.0 - beta)) : (beta > 2.0 ? (float)(1.0 / (beta - 1.0)) : 1.f); }
 
-// leftover ranks handled on the VALU pipe: up to 4 next to one MFMA tile (ranks 17..20), up to 2 next to two or three (33, 34,
-// 49, 50) -- four leftover ranks at two tiles left scratch reloads inside the right kernel's chunk loop, at three tiles hipcc
-// spilled hundreds of registers (256 per wave at two workgroups per CU)
-#define MU_REM_OF(q, rem) ((rem) <= 2 ? 2 : ((q) == 1 && (rem) <= 4 ? 4 : 0))
-// Rank split of the fused kernels: MT full 16-rank tiles on MFMA, plus -- for 16q+1 .. 16q+4 ranks, aligned X, not the
-// general-beta form -- the leftover ranks on the VALU pipe (REM = 2 or 4) instead of a padded tile.
-static inline void mu_split_rank(int r, bool rem_ok, int& MT, int& REM) {
-    const int q = r / 16, rem = r % 16;
-    if (rem_ok && q >= 1 && q <= 3 && rem >= 1 && MU_REM_OF(q, rem) > 0) { MT = q; REM = MU_REM_OF(q, rem); }
-    else { MT = (r + 15) / 16; REM = 0; }
-}
 // FN<MT, REM, BM, VEC>(args) over the instantiated (MT, REM, VEC) combinations; BMV without leftover-rank forms: REMOK = false
 #define MU_CALL(FN, BMV, REMOK, R, VECF, ...)                                                                \
     do {                                                                                                     \
-        int MT_, REM_;                                                                                       \
-        mu_split_rank((R), (REMOK) && (VECF), MT_, REM_);                                                    \
+        const nnf_rank_tiles t_ = mu_split_rank((R), (REMOK) && (VECF));                                     \
+        const int MT_ = t_.MT, REM_ = t_.REM;                                                                \
         if (REM_ == 2) switch (MT_) {                                                                        \
             case 1: return FN<1, (REMOK) ? 2 : 0, BMV, true>(__VA_ARGS__);                                   \
             case 2: return FN<2, (REMOK) ? 2 : 0, BMV, true>(__VA_ARGS__);                                   \
@@ -164,65 +149,44 @@ static inline void mu_split_rank(int r, bool rem_ok, int& MT, int& REM) {
         }                                                                                                    \
     } while (0)
 
+// The two launchers: plan (k_mu_plan.h; a refusal launches nothing), report, carve what the plan counted, launch.
 template <int MT, int REM, int BM, bool VEC>
 static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx,
                            const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* V_out,
                            int64_t ldvo, hipStream_t st, float* num_out = nullptr, int64_t ldnum = 0,
                            float* den_out = nullptr, int64_t ldden = 0, double* den_vec_out = nullptr) {
-    if ((int64_t)(16 * (MT + 1)) * ldu * 4 + 4 * (m + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;   // 32-bit image offsets
-    const int ncb = (int)nnf_cdiv(n, 64 * MU_RIGHT_NC(MT));   // column blocks: 256 columns per workgroup, 128 at MT > 4
-    const int64_t ldp = nnf_rup(n, 4);
-    const int nacc = (BM == BM_GEN) ? 2 : 1;
-    int64_t nsplit = (BM == BM_KL && MT <= 4 ? 2 : 1) * (int64_t)ctx->num_cus / ncb;   // resident 4-wave workgroups per CU
-    if (nsplit < 1) nsplit = 1;
-    const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
-    const int64_t max_split = nnf_cdiv(m, 64);
-    if (nsplit > max_split) { nsplit = max_split; bound = "min_rows"; }
-    const int64_t slab_elems = (int64_t)r * ldp;
+    const mu_right_plan pl = mu_plan_right(cur, ctx->num_cus, m, n, ldx, ldu, r, MT, BM);
+    if (pl.split.status != NNF_OK) return pl.split.status;
+    if (nnf_plan_debug()) mu_report_right(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, BM, pl);
+    const int ncb = pl.ncb, nsplit = (int)pl.split.nsplit, nacc = (BM == BM_GEN) ? 2 : 1;
+    const int64_t ldp = nnf_rup(n, 4), slab_elems = (int64_t)r * ldp;
     double* dvec = (double*)cur.take((size_t)r * 8);
-    if (!dvec) return NNF_ERR_WORKSPACE;
-    if (BM == BM_KL) {  // den[k] = colsum(U)[k] = rowsum(Ut)[k]   (mu.py:86-87 on the transposed problem)
-        const int rc = nnf_launch_rowsum(cur, Ut, ldu, r, m, num_out ? den_vec_out : dvec, st);
-        if (rc != NNF_OK) return rc;
-    }
-    int64_t ws_max = (int64_t)(cur.remaining() / 4) / (slab_elems * nacc);
-    // (two slab sets: the second starts on the cursor's 256-byte boundary, which a set of r * ldp * nsplit floats need not end on)
-    while (nacc == 2 && ws_max >= 1 && nnf_rup(ws_max * slab_elems * 4, 256) + ws_max * slab_elems * 4 > (int64_t)cur.remaining()) --ws_max;
-    if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
-    int64_t rps = nnf_rup(nnf_cdiv(m, nsplit), 64);
-    while ((rps + 128) * ldx * 4 >= (int64_t)0x7fff0000) {
-        if (rps <= 64) return NNF_ERR_UNSUPPORTED;
-        rps = nnf_rup(rps / 2, 64);
-        bound = "offset32";
-    }
-    nsplit = nnf_cdiv(m, rps);
-    if (nsplit > ws_max) return NNF_ERR_WORKSPACE;
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] mu_right m=%lld n=%lld r=%d mt=%d rem=%d vec=%d bm=%s nsplit=%lld rps=%lld bound=%s\n", (long long)m,
-                (long long)n, r, MT, REM, (int)VEC, BM == BM_KL ? "KL" : "GEN", (long long)nsplit, (long long)rps, bound);
+    double* part = pl.pieces > 1 ? (double*)cur.take((size_t)r * pl.pieces * 8) : nullptr;
     float* snum = (float*)cur.take((size_t)nsplit * slab_elems * 4);
     float* sden = nacc == 2 ? (float*)cur.take((size_t)nsplit * slab_elems * 4) : nullptr;
-    if (!snum || (nacc == 2 && !sden)) return NNF_ERR_WORKSPACE;
+    if (!dvec || (pl.pieces > 1 && !part) || !snum || (nacc == 2 && !sden)) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan took the same)
     const int a_vec_ok = ((((uintptr_t)Ut) & 15) == 0 && (ldu & 3) == 0) ? 1 : 0;
     const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, BM == BM_GEN));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_mu_right_kernel<MT, REM, BM, VEC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    const int grid = 8 * (int)nnf_cdiv(nsplit, 8) * ncb;
+    if (BM == BM_KL) {  // den[k] = colsum(U)[k] = rowsum(Ut)[k]   (mu.py:86-87 on the transposed problem)
+        const int rc = nnf_launch_rowsum(part, pl.pieces, Ut, ldu, r, m, num_out ? den_vec_out : dvec, st);
+        if (rc != NNF_OK) return rc;
+    }
     nnf_probe(ctx, NNF_PROBE_MU_RIGHT, 0, st);
-    hipLaunchKernelGGL((nnf_mu_right_kernel<MT, REM, BM, VEC>), dim3(grid), dim3(256), shm, st, X, m, n, ldx, Ut, ldu, V, ldv, r,
-                       (float)beta, snum, sden, ldp, ncb, (int)nsplit, rps, a_vec_ok);
+    hipLaunchKernelGGL((nnf_mu_right_kernel<MT, REM, BM, VEC>), dim3(nnf_split_grid(nsplit, ncb)), dim3(256), shm, st, X, m, n, ldx,
+                       Ut, ldu, V, ldv, r, (float)beta, snum, sden, ldp, ncb, nsplit, pl.split.rows_per_split, a_vec_ok);
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_MU_RIGHT, 1, st);
     if (num_out) {   // accumulate only (row-sharded runs): this block's numerator / denominator, slab-reduced in fixed order
-        int rc = nnf_launch_reduce_slabs(snum, (int)nsplit, slab_elems, r, n, ldp, num_out, ldnum, st);
+        int rc = nnf_launch_reduce_slabs(snum, nsplit, slab_elems, r, n, ldp, num_out, ldnum, st);
         if (rc != NNF_OK) return rc;
-        if (nacc == 2) return nnf_launch_reduce_slabs(sden, (int)nsplit, slab_elems, r, n, ldp, den_out, ldden, st);
+        if (nacc == 2) return nnf_launch_reduce_slabs(sden, nsplit, slab_elems, r, n, ldp, den_out, ldden, st);
         return NNF_OK;
     }
     int64_t fg = nnf_cdiv((int64_t)r * n, 256);
     if (fg > 2048) fg = 2048;
-    hipLaunchKernelGGL(nnf_mu_finish_kernel, dim3((int)fg), dim3(256), 0, st, V, ldv, r, n, snum, sden, (int)nsplit,
+    hipLaunchKernelGGL(nnf_mu_finish_kernel, dim3((int)fg), dim3(256), 0, st, V, ldv, r, n, snum, sden, nsplit,
                        slab_elems, ldp, BM == BM_KL ? dvec : (const double*)nullptr, gamma_of(beta), V_out, ldvo);
     NNF_CHECK_LAUNCH();
     return NNF_OK;
@@ -233,53 +197,28 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
                           const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* Ut_out,
                           int64_t lduo, hipStream_t st, int raw_num = 0, mu_left_extra ex = mu_left_extra{nullptr, 0, 1, nullptr},
                           double* cost_out = nullptr) {
-    if (64 * ldx * 4 + 4 * (n + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;
-    if ((int64_t)(16 * (MT + 1)) * ldv * 4 + 4 * (n + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;   // 32-bit image offsets
+    constexpr bool with_cost = BM == BM_FROB || BM == BM_KLC;
+    const mu_left_plan pl = mu_plan_left(cur, ctx->num_cus, m, n, ldx, ldv, r, nnf_rank_tiles{MT, REM}, BM);
+    if (pl.status != NNF_OK) return pl.status;
+    if (nnf_plan_debug()) mu_report_left(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, BM, pl);
     double* dvec = (double*)cur.take((size_t)r * 8);
-    if (!dvec) return NNF_ERR_WORKSPACE;
+    double* part = pl.pieces > 1 ? (double*)cur.take((size_t)r * pl.pieces * 8) : nullptr;
+    if (with_cost) ex.partial = (double*)cur.take((size_t)pl.grid * 8);
+    if (!dvec || (pl.pieces > 1 && !part) || (with_cost && (!ex.partial || !cost_out))) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan took the same)
     const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
     const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, BM == BM_GEN));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_mu_left_kernel<MT, REM, BM, VEC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     if (BM == BM_KL || BM == BM_KLC) {  // den[k] = rowsum(V)[k]   (mu.py:86-87)
-        const int rc = nnf_launch_rowsum(cur, V, ldv, r, n, dvec, st);
+        const int rc = nnf_launch_rowsum(part, pl.pieces, V, ldv, r, n, dvec, st);
         if (rc != NNF_OK) return rc;
     }
-    // Rows per workgroup (4 waves x 4, 3 or 2 tiles of 16 rows): whole ROUNDS of resident workgroups, all of about the same
-    // length -- R = ceil(T / (16 slots)) rounds of `slots` workgroups, each 8 to 16 tiles, as a mix of two adjacent sizes.
-    // 256-row workgroups everywhere put 977 workgroups on the 768 slots of the 250000-row pass of config D: a second round
-    // that is 27 % full and as long as the first.  Less than one round of 128-row workgroups: 128 rows each (most CUs busy).
-    const int64_t slots = (int64_t)MU_LEFT_WGPC(MT, REM, BM) * ctx->num_cus, T = nnf_cdiv(m, 16);
-    const int64_t W = nnf_cdiv(T, 16 * slots) * slots;
-    int64_t n_hi = 0, n_mid = 0, grid = W;
-    if (MU_LEFT_ROWS128(MT, BM) || T <= 8 * slots) {
-        grid = nnf_cdiv(m, 128);
-    } else if (MT > 4) {   // ranks 81 .. 128, KL: 192- and 128-row workgroups (rounds of 8 to 12 tiles each; 16 do not fit the registers)
-        const int64_t W3 = nnf_cdiv(T, 12 * slots) * slots;
-        if (T <= 8 * W3) grid = nnf_cdiv(m, 128);
-        else { grid = W3; n_mid = nnf_cdiv(T - 8 * W3, 4); }
-    } else if (T > 12 * W) {
-        n_hi = nnf_cdiv(T - 12 * W, 4);
-        n_mid = W - n_hi;
-    } else {
-        n_mid = nnf_cdiv(T - 8 * W, 4);
-    }
-    if (n_hi * 256 + n_mid * 192 + (grid - n_hi - n_mid) * 128 < m) return NNF_ERR_UNSUPPORTED;   // (cannot happen)
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] mu_left m=%lld n=%lld r=%d mt=%d rem=%d vec=%d bm=%s form=%s grid=%lld n_hi=%lld n_mid=%lld\n",
-                (long long)m, (long long)n, r, MT, REM, (int)VEC,
-                BM == BM_KL ? "KL" : BM == BM_KLC ? "KLC" : BM == BM_FROB ? "FROB" : "GEN",
-                T <= 8 * slots ? "small" : n_hi > 0 ? "hi" : n_mid > 0 ? "mid" : MT > 4 ? "rows128" : "mid", (long long)grid, (long long)n_hi, (long long)n_mid);
-    if (BM == BM_FROB || BM == BM_KLC) {
-        ex.partial = (double*)cur.take((size_t)grid * 8);
-        if (!ex.partial || !cost_out) return NNF_ERR_WORKSPACE;
-    }
     nnf_probe(ctx, NNF_PROBE_MU_LEFT, 0, st);
-    hipLaunchKernelGGL((nnf_mu_left_kernel<MT, REM, BM, VEC>), dim3((int)grid), dim3(256), shm, st, X, m, n, ldx, Ut, ldu, V, ldv, r,
-                       (float)beta, dvec, raw_num ? -1.f : gamma_of(beta), Ut_out, lduo, a_vec_ok, (int)n_hi, (int)n_mid, ex);
+    hipLaunchKernelGGL((nnf_mu_left_kernel<MT, REM, BM, VEC>), dim3((int)pl.grid), dim3(256), shm, st, X, m, n, ldx, Ut, ldu, V, ldv, r,
+                       (float)beta, dvec, raw_num ? -1.f : gamma_of(beta), Ut_out, lduo, a_vec_ok, (int)pl.n_hi, (int)pl.n_mid, ex);
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_MU_LEFT, 1, st);
-    if (BM == BM_FROB || BM == BM_KLC) return nnf_launch_sum_f64(ex.partial, grid, 1.0, cost_out, st);
+    if (with_cost) return nnf_launch_sum_f64(ex.partial, pl.grid, 1.0, cost_out, st);
     return NNF_OK;
 }
 
@@ -333,9 +272,7 @@ int nnf_mu_left_big_gen(
     nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
     const float* V, int64_t ldv, int r, double beta, float* Ut_out, int64_t lduo, hipStream_t st) {
 #if MU_PART == 5
-    // ranks 97 .. 100 (config E's rank), KL, aligned X: six tiles on MFMA and the four leftover ranks on the VALU pipe (REM)
-    // instead of a padded seventh tile -- 6.25 tiles' worth of work instead of 6.5 + 7 in the two MFMAs
-    if (r > 96 && r <= 100 && x_vec_ok(X, ldx))
+    if (mu_left_kl_six_and_four(r, x_vec_ok(X, ldx)))
         return launch_mu_left<6, 4, BM_KL, true>(ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, Ut_out, lduo, st);
 #endif
     MU_CALL_BIG(launch_mu_left, (MU_PART == 5 ? BM_KL : BM_GEN), r, x_vec_ok(X, ldx), ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r,

@@ -5,8 +5,6 @@
 #include "k_mu_plan.h"
 #include <math.h>
 
-enum { BM_KL = 1, BM_FROB = 2, BM_KLC = 3, BM_GEN = 9 };   // BM_KLC: the KL update + the KL divergence of its INPUT factors   // BM_FROB: R = X (plain X V^T) + the squared residual, see nnf_cp3_partial_cost_f32
-
 // extra operands of the left kernel's BM_FROB form: Khatri-Rao left factor generated from two short factors, cost partials
 struct mu_left_extra {
     const float* Fb;      // != nullptr: U[k][i] = Ut[k][i / nb] * Fb[k][i % nb]  (row (a, b) of a 3-way tensor seen as (A*B) x K)
@@ -33,13 +31,6 @@ __device__ __forceinline__ bool mu_kstep_on(int s4, int c, int KS, bool tail4) {
     else return 4 * s4 + c < KS;
 }
 
-// resident workgroups per CU of the left kernel: three for the small Frobenius forms (<= 168 VGPRs), one for general beta
-// and for ranks above 80 (MT > 5: 16 KiB of chunk images per rank tile)
-#define MU_LEFT_WGPC(MT, REM, BM) ((BM) == BM_GEN || (MT) > 5 ? 1 : (((MT) + ((REM) > 0) <= 2 && (REM) <= 2 && (BM) == BM_FROB) ? 3 : 2))
-// above rank 64 the left kernel has its 128-row form only for general beta (numerator + denominator + fragments in registers)
-// and at MT = 5 (there that form stays within 256 registers and 80 KiB of LDS: two workgroups share a CU, which measured
-// faster than the better balanced mix of 192- and 128-row workgroups at one per CU: 719 against 792 us at 100000 x 2000, r = 65)
-#define MU_LEFT_ROWS128(MT, BM) ((MT) > 4 && ((BM) == BM_GEN || (MT) == 5))
 #ifndef MU_WG_PER_CU
 #define MU_WG_PER_CU 2
 #endif
@@ -98,7 +89,6 @@ __device__ __forceinline__ void mu_elem(float x, float p, float beta, float& r1,
 // accumulators and the resident fragments -- at MT = 8 the general-beta form holds 64 + 64 + 64 registers of them instead of
 // 3 x 128 -- so that BOTH forms keep the fragments in registers and LDS holds the chunk images only (16 KiB per rank tile:
 // 128 KiB at MT = 8, one workgroup per CU).
-#define MU_RIGHT_NC(MT) ((MT) > 4 ? 2 : 4)
 template <int MT, int REM, int BM, bool VEC>
 __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) void nnf_mu_right_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
                                                               const float* __restrict__ Ut, int64_t ldu,
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(REM == 0 || BM == BM_KL, "leftover ranks on the VALU pipe: KL form only");
     static_assert(REM == 0 || MT <= 4, "leftover ranks on the VALU pipe: up to three full tiles");
-    constexpr int NC = MU_RIGHT_NC(MT);                              // 16-column tiles per wave: columns jl + cc, cc < NC
+    constexpr int NC = mu_right_nc(MT);                              // 16-column tiles per wave: columns jl + cc, cc < NC
     constexpr int MTA = MT + (REM > 0 ? 1 : 0);                      // tiles of the F_A image
     constexpr int NR = REM > 0 ? REM : 1;
     const int KS = REM > 0 ? 4 * MT : ((r + 3) >> 2);
@@ -798,7 +788,7 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
 }
 
 template <int MT, int REM, int BM, bool VEC>
-__global__ __launch_bounds__(256, MU_LEFT_WGPC(MT, REM, BM)) void nnf_mu_left_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+__global__ __launch_bounds__(256, mu_left_wgpc(MT, REM, BM)) void nnf_mu_left_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
                                                              const float* __restrict__ Ut, int64_t ldu,
                                                              const float* __restrict__ V, int64_t ldv, int r, float beta,
                                                              const double* __restrict__ den_vec, float gamma,
@@ -808,7 +798,7 @@ __global__ __launch_bounds__(256, MU_LEFT_WGPC(MT, REM, BM)) void nnf_mu_left_ke
     // the host picks the mix that fills whole rounds of resident workgroups (launch_mu_left)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = (int)blockIdx.x;
-    if constexpr (MU_LEFT_ROWS128(MT, BM)) {
+    if constexpr (mu_left_rows128(MT, BM)) {
         // ranks 65 .. 128, general beta: 128-row workgroups only (two row tiles per wave: 16 MT accumulator registers per set
         // instead of 32 MT, and half the resident fragments -- this form holds its fragments in registers as well)
         nnf_mu_left_body<MT, REM, BM, VEC, 2>(X, m, n, ldx, Ut, ldu, V, ldv, r, beta, den_vec, gamma, Ut_out, lduo, a_vec_ok,

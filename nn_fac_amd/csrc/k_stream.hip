@@ -27,13 +27,6 @@
 #ifndef XTY_BIG_WG
 #define XTY_BIG_WG 2   // resident workgroups per CU the W^T X kernel of five or six rank tiles is compiled for (A/B: tools/abl_build.sh)
 #endif
-// W^T X, workgroups per CU by rank tiles: up to four tiles three (<= 168 registers); five and six tiles (ranks 65 ... 98) TWO --
-// the kernel fits 256 registers there without a spill where the compiler took up to 348 for one wave per SIMD.  Six tiles + four
-// leftover ranks (rank 100) and seven / eight tiles stay at one: at 256 registers rank 100 spills 4 and -- worse -- waits for a
-// staging load inside the chunk loop (a full drain of the X prefetch ring per trip, tools/check_loop_drains.py), for 6.54 -> 6.34 ms
-// at 10^6 x 4000 (tools/probes/xty_occ_probe.py): not taken.
-template <int MT, int REM>
-constexpr int nnf_xty_wg_per_cu() { return MT + (REM > 0) <= 4 ? 3 : ((MT <= 6 && !(MT == 6 && REM == 4)) ? XTY_BIG_WG : 1); }
 NNF_BUILD_FLAGS(k_stream, "XHT_ABL=" NNF_STR(XHT_ABL) " XTY_BIG_WG=" NNF_STR(XTY_BIG_WG))
 
 // =========================================================================================================
@@ -45,7 +38,7 @@ NNF_BUILD_FLAGS(k_stream, "XHT_ABL=" NNF_STR(XHT_ABL) " XTY_BIG_WG=" NNF_STR(XTY
 // is otherwise idle here (fp32 MFMA and fp32 VALU have the same peak on gfx950, so padding r=50 to 64 would burn 22 % of
 // the MFMA time on zeros).  The leftover rows' operand is the (MT+1)-th tile of the same LDS image, read as a broadcast.
 template <int MT, int REM, bool VEC>
-__global__ __launch_bounds__(256, (nnf_xty_wg_per_cu<MT, REM>())) void nnf_xty_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+__global__ __launch_bounds__(256, (nnf_xty_wg_per_cu(MT, REM, XTY_BIG_WG))) void nnf_xty_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
                                                          const float* __restrict__ Ut, int64_t ldu, int r,
                                                          float* __restrict__ slabs, int64_t ldp, int ncb, int nsplit,
                                                          int64_t rows_per_split, int a_vec_ok) {
@@ -292,54 +285,24 @@ int nnf_launch_reduce_slabs(const float* slabs, int nslab, int64_t slab_stride, 
     return NNF_OK;
 }
 
+// plan (k_stream_plan.h; a refusal launches nothing), report, carve, launch, reduce
 template <int MT, int REM, bool VEC>
 static int launch_xty(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int r,
                       int64_t ldu, float* out, int64_t ldo, hipStream_t st) {
-    const int ncb = (int)nnf_cdiv(n, 256);
-    const int64_t ldp = nnf_rup(n, 4);
-    int64_t target = nnf_xty_wg_per_cu<MT, REM>() * (int64_t)ctx->num_cus / ncb;   // resident workgroups per CU
-    if (target < 1) target = 1;
-    int64_t nsplit = target;
-    const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
-    // a workgroup sums its rows in fp32 (MFMA accumulators); the slabs are added in fp64.  Cap the rows per workgroup: at
-    // 1e6 x 4000 rank 100 the plan above is 16 splits of 62500 rows, and an entry of U^T X came out with 9.5e-7 relative rms
-    // and a -2.2e-7 MEAN error (tools/probes/accum_error_probe.py) -- enough to take the Gram-identity cost of a HALS iteration
-    // (which multiplies the mean by ||X||^2) to its 5e-4 bound.  The mean falls with the SQUARE of the chain length (62500 ->
-    // 8192 rows: -2.2e-7 -> -3.7e-9, rms 9.5e-7 -> 1.2e-7), and at 8192 rows it was still what sent a 10^6 x 4000 rank-100 run
-    // back to the streaming cost kernel after ~20 iterations (tools/probes/identity_terms_probe.py: bias term 3.3e4 of a 5.9e4
-    // bound, actual error 1.4e4).  2048 rows: 489 slabs of 1.6 MB there (+10 % traffic on an MFMA-bound pass; fewer if the
-    // context workspace is smaller -- the Python engine creates its main context with 1 GiB).
-    const int64_t ROWS_CAP = 2048;
-    if (nsplit < nnf_cdiv(m, ROWS_CAP)) { nsplit = nnf_cdiv(m, ROWS_CAP); bound = "rows_cap"; }
-    const int64_t max_split = nnf_cdiv(m, 64);
-    if (nsplit > max_split) { nsplit = max_split; bound = "min_rows"; }
-    // workspace bound
-    const int64_t slab_elems = (int64_t)r * ldp;
-    const int64_t ws_max = (int64_t)(cur.remaining() / 4) / slab_elems;
-    if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
-    int64_t rows_per_split = nnf_rup(nnf_cdiv(m, nsplit), 64);
-    // 32-bit buffer offsets inside one split
-    while ((rows_per_split + 128) * ldx * 4 >= (int64_t)0x7fff0000) {
-        if (rows_per_split <= 64) return NNF_ERR_UNSUPPORTED;
-        rows_per_split = nnf_rup(rows_per_split / 2, 64);
-        bound = "offset32";
-    }
-    nsplit = nnf_cdiv(m, rows_per_split);
-    if (nsplit > ws_max) return NNF_ERR_WORKSPACE;
+    const nnf_split_plan pl = nnf_plan_xty(ctx->num_cus, m, n, ldx, r, nnf_rank_tiles{MT, REM}, XTY_BIG_WG, cur.remaining());
+    if (pl.status != NNF_OK) return pl.status;
+    if (nnf_plan_debug()) nnf_report_xty(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, pl);
+    const int ncb = (int)nnf_cdiv(n, 256), nsplit = (int)pl.nsplit;
+    const int64_t ldp = nnf_rup(n, 4), slab_elems = (int64_t)r * ldp;
     float* slabs = (float*)cur.take((size_t)nsplit * slab_elems * 4);
-    if (!slabs) return NNF_ERR_WORKSPACE;
+    if (!slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
     const int a_vec_ok = ((((uintptr_t)Ut) & 15) == 0 && (ldu & 3) == 0) ? 1 : 0;
-    const int grid = 8 * (int)nnf_cdiv(nsplit, 8) * ncb;
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] xty m=%lld n=%lld r=%d mt=%d rem=%d vec=%d nsplit=%lld rows_per_split=%lld bound=%s grid=%d\n",
-                (long long)m, (long long)n, r, MT, REM, (int)VEC, (long long)nsplit, (long long)rows_per_split, bound, grid);
     nnf_probe(ctx, NNF_PROBE_XTY, 0, st);   // measurement hook: the main kernel alone (bench.py)
-    hipLaunchKernelGGL((nnf_xty_kernel<MT, REM, VEC>), dim3(grid), dim3(256), 0, st, X, m, n, ldx, Ut, ldu, r, slabs, ldp, ncb,
-                       (int)nsplit, rows_per_split, a_vec_ok);
+    hipLaunchKernelGGL((nnf_xty_kernel<MT, REM, VEC>), dim3(nnf_split_grid(nsplit, ncb)), dim3(256), 0, st, X, m, n, ldx, Ut, ldu, r,
+                       slabs, ldp, ncb, nsplit, pl.rows_per_split, a_vec_ok);
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_XTY, 1, st);
-    return nnf_launch_reduce_slabs(slabs, (int)nsplit, slab_elems, r, n, ldp, out, ldo, st);
+    return nnf_launch_reduce_slabs(slabs, nsplit, slab_elems, r, n, ldp, out, ldo, st);
 }
 
 // =========================================================================================================
@@ -509,81 +472,29 @@ __global__ __launch_bounds__(256, (MT + (REM > 0) <= 4 || NTH <= 2 ? 2 : 1)) voi
 template <int MT, int REM, bool VEC>
 static int launch_xht(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r, int64_t ldv,
                       float* out, int64_t ldo, hipStream_t st) {
-    if (64 * ldx * 4 + 4 * (n + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;
-    const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
-    const int64_t slots = (int64_t)(MT + (REM > 0) <= 4 ? 2 : 1) * ctx->num_cus;   // resident workgroups
-    const int64_t T = nnf_cdiv(m, 16), waves = 4 * slots;
-    int nth = 4;
-    int64_t n_hi, grid;
-    float* tail_slabs = nullptr;
-    int64_t tail_row0 = 0, tail_ld = 0;
-    int tail_tiles = 0, tail_parts = 0, tail_cpp = 0;
-    // six and more rank tiles (ranks 96 ... 128), many rounds: TWO row tiles per wave keep a wave at 248 registers, so that two
-    // workgroups share a CU -- the four-tile form needs 404 (256 + 148 accumulation registers) and runs one wave per SIMD.
-    // Measured (tools/probes/xht_nt2_probe.py, four -> two tiles): rank 100, 10^6 x 4000 7.16 -> 6.56 ms (0.71 -> 0.775 of the MFMA
-    // peak), 500000 rows 3.58 -> 3.47, 250000 1.79 -> 1.73; rank 96 x 600000 2.17 -> 2.05; ranks 112 / 128 x 10^6 -4 % / -2 %;
-    // below ~230000 rows (125000: 0.97 -> 1.00) and at five rank tiles (rank 80: 2.75 -> 2.79) the four-tile form stays ahead.
-    // NNF_XHT_NT2=0 / 1 forces either form (A/B on one box).
+    if (!nnf_xht_offsets_ok(n, ldx)) return NNF_ERR_UNSUPPORTED;
     static const int nt2 = [] { const char* e = getenv("NNF_XHT_NT2"); return e ? atoi(e) : -1; }();
-    const bool two_tiles = MT + (REM > 0) > 4 && T > 4 * waves && (nt2 >= 0 ? nt2 != 0 : (MT + (REM > 0) >= 6 && T > 14 * waves));
-    const char* form;   // (NNF_PLAN_DEBUG)
-    if (two_tiles) {
-        form = "two_tiles";
-        nth = 2;
-        n_hi = grid = nnf_cdiv(m, 128);
-    } else if (T > 4 * waves) {            // several rounds: 256-row workgroups
-        form = "rounds";
-        n_hi = grid = nnf_cdiv(m, 256);
-    } else if (T > 2 * waves) {     // one round: (4,3) or (3,2) tiles per wave
-        nth = T > 3 * waves ? 4 : 3;
-        form = nth == 4 ? "round43" : "round32";
-        n_hi = nnf_cdiv(T - 4 * (nth - 1) * slots, 4);
-        grid = slots;
-        // few tiles beyond a whole round of nth - 1 per wave (config B: 106 beyond 6144): every workgroup stays at nth - 1 and the
-        // extra tiles are contracted in k-split shares by all of them -- 6 + 2 % on every SIMD instead of 7 tiles on the busiest.
-        // (Not for ranks <= 32: the LDS-staged form is bit for bit the unsplit kernel there, tests.  NNF_XHT_TAIL=0 switches it off.)
-        static const int tail_on = [] { const char* e = getenv("NNF_XHT_TAIL"); return e ? atoi(e) : 1; }();
-        const int64_t extra = T - 4 * (nth - 1) * slots, nchunk_all = nnf_cdiv(n, 64);
-        if (tail_on && MT + (REM > 0) >= 3 && extra > 0 && nchunk_all >= 4) {
-            int parts = 32;
-            while (parts > 1 && (parts > nchunk_all || 4 * (slots / parts) < extra)) parts >>= 1;
-            if (parts >= 4 && 4 * (slots / parts) >= extra && 8 * extra <= T) {
-                tail_parts = parts;
-                tail_tiles = (int)extra;
-                tail_cpp = (int)nnf_cdiv(nchunk_all, parts);
-                tail_row0 = 64 * (int64_t)(nth - 1) * slots;
-                tail_ld = nnf_rup(m - tail_row0, 4);
-                tail_slabs = (float*)cur.take((size_t)parts * r * tail_ld * 4);
-                if (tail_slabs) n_hi = 0;
-                else tail_parts = 0;
-            }
-        }
-    } else {                        // small: 128-row workgroups
-        form = "small";
-        nth = 3;
-        n_hi = 0;
-        grid = nnf_cdiv(m, 128);
-    }
-    if (n_hi * 64 * nth + (grid - n_hi) * 64 * (nth - 1) + 16 * (int64_t)tail_tiles < m) return NNF_ERR_UNSUPPORTED;   // (cannot happen: the split covers m by construction)
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] xht m=%lld n=%lld r=%d mt=%d rem=%d vec=%d form=%s nth=%d n_hi=%lld grid=%lld tail_parts=%d "
-                        "tail_tiles=%d tail_cpp=%d\n", (long long)m, (long long)n, r, MT, REM, (int)VEC, form, nth, (long long)n_hi,
-                (long long)grid, tail_parts, tail_parts ? tail_tiles : 0, tail_parts ? tail_cpp : 0);
+    static const int tail_on = [] { const char* e = getenv("NNF_XHT_TAIL"); return e ? atoi(e) : 1; }();
+    const nnf_xht_plan pl = nnf_plan_xht_direct(ctx->num_cus, m, n, r, nnf_rank_tiles{MT, REM}, nt2, tail_on, cur.remaining());
+    if (!pl.covers(m)) return NNF_ERR_UNSUPPORTED;   // (cannot happen: the split covers m by construction)
+    if (nnf_plan_debug()) nnf_report_xht(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, false, pl);
+    float* tail_slabs = pl.tail_parts > 0 ? (float*)cur.take((size_t)pl.tail_parts * r * pl.tail_ld * 4) : nullptr;
+    if (pl.tail_parts > 0 && !tail_slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
+    const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
     nnf_probe(ctx, NNF_PROBE_XHT, 0, st);
-    if (nth == 4)
-        hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, 4>), dim3((int)grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo,
-                           a_vec_ok, (int)n_hi, tail_slabs, tail_row0, tail_ld, tail_tiles, tail_parts, tail_cpp);
-    else if (nth == 2) {
-        if constexpr (MT + (REM > 0) > 4)
-            hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, 2>), dim3((int)grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo,
-                               a_vec_ok, (int)n_hi, tail_slabs, tail_row0, tail_ld, tail_tiles, tail_parts, tail_cpp);
-    } else
-        hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, 3>), dim3((int)grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo,
-                           a_vec_ok, (int)n_hi, tail_slabs, tail_row0, tail_ld, tail_tiles, tail_parts, tail_cpp);
+#define NNF_XHT_GO(NTH)                                                                                                          \
+    hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, NTH>), dim3((int)pl.grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo, \
+                       a_vec_ok, (int)pl.n_hi, tail_slabs, pl.tail_row0, pl.tail_ld, pl.tail_tiles, pl.tail_parts, pl.tail_cpp)
+    if (pl.nth == 4) NNF_XHT_GO(4);
+    else if (pl.nth == 2) {
+        if constexpr (MT + (REM > 0) > 4) NNF_XHT_GO(2);
+    } else NNF_XHT_GO(3);
+#undef NNF_XHT_GO
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_XHT, 1, st);
-    if (tail_parts > 0)    // the k-split shares of the last rows, added in share order
-        return nnf_launch_reduce_slabs(tail_slabs, tail_parts, (int64_t)r * tail_ld, r, m - tail_row0, tail_ld, out + tail_row0, ldo, st);
+    if (pl.tail_parts > 0)    // the k-split shares of the last rows, added in share order
+        return nnf_launch_reduce_slabs(tail_slabs, pl.tail_parts, (int64_t)r * pl.tail_ld, r, m - pl.tail_row0, pl.tail_ld,
+                                       out + pl.tail_row0, ldo, st);
     return NNF_OK;
 }
 
@@ -1267,13 +1178,6 @@ int nnf_launch_sum_f64(const double* partial, int64_t count, double scale, doubl
         case 7: return FN<7, REM, VEC>(__VA_ARGS__);      \
         default: return FN<8, REM, VEC>(__VA_ARGS__);     \
     }
-// rank -> (MFMA tiles, VALU leftover rows): r = 16q + (1..4), q >= 1 keeps q tiles on MFMA and 2 or 4 rows on VALU
-static inline void split_rank(int r, int& MT, int& REM) {
-    const int q = r / 16, rem = r % 16;
-    if (q >= 1 && q <= 7 && rem >= 1 && rem <= 4) { MT = q; REM = rem <= 2 ? 2 : 4; }
-    else { MT = (r + 15) / 16; REM = 0; }
-}
-
 int nnf_xty_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut,
                  int r, int64_t ldu, float* out, int64_t ldo, hipStream_t st) {
     if (!ctx || !X || !Ut || !out || m < 1 || n < 1 || r < 1 || ldx < n || ldu < m || ldo < n) return NNF_ERR_ARG;
@@ -1289,10 +1193,10 @@ int nnf_xty_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, in
         }
         return NNF_OK;
     }
-    int MT, REM;
-    split_rank(r, MT, REM);
-    if (!x_vec_ok(X, ldx)) {
-        MT = (r + 15) / 16;
+    const bool vec = x_vec_ok(X, ldx);
+    const nnf_rank_tiles t = nnf_xty_tiles(r, vec);
+    const int MT = t.MT, REM = t.REM;
+    if (!vec) {
         DISPATCH_MT(launch_xty, 0, false, ctx, cur, X, m, n, ldx, Ut, r, ldu, out, ldo, st)
     } else if (REM == 2) {
         DISPATCH_MT(launch_xty, 2, true, ctx, cur, X, m, n, ldx, Ut, r, ldu, out, ldo, st)
@@ -1324,17 +1228,13 @@ int nnf_xht_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, in
         }
         return NNF_OK;
     }
-    int MT, REM;
-    split_rank(r, MT, REM);
-    // ranks 51, 52: three tiles + four leftover ranks next to the 4-row-tile body do not fit 256 registers (84 bytes of scratch,
-    // drains inside the chunk loop: 292 us against 238 us for the padded four tiles at 100000 x 2000, tools/probes/rank_step_probe.py)
-    if (MT == 3 && REM == 4) { MT = 4; REM = 0; }
-    // X staged through LDS in 256-byte row pieces (k_xht_lds.hip) where the load path, not the MFMA rate, bounds the product
+    const bool vec = x_vec_ok(X, ldx);
+    const nnf_rank_tiles t = nnf_xht_tiles(r, vec);
+    const int MT = t.MT, REM = t.REM;
     const char* pick = getenv("NNF_XHT");       // measurement knob: "direct" keeps the register-fragment kernel
-    if (x_vec_ok(X, ldx) && MT + (REM > 0) <= 2 && !(pick && pick[0] == 'd'))
+    if (nnf_xht_use_lds(t, vec) && !(pick && pick[0] == 'd'))
         return nnf_xht_lds_launch(ctx, MT, REM, X, m, n, ldx, V, r, ldv, out, ldo, st);
-    if (!x_vec_ok(X, ldx)) {
-        MT = (r + 15) / 16;
+    if (!vec) {
         DISPATCH_MT(launch_xht, 0, false, ctx, cur, X, m, n, ldx, V, r, ldv, out, ldo, st)
     } else if (REM == 2) {
         DISPATCH_MT(launch_xht, 2, true, ctx, cur, X, m, n, ldx, V, r, ldv, out, ldo, st)

@@ -1,0 +1,223 @@
+// Launch plans of the streaming and MTTKRP launchers (k_stream.hip, k_xht_lds.hip, k_mttkrp.hip; k_mu_plan.h builds on them):
+// what a call will launch, decided from sizes alone before anything is carved from the workspace or launched, and the
+// NNF_PLAN_DEBUG line that reports it.  No HIP in here: tools/nnf_plan.cpp is a plain host program that prints the same plans
+// for any CU count (tests/test_mu_plan_table.py).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include "../../include/nnfac_hip.h"
+
+constexpr int64_t nnf_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+constexpr int64_t nnf_rup(int64_t a, int64_t b) { return nnf_cdiv(a, b) * b; }
+constexpr int64_t NNF_OFFSET32_END = 0x7fff0000;   // the byte offsets of buffer loads stay below this
+
+// workspace carve helper: 256-byte aligned bump allocator (a plan asks a copy of the caller's cursor what would fit; on a null
+// base the same take / remaining sequence runs without a device)
+struct nnf_ctx;
+struct nnf_ws_cursor {
+    char* base;
+    size_t cap, off;
+    nnf_ws_cursor(char* b, size_t c) : base(b), cap(c), off(0) {}
+    nnf_ws_cursor(nnf_ctx* c);   // over ctx->ws (nnf_internal.h)
+    bool reserve(size_t bytes) {   // take() without the address: what a plan asks
+        const size_t a = (off + 255) & ~size_t(255);
+        if (a + bytes > cap) return false;
+        off = a + bytes;
+        return true;
+    }
+    void* take(size_t bytes) { return reserve(bytes) ? base + (off - bytes) : nullptr; }
+    size_t remaining() const {
+        const size_t a = (off + 255) & ~size_t(255);
+        return a < cap ? cap - a : 0;
+    }
+};
+
+// ---- rank -> (MFMA tiles, VALU leftover rows) ----
+struct nnf_rank_tiles { int MT, REM; };
+// r = 16q + (1..4), q >= 1 keeps q tiles on MFMA and 2 or 4 rows on VALU (aligned X only: the callers pad otherwise)
+constexpr nnf_rank_tiles nnf_split_rank(int r) {
+    const int q = r / 16, rem = r % 16;
+    return (q >= 1 && q <= 7 && rem >= 1 && rem <= 4) ? nnf_rank_tiles{q, rem <= 2 ? 2 : 4} : nnf_rank_tiles{(r + 15) / 16, 0};
+}
+// W^T X: the leftover rows need 16-byte loads of X
+constexpr nnf_rank_tiles nnf_xty_tiles(int r, bool vec) { return vec ? nnf_split_rank(r) : nnf_rank_tiles{(r + 15) / 16, 0}; }
+// X H^T.  Ranks 51, 52: three tiles + four leftover ranks next to the 4-row-tile body do not fit 256 registers (84 bytes of
+// scratch, drains inside the chunk loop: 292 us against 238 us for the padded four tiles at 100000 x 2000,
+// tools/probes/rank_step_probe.py)
+constexpr nnf_rank_tiles nnf_xht_tiles(int r, bool vec) {
+    const nnf_rank_tiles t = nnf_split_rank(r);
+    return !vec ? nnf_rank_tiles{(r + 15) / 16, 0} : (t.MT == 3 && t.REM == 4) ? nnf_rank_tiles{4, 0} : t;
+}
+// X staged through LDS in 256-byte row pieces (k_xht_lds.hip) where the load path, not the MFMA rate, bounds the product
+constexpr bool nnf_xht_use_lds(nnf_rank_tiles t, bool vec) { return vec && t.MT + (t.REM > 0) <= 2; }
+
+// W^T X, workgroups per CU by rank tiles: up to four tiles three (<= 168 registers); five and six tiles (ranks 65 ... 98) `big_wg`
+// (the build switch XTY_BIG_WG: two) -- the kernel fits 256 registers there without a spill where the compiler took up to 348 for
+// one wave per SIMD.  Six tiles + four leftover ranks (rank 100) and seven / eight tiles stay at one: at 256 registers rank 100
+// spills 4 and -- worse -- waits for a staging load inside the chunk loop (a full drain of the X prefetch ring per trip,
+// tools/check_loop_drains.py), for 6.54 -> 6.34 ms at 10^6 x 4000 (tools/probes/xty_occ_probe.py): not taken.
+constexpr int nnf_xty_wg_per_cu(int MT, int REM, int big_wg) {
+    return MT + (REM > 0) <= 4 ? 3 : ((MT <= 6 && !(MT == 6 && REM == 4)) ? big_wg : 1);
+}
+// resident workgroups per CU of the direct X H^T kernel in its four- and three-tile forms
+constexpr int nnf_xht_wg_per_cu(int MT, int REM) { return MT + (REM > 0) <= 4 ? 2 : 1; }
+// W^T X: a workgroup sums its rows in fp32 (MFMA accumulators); the slabs are added in fp64.  Cap the rows per workgroup: at
+// 1e6 x 4000 rank 100 the occupancy plan is 16 splits of 62500 rows, and an entry of U^T X came out with 9.5e-7 relative rms
+// and a -2.2e-7 MEAN error (tools/probes/accum_error_probe.py) -- enough to take the Gram-identity cost of a HALS iteration
+// (which multiplies the mean by ||X||^2) to its 5e-4 bound.  The mean falls with the SQUARE of the chain length (62500 ->
+// 8192 rows: -2.2e-7 -> -3.7e-9, rms 9.5e-7 -> 1.2e-7), and at 8192 rows it was still what sent a 10^6 x 4000 rank-100 run
+// back to the streaming cost kernel after ~20 iterations (tools/probes/identity_terms_probe.py: bias term 3.3e4 of a 5.9e4
+// bound, actual error 1.4e4).  2048 rows: 489 slabs of 1.6 MB there (+10 % traffic on an MFMA-bound pass; fewer if the
+// context workspace is smaller -- the Python engine creates its main context with 1 GiB).
+constexpr int64_t NNF_XTY_ROWS_CAP = 2048;
+
+// ---- the long axis cut into slabs (W^T X, the right MU update, the MTTKRP rows kernel) ----
+struct nnf_split_plan {
+    int status;                // NNF_OK, or the refusal
+    int64_t nsplit, rows_per_split;
+    const char* bound;         // which bound set the split count (NNF_PLAN_DEBUG)
+    int64_t ws_max;            // slabs (per set) the free workspace holds
+};
+// rows x pitch floats under col_blocks column blocks: `resident` workgroups (per CU x CUs) shared among the column blocks, raised
+// to rows / rows_cap (0: no cap), cut to rows / 64 and to what free_bytes hold of nsets sets of slabs of slab_bytes each; the
+// rows per split in 64s, halved until (rows + 128) * pitch * 4 stays inside 32-bit offsets.
+inline nnf_split_plan nnf_plan_split(int64_t rows, int64_t pitch, int64_t col_blocks, int64_t resident, int64_t rows_cap,
+                                     int64_t slab_bytes, int nsets, size_t free_bytes, const char* min_rows = "min_rows") {
+    nnf_split_plan p{NNF_OK, resident / col_blocks, 0, "occupancy", 0};
+    if (p.nsplit < 1) p.nsplit = 1;
+    if (rows_cap > 0 && p.nsplit < nnf_cdiv(rows, rows_cap)) { p.nsplit = nnf_cdiv(rows, rows_cap); p.bound = "rows_cap"; }
+    if (p.nsplit > nnf_cdiv(rows, 64)) { p.nsplit = nnf_cdiv(rows, 64); p.bound = min_rows; }
+    const int64_t free = (int64_t)free_bytes;
+    p.ws_max = free / (slab_bytes * nsets);
+    // (every further set starts on the cursor's 256-byte boundary, which a set of nsplit slabs need not end on)
+    while (nsets > 1 && p.ws_max >= 1 && (nsets - 1) * nnf_rup(p.ws_max * slab_bytes, 256) + p.ws_max * slab_bytes > free) --p.ws_max;
+    if (p.ws_max < 1) { p.status = NNF_ERR_WORKSPACE; return p; }
+    if (p.nsplit > p.ws_max) { p.nsplit = p.ws_max; p.bound = "workspace"; }
+    p.rows_per_split = nnf_rup(nnf_cdiv(rows, p.nsplit), 64);
+    while ((p.rows_per_split + 128) * pitch * 4 >= NNF_OFFSET32_END) {
+        if (p.rows_per_split <= 64) { p.status = NNF_ERR_UNSUPPORTED; return p; }
+        p.rows_per_split = nnf_rup(p.rows_per_split / 2, 64);
+        p.bound = "offset32";
+    }
+    p.nsplit = nnf_cdiv(rows, p.rows_per_split);
+    if (p.nsplit > p.ws_max) p.status = NNF_ERR_WORKSPACE;
+    return p;
+}
+// workgroups of a split kernel: the splits in eights (nnf_xcd_map) x the column blocks
+constexpr int nnf_split_grid(int64_t nsplit, int col_blocks) { return 8 * (int)nnf_cdiv(nsplit, 8) * col_blocks; }
+
+inline nnf_split_plan nnf_plan_xty(int cus, int64_t m, int64_t n, int64_t ldx, int r, nnf_rank_tiles t, int big_wg, size_t free_bytes) {
+    return nnf_plan_split(m, ldx, nnf_cdiv(n, 256), nnf_xty_wg_per_cu(t.MT, t.REM, big_wg) * (int64_t)cus, NNF_XTY_ROWS_CAP,
+                          (int64_t)r * nnf_rup(n, 4) * 4, 1, free_bytes);
+}
+inline void nnf_report_xty(FILE* f, int64_t m, int64_t n, int r, nnf_rank_tiles t, bool vec, const nnf_split_plan& p,
+                           const char* more = "") {
+    fprintf(f, "[nnf plan] xty m=%lld n=%lld r=%d mt=%d rem=%d vec=%d nsplit=%lld rows_per_split=%lld bound=%s grid=%d%s\n",
+            (long long)m, (long long)n, r, t.MT, t.REM, (int)vec, (long long)p.nsplit, (long long)p.rows_per_split, p.bound,
+            nnf_split_grid(p.nsplit, (int)nnf_cdiv(n, 256)), more);
+}
+
+// MTTKRP rows kernel: the tensor as an m x n matrix (no padding), two workgroups per CU, no rows cap
+inline nnf_split_plan nnf_plan_rows(int cus, int64_t m, int64_t n, int r, size_t free_bytes) {
+    return nnf_plan_split(m, n, nnf_cdiv(n, 256), 2 * (int64_t)cus, 0, (int64_t)r * nnf_rup(n, 4) * 4, 1, free_bytes, "rows");
+}
+// buffer-addressed Khatri-Rao generation: 31-bit byte offsets into both factors, at most one wrap inside four rows
+// (padded rank rows: their offsets must not wrap either)
+constexpr bool nnf_rows_kr_fast(int64_t nb, int MT, int64_t lda, int64_t ldb) {
+    return nb >= 4 && (int64_t)(16 * MT) * lda * 4 < NNF_OFFSET32_END && (int64_t)(16 * MT) * ldb * 4 < NNF_OFFSET32_END;
+}
+inline void nnf_report_rows(FILE* f, int64_t m, int64_t n, int64_t nb, int r, int MT, bool vec, bool kr_fast,
+                            const nnf_split_plan& p, const char* more = "") {
+    fprintf(f, "[nnf plan] mttkrp_rows m=%lld n=%lld nb=%lld r=%d mt=%d VEC=%d krf=%d krdiv=%s nsplit=%lld rps=%lld bound=%s%s\n",
+            (long long)m, (long long)n, (long long)nb, r, MT, (int)vec, (int)kr_fast, !kr_fast ? "slow" : nb >= 64 ? "carry" : "redivide",
+            (long long)p.nsplit, (long long)p.rows_per_split, p.bound, more);
+}
+
+// ---- X H^T: rows of X over workgroups ----
+// A workgroup is four waves of `nth` 16-row tiles each; the first n_hi workgroups take nth tiles per wave, the others nth - 1.
+struct nnf_xht_plan {
+    const char* form;
+    int nth;
+    int64_t n_hi, grid;
+    int tail_parts, tail_tiles, tail_cpp;   // the k-split tail (all 0: none)
+    int64_t tail_row0, tail_ld;
+    bool covers(int64_t m) const { return n_hi * 64 * nth + (grid - n_hi) * 64 * (nth - 1) + 16 * (int64_t)tail_tiles >= m; }
+};
+// `slots` resident workgroups, `tiles` rank tiles (leftover ranks count as one).  nt2 / tail_on: NNF_XHT_NT2 (-1: unset) and
+// NNF_XHT_TAIL; narrow: the LDS-staged kernel's 32-row waves.  free_bytes: what the tail's slabs may take.
+inline nnf_xht_plan nnf_plan_xht(int64_t m, int64_t n, int r, int64_t slots, int tiles, int nt2, int tail_on, size_t free_bytes,
+                                 bool narrow = false) {
+    const int64_t T = nnf_cdiv(m, 16), waves = 4 * slots;
+    nnf_xht_plan p{"small", 3, 0, nnf_cdiv(m, 128), 0, 0, 0, 0, 0};   // small: 128-row workgroups
+    // six and more rank tiles (ranks 96 ... 128), many rounds: TWO row tiles per wave keep a wave at 248 registers, so that two
+    // workgroups share a CU -- the four-tile form needs 404 (256 + 148 accumulation registers) and runs one wave per SIMD.
+    // Measured (tools/probes/xht_nt2_probe.py, four -> two tiles): rank 100, 10^6 x 4000 7.16 -> 6.56 ms (0.71 -> 0.775 of the MFMA
+    // peak), 500000 rows 3.58 -> 3.47, 250000 1.79 -> 1.73; rank 96 x 600000 2.17 -> 2.05; ranks 112 / 128 x 10^6 -4 % / -2 %;
+    // below ~230000 rows (125000: 0.97 -> 1.00) and at five rank tiles (rank 80: 2.75 -> 2.79) the four-tile form stays ahead.
+    // NNF_XHT_NT2=0 / 1 forces either form (A/B on one box).
+    const bool two_tiles = tiles > 4 && T > 4 * waves && (nt2 >= 0 ? nt2 != 0 : (tiles >= 6 && T > 14 * waves));
+    if (narrow || two_tiles) {
+        p.form = narrow ? "shared_lines" : "two_tiles";
+        p.nth = 2;
+        p.n_hi = p.grid = nnf_cdiv(m, 128);
+    } else if (T > 4 * waves) {     // several rounds: 256-row workgroups
+        p.form = "rounds";
+        p.nth = 4;
+        p.n_hi = p.grid = nnf_cdiv(m, 256);
+    } else if (T > 2 * waves) {     // one round: (4,3) or (3,2) tiles per wave
+        p.nth = T > 3 * waves ? 4 : 3;
+        p.form = p.nth == 4 ? "round43" : "round32";
+        const int64_t extra = T - 4 * (p.nth - 1) * slots, nchunk_all = nnf_cdiv(n, 64);
+        p.n_hi = nnf_cdiv(extra, 4);
+        p.grid = slots;
+        // few tiles beyond a whole round of nth - 1 per wave (config B: 106 beyond 6144): every workgroup stays at nth - 1 and the
+        // extra tiles are contracted in k-split shares by all of them -- 6 + 2 % on every SIMD instead of 7 tiles on the busiest.
+        // (Not for ranks <= 32: the LDS-staged form is bit for bit the unsplit kernel there, tests.  NNF_XHT_TAIL=0 switches it off.)
+        if (tail_on && tiles >= 3 && extra > 0 && nchunk_all >= 4) {
+            int parts = 32;
+            while (parts > 1 && (parts > nchunk_all || 4 * (slots / parts) < extra)) parts >>= 1;
+            const int64_t row0 = 64 * (int64_t)(p.nth - 1) * slots, ld = nnf_rup(m - row0, 4);
+            // (slabs that do not fit the workspace: the (nth, nth - 1) mix above)
+            if (parts >= 4 && 4 * (slots / parts) >= extra && 8 * extra <= T && (size_t)parts * r * ld * 4 <= free_bytes) {
+                p.n_hi = 0;
+                p.tail_parts = parts;
+                p.tail_tiles = (int)extra;
+                p.tail_cpp = (int)nnf_cdiv(nchunk_all, parts);
+                p.tail_row0 = row0;
+                p.tail_ld = ld;
+            }
+        }
+    }
+    return p;
+}
+// a workgroup's 64 rows of X and a factor chunk inside 32-bit offsets (else both kernels refuse)
+constexpr bool nnf_xht_offsets_ok(int64_t n, int64_t ldx) { return 64 * ldx * 4 + 4 * (n + 128) < NNF_OFFSET32_END; }
+// the register-fragment kernel (nnf_xht_kernel)
+inline nnf_xht_plan nnf_plan_xht_direct(int cus, int64_t m, int64_t n, int r, nnf_rank_tiles t, int nt2, int tail_on, size_t free_bytes) {
+    return nnf_plan_xht(m, n, r, (int64_t)nnf_xht_wg_per_cu(t.MT, t.REM) * cus, t.MT + (t.REM > 0), nt2, tail_on, free_bytes);
+}
+// lds: the LDS-staged kernel (its tiling is reported as such; always 16-byte loads, never a tail)
+inline void nnf_report_xht(FILE* f, int64_t m, int64_t n, int r, nnf_rank_tiles t, bool vec, bool lds, const nnf_xht_plan& p,
+                           const char* more = "") {
+    fprintf(f, "[nnf plan] xht m=%lld n=%lld r=%d mt=%d rem=%d vec=%d form=%s%s nth=%d n_hi=%lld grid=%lld tail_parts=%d "
+               "tail_tiles=%d tail_cpp=%d%s\n", (long long)m, (long long)n, r, t.MT, t.REM, (int)vec, lds ? "lds tiling=" : "", p.form,
+            p.nth, (long long)p.n_hi, (long long)p.grid, p.tail_parts, p.tail_tiles, p.tail_cpp, more);
+}
+// the LDS-staged kernel's wave height.  A row pitch that is not a whole number of 128-byte lines leaves every 256-byte piece
+// sharing its first and last line with the neighbouring chunks' pieces of the same row: the wave comes back for them one chunk
+// later, after everything the XCD's 64 resident workgroups fetched in between -- 4 MB with 64-row waves, the size of the L2
+// (250000 x 500: 660 MB fetched for 500 MB, 127 us).  32-row waves (48 KB of LDS: three workgroups per CU) halve that distance:
+// 559 MB, 120 us.  Aligned pitches have no shared lines and keep the 64-row waves (100000 x 2000 rank 32: 157 us against 175).
+// (rows start on a line every 128 / gcd(pitch mod 128, 128) rows: the narrow form from every fourth row on -- with every
+//  second row aligned, 100000 x 2000, the 64-row waves stay ahead, 159 us against 190).  pin: NNF_XHT_NT (0: unset, 2: narrow)
+inline bool nnf_xht_lds_narrow(int64_t ldx, int pin) {
+    int64_t off = (ldx * 4) % 128, gcd = 128;
+    while (off) { const int64_t t = gcd % off; gcd = off; off = t; }
+    return pin ? pin == 2 : (128 / gcd >= 4);
+}
+// the LDS-staged kernel (nnf_xht_lds_kernel): the same row tiling at two resident workgroups per CU, without the two-tile form and
+// the tail
+inline nnf_xht_plan nnf_plan_xht_lds(int cus, int64_t m, int64_t n, int r, nnf_rank_tiles t, int64_t ldx, int pin) {
+    return nnf_plan_xht(m, n, r, (int64_t)2 * cus, t.MT + (t.REM > 0), 0, 0, 0, nnf_xht_lds_narrow(ldx, pin));
+}

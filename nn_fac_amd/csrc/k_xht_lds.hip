@@ -143,7 +143,7 @@ __device__ __forceinline__ void nnf_xht_lds_body(const float* __restrict__ X, in
     }
 }
 
-// The first n_hi workgroups take NTH row tiles per wave, the others NTH-1 (nnf_xht_kernel's split: one round of resident
+// The first n_hi workgroups take NTH row tiles per wave, the others NTH-1 (nnf_plan_xht: one round of resident
 // workgroups covers the matrix where it can).
 template <int MT, int REM, int NTH>
 __global__ __launch_bounds__(256, (NTH == 2 ? 3 : 2)) void nnf_xht_lds_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
@@ -164,57 +164,20 @@ __global__ __launch_bounds__(256, (NTH == 2 ? 3 : 2)) void nnf_xht_lds_kernel(co
 template <int MT, int REM>
 static int launch_xht_lds(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r, int64_t ldv,
                           float* out, int64_t ldo, hipStream_t st) {
-    if (64 * ldx * 4 + 4 * (n + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;
-    const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
-    const int64_t slots = (int64_t)2 * ctx->num_cus;   // resident workgroups
-    const int64_t T = nnf_cdiv(m, 16), waves = 4 * slots;
-    int nth = 4;
-    int64_t n_hi, grid;
-    // A row pitch that is not a whole number of 128-byte lines leaves every 256-byte piece sharing its first and last line with
-    // the neighbouring chunks' pieces of the same row: the wave comes back for them one chunk later, after everything the XCD's
-    // 64 resident workgroups fetched in between -- 4 MB with 64-row waves, the size of the L2 (250000 x 500: 660 MB fetched for
-    // 500 MB, 127 us).  32-row waves (48 KB of LDS: three workgroups per CU) halve that distance: 559 MB, 120 us.  Aligned pitches
-    // have no shared lines and keep the 64-row waves (100000 x 2000 rank 32: 157 us against 175).
+    if (!nnf_xht_offsets_ok(n, ldx)) return NNF_ERR_UNSUPPORTED;
     static const int pin = [] { const char* e = getenv("NNF_XHT_NT"); return e ? atoi(e) : 0; }();       // measurement knob
-    // (rows start on a line every 128 / gcd(pitch mod 128, 128) rows: the narrow form from every fourth row on -- with every
-    //  second row aligned, 100000 x 2000, the 64-row waves stay ahead, 159 us against 190)
-    int64_t off = (ldx * 4) % 128, gcd = 128;
-    while (off) { const int64_t t = gcd % off; gcd = off; off = t; }
-    const bool shared_lines = pin ? pin == 2 : (128 / gcd >= 4);
-    const char* tiling;   // (NNF_PLAN_DEBUG)
-    if (shared_lines) {
-        tiling = "shared_lines";
-        nth = 2;
-        n_hi = grid = nnf_cdiv(m, 128);
-    } else if (T > 4 * waves) {            // several rounds of 256-row workgroups
-        tiling = "rounds";
-        n_hi = grid = nnf_cdiv(m, 256);
-    } else if (T > 2 * waves) {     // one round: (4,3) or (3,2) tiles per wave
-        nth = T > 3 * waves ? 4 : 3;
-        tiling = nth == 4 ? "round43" : "round32";
-        n_hi = nnf_cdiv(T - 4 * (nth - 1) * slots, 4);
-        grid = slots;
-    } else {                        // small: 128-row workgroups
-        tiling = "small";
-        nth = 3;
-        n_hi = 0;
-        grid = nnf_cdiv(m, 128);
-    }
-    if (n_hi * 64 * nth + (grid - n_hi) * 64 * (nth - 1) < m) return NNF_ERR_UNSUPPORTED;   // (the split covers m by construction)
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] xht m=%lld n=%lld r=%d mt=%d rem=%d vec=1 form=lds tiling=%s nth=%d n_hi=%lld grid=%lld "
-                        "tail_parts=0 tail_tiles=0 tail_cpp=0\n", (long long)m, (long long)n, r, MT, REM, tiling, nth, (long long)n_hi,
-                (long long)grid);
+    const nnf_xht_plan pl = nnf_plan_xht_lds(ctx->num_cus, m, n, r, nnf_rank_tiles{MT, REM}, ldx, pin);
+    if (!pl.covers(m)) return NNF_ERR_UNSUPPORTED;   // (the split covers m by construction)
+    if (nnf_plan_debug()) nnf_report_xht(stderr, m, n, r, nnf_rank_tiles{MT, REM}, true, true, pl);
+    const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
     nnf_probe(ctx, NNF_PROBE_XHT, 0, st);
-    if (nth == 4)
-        hipLaunchKernelGGL((nnf_xht_lds_kernel<MT, REM, 4>), dim3((int)grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo,
-                           a_vec_ok, (int)n_hi);
-    else if (nth == 2)
-        hipLaunchKernelGGL((nnf_xht_lds_kernel<MT, REM, 2>), dim3((int)grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo,
-                           a_vec_ok, (int)n_hi);
-    else
-        hipLaunchKernelGGL((nnf_xht_lds_kernel<MT, REM, 3>), dim3((int)grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo,
-                           a_vec_ok, (int)n_hi);
+#define NNF_XHT_LDS_GO(NTH)                                                                                                           \
+    hipLaunchKernelGGL((nnf_xht_lds_kernel<MT, REM, NTH>), dim3((int)pl.grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo, \
+                       a_vec_ok, (int)pl.n_hi)
+    if (pl.nth == 4) NNF_XHT_LDS_GO(4);
+    else if (pl.nth == 2) NNF_XHT_LDS_GO(2);
+    else NNF_XHT_LDS_GO(3);
+#undef NNF_XHT_LDS_GO
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_XHT, 1, st);
     return NNF_OK;

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "../../include/nnfac_hip.h"
+#include "k_mu_plan.h"   // the host-only launch plans (k_stream_plan.h, k_mu_plan.h): sizes in, plan out, no HIP
 
 struct nnf_ctx {
     int device;
@@ -61,9 +62,6 @@ static inline void nnf_probe(nnf_ctx* c, int id, int which, hipStream_t st) {
         if (e__ != hipSuccess) return NNF_ERR_LAUNCH;        \
     } while (0)
 
-static inline int64_t nnf_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int64_t nnf_rup(int64_t a, int64_t b) { return nnf_cdiv(a, b) * b; }
-
 // NNF_PLAN_DEBUG: the streaming, MU, MTTKRP and dimension-tree launchers write one stderr line per call naming the plan they took,
 // "[nnf plan] <launcher> m=.. n=.. r=.. key=value ..." (tests/test_gpu_launch_plans.py and test_gpu_tensor_plans.py key on it).  Read once per unit.
 static inline bool nnf_plan_debug() {
@@ -71,22 +69,7 @@ static inline bool nnf_plan_debug() {
     return dbg;
 }
 
-// workspace carve helper: 256-byte aligned bump allocator over ctx->ws
-struct nnf_ws_cursor {
-    char* base;
-    size_t cap, off;
-    __host__ nnf_ws_cursor(nnf_ctx* c) : base(c->ws), cap(c->ws_bytes), off(0) {}
-    __host__ void* take(size_t bytes) {
-        size_t a = (off + 255) & ~size_t(255);
-        if (a + bytes > cap) return nullptr;
-        off = a + bytes;
-        return base + a;
-    }
-    __host__ size_t remaining() const {
-        const size_t a = (off + 255) & ~size_t(255);
-        return a < cap ? cap - a : 0;
-    }
-};
+inline nnf_ws_cursor::nnf_ws_cursor(nnf_ctx* c) : base(c->ws), cap(c->ws_bytes), off(0) {}
 
 // ---- device helpers -------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));

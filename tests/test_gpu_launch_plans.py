@@ -11,10 +11,11 @@ data.
 The MU rows run up to rank 128: the kernels of five to eight rank tiles have launch forms of their own (128-row workgroups only,
 or a 192 / 128-row mix over rounds of at most 12 tiles; 128-column workgroups in the right update), and REQUIRED_BIG names what
 the rows with mt >= 5 must reach without the help of the rows below.  `mu_accum` is the accumulate-only form of the right update
-(nnf_mu_right_accum_f32): the same plans, the slabs reduced into num / den.  tests/test_mu_plan_table.py checks the MU rows
-against a Python restatement of the two launchers without a device.
+(nnf_mu_right_accum_f32): the same plans, the slabs reduced into num / den.  tests/test_mu_plan_table.py checks the X H^T, W^T X
+and MU rows without a device, against the library's own plan arithmetic (csrc/k_stream_plan.h, k_mu_plan.h through
+tools/nnf_plan.cpp) at 256 and 304 compute units.
 
-One branch is not reachable and has no case: launch_xht refuses the tail when 8 * extra > T, but a tail of four or more
+One branch is not reachable and has no case: nnf_plan_xht refuses the tail when 8 * extra > T, but a tail of four or more
 shares already needs extra <= 4 * (slots / parts) <= slots, and a one-round T is more than 8 * slots.
 """
 import collections

@@ -1,129 +1,63 @@
-"""The MU rows of test_gpu_launch_plans.plan_cases against a plain restatement of launch_mu_left and launch_mu_right (k_mu.hip,
-k_mu_kernels.h), at 256 and at 304 compute units.  No GPU: this is what keeps the table's shapes on the side of the thresholds
-they name on a machine that cannot ask the library (test_plan_table does, through NNF_PLAN_DEBUG, on the device)."""
+"""The MU, X H^T and W^T X rows of test_gpu_launch_plans.plan_cases and the mttkrp_rows rows of test_gpu_tensor_plans.tensor_cases
+against the library's own plan arithmetic, at 256 and at 304 compute units.  No GPU: the launchers take their plans from HIP-free
+headers (nn_fac_amd/csrc/k_stream_plan.h, k_mu_plan.h), and tools/nnf_plan.cpp, a plain host program over the same headers,
+prints the plan of a case as the library reports it under NNF_PLAN_DEBUG.  This is what keeps the tables' shapes on the side of
+the thresholds they name on a machine that cannot ask the library (test_plan_table and test_tensor_plan_table do, on the device)."""
+import atexit
 import collections
+import functools
+import os
+import shutil
+import subprocess
+import tempfile
 
 import pytest
 
-from test_gpu_launch_plans import REQUIRED, REQUIRED_BIG, _cdiv, note_plan, plan_cases
+import test_gpu_tensor_plans as tensor
+from test_gpu_launch_plans import REQUIRED, REQUIRED_BIG, ROOT, _cdiv, note_plan, parse_plans, plan_cases
 
-LIM = 0x7fff0000
 WS_DEFAULT = 1024 << 20         # get_engine's context
-ERR_UNSUPPORTED, ERR_WORKSPACE = -3, -4
 CUS = (256, 304)
+LAUNCHER = {"mu_left": "mu_left", "mu_right": "mu_right", "mu_accum": "mu_right", "xht": "xht", "xty": "xty"}
 
 
-def _rup(a, b):
-    return _cdiv(a, b) * b
+@functools.lru_cache(maxsize=None)
+def plan_tool():
+    """tools/nnf_plan.cpp, built once with the host compiler (no ROCm include path)."""
+    tmp = tempfile.mkdtemp(prefix="nnf_plan_")
+    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+    exe = os.path.join(tmp, "nnf_plan")
+    subprocess.run([os.environ.get("CXX", "c++"), "-std=c++17", "-I", os.path.join(ROOT, "nn_fac_amd", "csrc"),
+                    os.path.join(ROOT, "tools", "nnf_plan.cpp"), "-o", exe], check=True)
+    return exe
 
 
-class Cursor:
-    """nnf_ws_cursor: blocks of the context workspace, each on a 256-byte boundary."""
-
-    def __init__(self, cap):
-        self.cap, self.off = cap, 0
-
-    def take(self, nbytes):
-        a = _rup(self.off, 256)
-        if a + nbytes > self.cap:
-            return None
-        self.off = a + nbytes
-        return a
-
-    def remaining(self):
-        return max(self.cap - _rup(self.off, 256), 0)
+def ask(lines):
+    """The tool's answer to each case line: the fields of the report line (numbers as int), or {"status": code}."""
+    p = subprocess.run([plan_tool()], input="".join(l + "\n" for l in lines), capture_output=True, text=True, check=True)
+    answers = p.stdout.splitlines()
+    assert len(answers) == len(lines), p.stdout[-2000:]
+    out = []
+    for n, text in enumerate(answers):
+        reports = parse_plans("[case] %d\n%s\n" % (n, text))[str(n)]
+        kv = reports[0][1] if reports else dict([text.split("=", 1)])
+        out.append({k: int(v) if v.lstrip("-").isdigit() else v for k, v in kv.items()})
+    return out
 
 
-def split_rank(r, rem_ok):
-    """mu_split_rank: (MT, REM).  Leftover ranks on the VALU pipe: up to 4 next to one tile, up to 2 next to two or three."""
-    q, rem = divmod(r, 16)
-    rem_of = 2 if rem <= 2 else (4 if q == 1 and rem <= 4 else 0)
-    if rem_ok and 1 <= q <= 3 and rem >= 1 and rem_of > 0:
-        return q, rem_of
-    return _cdiv(r, 16), 0
+def case_line(C, case):
+    return "%s %d %d %d %d %d %r %d" % (LAUNCHER[case.kernel], C, case.m, case.n, case.r, case.ld or case.n, case.beta or 0.0,
+                                        WS_DEFAULT if case.ws is None else case.ws)
 
 
-def rowsum_scratch(cur, r, K):
-    """nnf_launch_rowsum: r x np partials when a row has np = min(K / 8192, 64) > 1 pieces."""
-    pieces = min(K // 8192, 64)
-    return pieces <= 1 or cur.take(r * pieces * 8) is not None
-
-
-def left_plan(C, case):
-    m, n, r, ldx = case.m, case.n, case.r, case.ld or case.n
-    kl, vec = case.beta == 1.0, (case.ld or case.n) % 4 == 0          # (the test's X starts an allocation: 16-byte aligned)
-    ldv = n
-    if r > 64:
-        mt, rem = (6, 4) if kl and 96 < r <= 100 and vec else (_cdiv(r, 16), 0)
-    else:
-        mt, rem = split_rank(r, kl and vec)
-    if rem:
-        vec = True
-    if 64 * ldx * 4 + 4 * (n + 128) >= LIM or 16 * (mt + 1) * ldv * 4 + 4 * (n + 128) >= LIM:
-        return dict(status=ERR_UNSUPPORTED)
-    wgpc = 1 if not kl or mt > 5 else 2                               # MU_LEFT_WGPC (KL, general beta)
-    rows128 = mt > 4 and (not kl or mt == 5)                          # MU_LEFT_ROWS128
-    slots, T = wgpc * C, _cdiv(m, 16)
-    W = _cdiv(T, 16 * slots) * slots
-    n_hi, n_mid, grid = 0, 0, W
-    if rows128 or T <= 8 * slots:
-        grid = _cdiv(m, 128)
-    elif mt > 4:
-        W3 = _cdiv(T, 12 * slots) * slots
-        if T <= 8 * W3:
-            grid = _cdiv(m, 128)
-        else:
-            grid, n_mid = W3, _cdiv(T - 8 * W3, 4)
-    elif T > 12 * W:
-        n_hi = _cdiv(T - 12 * W, 4)
-        n_mid = W - n_hi
-    else:
-        n_mid = _cdiv(T - 8 * W, 4)
-    form = "small" if T <= 8 * slots else "hi" if n_hi > 0 else "mid" if n_mid > 0 else "rows128" if mt > 4 else "mid"
-    return dict(m=m, n=n, r=r, mt=mt, rem=rem, vec=int(vec), bm="KL" if kl else "GEN", form=form, grid=grid, n_hi=n_hi,
-                n_mid=n_mid, slots=slots)
-
-
-def right_plan(C, case):
-    m, n, r, ldx = case.m, case.n, case.r, case.ld or case.n
-    kl, vec = case.beta == 1.0, (case.ld or case.n) % 4 == 0
-    ldu = m
-    mt, rem = (_cdiv(r, 16), 0) if r > 64 else split_rank(r, kl and vec)
-    if rem:
-        vec = True
-    if 16 * (mt + 1) * ldu * 4 + 4 * (m + 128) >= LIM:
-        return dict(status=ERR_UNSUPPORTED)
-    ncb = _cdiv(n, 64 * (2 if mt > 4 else 4))                         # MU_RIGHT_NC
-    ldp, nacc = _rup(n, 4), 1 if kl else 2
-    nsplit = max((2 if kl and mt <= 4 else 1) * C // ncb, 1)
-    bound = "occupancy"
-    if nsplit > _cdiv(m, 64):
-        nsplit, bound = _cdiv(m, 64), "min_rows"
-    slab = r * ldp * 4
-    cur = Cursor(case.ws if case.ws is not None else WS_DEFAULT)
-    if cur.take(r * 8) is None or (kl and not rowsum_scratch(cur, r, m)):
-        return dict(status=ERR_WORKSPACE)
-    ws_max = cur.remaining() // (slab * nacc)
-    while nacc == 2 and ws_max >= 1 and _rup(ws_max * slab, 256) + ws_max * slab > cur.remaining():
-        ws_max -= 1                                                   # (the second slab set starts on a 256-byte boundary)
-    if ws_max < 1:
-        return dict(status=ERR_WORKSPACE)
-    if nsplit > ws_max:
-        nsplit, bound = ws_max, "workspace"
-    rps = _rup(_cdiv(m, nsplit), 64)
-    while (rps + 128) * ldx * 4 >= LIM:
-        if rps <= 64:
-            return dict(status=ERR_UNSUPPORTED)
-        rps, bound = _rup(rps // 2, 64), "offset32"
-    nsplit = _cdiv(m, rps)
-    if nsplit > ws_max or any(cur.take(nsplit * slab) is None for _ in range(nacc)):
-        return dict(status=ERR_WORKSPACE)
-    return dict(m=m, n=n, r=r, mt=mt, rem=rem, vec=int(vec), bm="KL" if kl else "GEN", nsplit=nsplit, rps=rps, bound=bound,
-                ncb=ncb, ws_max=ws_max)
+@functools.lru_cache(maxsize=None)
+def _answers(C):
+    lines = [case_line(C, c) for c in plan_cases(C).values() if c.kernel in LAUNCHER]
+    return dict(zip(lines, ask(lines)))
 
 
 def plan_of(C, case):
-    return left_plan(C, case) if case.kernel == "mu_left" else right_plan(C, case)
+    return _answers(C)[case_line(C, case)]
 
 
 def mu_cases(C):
@@ -132,7 +66,7 @@ def mu_cases(C):
 
 @pytest.mark.parametrize("C", CUS)
 def test_mu_cases_take_the_plans_they_name(C):
-    """Every field a MU case lists is what the restated launchers give, and the workgroups of every left plan cover the
+    """Every field a MU case lists is what the library's plan gives, and the workgroups of every left plan cover the
     rows with none of them starting beyond the last row."""
     bad = []
     for name, case in mu_cases(C).items():
@@ -191,3 +125,68 @@ def test_mu_cases_reach_required(C):
     acc = {(p["mt"] >= 5, p["bm"], p["bound"]) for nm, p in plans.items() if cases[nm].kernel == "mu_accum" and p["nsplit"] > 1}
     assert acc >= {(False, "KL", "occupancy"), (False, "GEN", "occupancy"), (True, "KL", "occupancy"),
                    (True, "GEN", "occupancy"), (True, "GEN", "workspace")}, acc
+
+
+def xcases(C):
+    return {nm: c for nm, c in plan_cases(C).items() if c.kernel in ("xht", "xty")}
+
+
+@pytest.mark.parametrize("C", CUS)
+def test_xht_xty_cases_take_the_plans_they_name(C):
+    """Every field an X H^T or W^T X case lists is what the library's plan gives, the table reaches what REQUIRED names for the two
+    launchers, and the workgroups (and tail tiles) of every X H^T plan cover the rows."""
+    seen, bad = collections.defaultdict(set), []
+    for name, case in xcases(C).items():
+        plan = plan_of(C, case)
+        assert "status" not in plan, (name, plan)
+        for key, want in case.expect.items():
+            if str(plan.get(key)) != str(want):
+                bad.append((name, key, plan.get(key), want))
+        note_plan(seen, collections.defaultdict(set), case.kernel, plan)
+        if case.kernel == "xht":
+            rows = 64 * (plan["n_hi"] * plan["nth"] + (plan["grid"] - plan["n_hi"]) * (plan["nth"] - 1)) + 16 * plan["tail_tiles"]
+            assert plan["grid"] >= plan["n_hi"] and rows >= case.m, (name, plan)
+            if plan["tail_parts"]:
+                seen[("xht", "tail_parts")].add(str(plan["tail_parts"]))
+    assert not bad, "\n".join(map(str, bad))
+    for key in (("xht", "form"), ("xty", "bound")):
+        assert REQUIRED[key] <= seen[key], (key, REQUIRED[key] - seen[key])
+    assert {"4", "8", "16", "32"} <= seen[("xht", "tail_parts")]
+
+
+def rows_line(C, case):
+    """A mode-2 MTTKRP case of tensor_cases as the rows launcher sees it (its first rank pass): T as an (I J) x K matrix."""
+    (I, J, K), ld, al = case.shape, case.ld or {}, case.align or {}
+    return "mttkrp_rows %d %d %d %d %d 0 %d nb=%d lda=%d ldb=%d align=%d" % (
+        C, I * J, K, min(case.R, 128), K, WS_DEFAULT if case.ws is None else case.ws, J, I + ld.get("f0", 0), J + ld.get("f1", 0),
+        al.get("T", 0))
+
+
+@pytest.mark.parametrize("C", CUS)
+def test_mttkrp_rows_cases_take_the_plans_they_name(C):
+    """Every field (or refusal) a mode-2 MTTKRP case of test_gpu_tensor_plans lists is what the library's plan gives, which is
+    also what that file's own formula gives, and the rows reach what its REQUIRED names for the launcher."""
+    cases = {nm: c for nm, c in tensor.tensor_cases(C).items() if c.kernel == "mttkrp" and c.mode == 2}
+    plans = dict(zip(cases, ask([rows_line(C, c) for c in cases.values()])))
+    seen, refused, bad = collections.defaultdict(set), set(), []
+    for name, case in cases.items():
+        plan = plans[name]
+        formula = tensor.plan_of(C, case)
+        if {k: str(v) for k, v in formula.items()} != {k: str(plan.get(k)) for k in formula}:
+            bad.append((name, "formula", formula, plan))
+        if "status" in plan or "status" in case.expect:
+            if plan != case.expect:
+                bad.append((name, plan, case.expect))
+            refused.add(plan.get("status"))
+            continue
+        for key, want in case.expect.items():
+            if str(plan.get(key)) != str(want):
+                bad.append((name, key, plan.get(key), want))
+        tensor._note(seen, "mttkrp_rows", plan)
+        if plan["bound"] == "workspace":
+            assert plan["nsplit"] == _cdiv(plan["m"], 64 * _cdiv(_cdiv(plan["m"], plan["ws_max"]), 64)), (name, plan)
+    assert not bad, "\n".join(map(str, bad))
+    for key, want in tensor.REQUIRED.items():
+        if key[0] == "mttkrp_rows":
+            assert want <= seen[key], (C, key, want - seen[key])
+    assert tensor.ERR_WORKSPACE in refused

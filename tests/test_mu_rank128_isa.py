@@ -16,7 +16,7 @@ def test_rank_65_to_128_mu_kernels_fit_registers_and_lds_without_scratch(built_l
     """Every instantiation the dispatcher can select above rank 64 -- MT = 5 .. 8 rank tiles, KL and general beta, aligned and
     unaligned X, both kernels, and the left KL form with four leftover ranks on the VALU pipe: 33 in all -- is in the kept ISA (build/k_mu3.s .. k_mu6.s) with a private segment of 0 bytes
     and no spilled register, at most 512 VGPR + AGPR (one 256-thread workgroup per CU), and static LDS plus the dynamic LDS
-    the launcher computes (csrc/k_mu_plan.h, through tools/mu_shm.cpp) within the 160 KiB of a CU."""
+    the launcher computes (csrc/k_mu_plan.h, through tools/nnf_plan.cpp) within the 160 KiB of a CU."""
     tool = _budget_tool()
     rows = tool.table()
     assert len(rows) == 33

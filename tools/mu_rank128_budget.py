@@ -3,7 +3,7 @@
 
 Reads the code-object metadata in the ISA that `make` keeps next to the objects (nn_fac_amd/csrc/build/k_mu3.s .. k_mu6.s: right
 KL, right general beta, left KL, left general beta) and, for the dynamic LDS, asks the launchers' own arithmetic
-(csrc/k_mu_plan.h through tools/mu_shm.cpp, compiled on the fly with the host compiler).
+(csrc/k_mu_plan.h through `tools/nnf_plan.cpp shm`, compiled on the fly with the host compiler).
 
     python tools/mu_rank128_budget.py          one line per instantiation, exit status 1 if one is over budget
 
@@ -55,9 +55,9 @@ def launcher_lds():
     """{(MT, REM, form): bytes of dynamic LDS the launchers request} from csrc/k_mu_plan.h."""
     cxx = os.environ.get("CXX", "c++")
     with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "mu_shm")
-        subprocess.run([cxx, "-std=c++17", "-I", CSRC, os.path.join(ROOT, "tools", "mu_shm.cpp"), "-o", exe], check=True)
-        lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split("\n")
+        exe = os.path.join(tmp, "nnf_plan")
+        subprocess.run([cxx, "-std=c++17", "-I", CSRC, os.path.join(ROOT, "tools", "nnf_plan.cpp"), "-o", exe], check=True)
+        lines = subprocess.run([exe, "shm"], check=True, capture_output=True, text=True).stdout.split("\n")
     return {(int(a), int(b), c): int(d) for a, b, c, d in (l.split() for l in lines if l.strip())}
 
 

@@ -1,0 +1,98 @@
+// The launch plans of libnnfac_hip.so without a device: the library's own plan functions (nn_fac_amd/csrc/k_stream_plan.h,
+// k_mu_plan.h) for any CU count, printed as the library reports them under NNF_PLAN_DEBUG.
+//
+//   nnf_plan < cases     one case per line:  <launcher> <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [key=value ...]
+//                        launcher: xht | xty | mu_left | mu_right | mttkrp_rows; the factors are contiguous (r x m, r x n);
+//                        optional keys: align= (offset of X from a 16-byte boundary, in floats; default 0) and, for mttkrp_rows
+//                        (m x n = the unfolded tensor, pitch n), nb= lda= ldb= (Khatri-Rao inner length, factor pitches).
+//                        Answer, one line per case: the "[nnf plan] ..." line of that launch, followed on the same line by the
+//                        fields of the plan the report leaves out (slots, ncb, ws_max), or "status=<code>" for a refusal.
+//                        beta = 2 (the Gram form of the MU updates: X H^T / W^T X + a Gram) is not a plan of these launchers.
+//   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
+//                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
+//
+// Build: c++ -std=c++17 -I nn_fac_amd/csrc tools/nnf_plan.cpp -o nnf_plan   (tests/test_mu_plan_table.py and
+// tools/mu_rank128_budget.py do it)
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "k_mu_plan.h"
+
+static long long key_of(const char* rest, const char* key, long long dflt) {
+    char pat[32];
+    snprintf(pat, sizeof pat, " %s=", key);
+    const char* at = strstr(rest, pat);
+    return at ? atoll(at + strlen(pat)) : dflt;
+}
+
+static int print_shm() {
+    for (int MT = 5; MT <= 8; ++MT)
+        for (int gen = 0; gen < 2; ++gen)
+            printf("%d 0 %s %zu\n", MT, gen ? "GEN" : "KL", mu_shm(MT, 0, 16 * MT, mu_frags_in_regs(MT, gen != 0)));
+    printf("6 4 KL %zu\n", mu_shm(6, 4, 100, mu_frags_in_regs(6, false)));   // ranks 97 .. 100: leftover ranks on the VALU pipe
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && strcmp(argv[1], "shm") == 0) return print_shm();
+    char line[512], name[32], more[96];
+    while (fgets(line, sizeof line, stdin)) {
+        long long C, m, n, r, ld, ws;
+        double beta;
+        int used = 0;
+        if (sscanf(line, "%31s %lld %lld %lld %lld %lld %lf %lld%n", name, &C, &m, &n, &r, &ld, &beta, &ws, &used) != 8) {
+            if (line[strspn(line, " \t\r\n")] == 0) continue;
+            fprintf(stderr, "nnf_plan: bad case line: %s", line);
+            return 2;
+        }
+        const char* rest = line + used;
+        const bool vec = key_of(rest, "align", 0) % 4 == 0 && ld % 4 == 0;   // x_vec_ok
+        const nnf_ws_cursor cur(nullptr, (size_t)ws);
+        const bool left = strcmp(name, "mu_left") == 0;
+        int status = NNF_ERR_UNSUPPORTED;   // (ranks above 128 run in passes of 128: ask for one pass)
+        more[0] = 0;
+        if (m < 1 || n < 1 || r < 1 || ld < n) {
+            status = NNF_ERR_ARG;
+        } else if (r > NNF_MAX_RANK) {
+        } else if (strcmp(name, "xty") == 0) {
+            const nnf_rank_tiles t = nnf_xty_tiles((int)r, vec);
+            const nnf_split_plan p = nnf_plan_xty((int)C, m, n, ld, (int)r, t, 2, cur.remaining());   // (XTY_BIG_WG: the product's 2)
+            snprintf(more, sizeof more, " ws_max=%lld", (long long)p.ws_max);
+            if ((status = p.status) == NNF_OK) nnf_report_xty(stdout, m, n, (int)r, t, vec, p, more);
+        } else if (strcmp(name, "xht") == 0) {
+            const nnf_rank_tiles t = nnf_xht_tiles((int)r, vec);
+            const bool lds = nnf_xht_use_lds(t, vec);
+            if (nnf_xht_offsets_ok(n, ld)) {
+                const nnf_xht_plan p = lds ? nnf_plan_xht_lds((int)C, m, n, (int)r, t, ld, 0)
+                                           : nnf_plan_xht_direct((int)C, m, n, (int)r, t, -1, 1, cur.remaining());
+                if (p.covers(m)) {
+                    status = NNF_OK;
+                    nnf_report_xht(stdout, m, n, (int)r, t, vec, lds, p);
+                }
+            }
+        } else if (strcmp(name, "mttkrp_rows") == 0) {
+            const int MT = (int)(r + 15) / 16;
+            const nnf_split_plan p = nnf_plan_rows((int)C, m, n, (int)r, cur.remaining());
+            snprintf(more, sizeof more, " ws_max=%lld", (long long)p.ws_max);
+            if ((status = p.status) == NNF_OK)
+                nnf_report_rows(stdout, m, n, key_of(rest, "nb", 1), (int)r, MT, vec,
+                                nnf_rows_kr_fast(key_of(rest, "nb", 1), MT, key_of(rest, "lda", 1), key_of(rest, "ldb", 1)), p, more);
+        } else if ((left || strcmp(name, "mu_right") == 0) && beta != 2.0) {
+            const int BM = beta == 1.0 ? BM_KL : BM_GEN;
+            const nnf_rank_tiles t = mu_tiles_of(left, (int)r, BM == BM_KL, vec);
+            if (left) {
+                const mu_left_plan p = mu_plan_left(cur, (int)C, m, n, ld, n, (int)r, t, BM);
+                snprintf(more, sizeof more, " slots=%lld", (long long)p.slots);
+                if ((status = p.status) == NNF_OK) mu_report_left(stdout, m, n, (int)r, t, vec, BM, p, more);
+            } else {
+                const mu_right_plan p = mu_plan_right(cur, (int)C, m, n, ld, m, (int)r, t.MT, BM);
+                snprintf(more, sizeof more, " ncb=%d ws_max=%lld", p.ncb, (long long)p.split.ws_max);
+                if ((status = p.split.status) == NNF_OK) mu_report_right(stdout, m, n, (int)r, t, vec, BM, p, more);
+            }
+        } else {
+            status = NNF_ERR_ARG;
+        }
+        if (status != NNF_OK) printf("status=%d\n", status);
+    }
+    return 0;
+}
