@@ -361,6 +361,24 @@ int nnf_ntd_core_pg_f32(nnf_ctx* ctx, float* core, const float* MtX, const float
                         int d1, int d2, double sparse, double delta, int max_iter, double norm_sq, double* status_f64,
                         void* stream);
 
+/* The same update for a core of any order: ndim modes, dims[i] the extents (host array), M[i] = F_i^T F_i (host array of ndim
+ * device pointers, each dims[i] x dims[i], dense); core and MtX are dims[0] x ... x dims[ndim-1], row-major.  Semantics,
+ * status block and arithmetic (fp64 accumulation, fixed summation order) are those of nnf_ntd_core_pg_f32, the power
+ * iterations and the mode products run in mode order; with ndim = 3 the result is bit-identical to that entry's.
+ * Limits: 3 <= ndim <= 8, every extent 1..128, S = prod dims <= 2^22; anything else returns NNF_ERR_ARG / NNF_ERR_UNSUPPORTED
+ * before anything is launched or written.  Forms (S1 = S / dims[0]; a Gram "image" is the transposed Gram with rows padded
+ * to a multiple of four floats, sum_i dims[i] * roundup4(dims[i]) * 4 bytes for all modes):
+ *   multi  S >= 2048, 4 <= dims[0] <= CUs and 3.2 KB + images of modes 1.. + 4 S1 doubles <= 150 KB: one workgroup per
+ *          mode-0 slab holds its slab of core, MtX and two scratch arrays (fp64) and those images in LDS; the slabs'
+ *          partial products are exchanged through the workspace, one grid barrier per step (bounded spin: status[5] = 1).
+ *   lds64  one workgroup; all images + four S-sized fp64 arrays in LDS (<= 160 KB with 2.2 KB of vectors).
+ *   lds32  the same with the four arrays stored as fp32 (accumulation stays fp64).
+ *   ws     one workgroup; the four fp64 arrays in the context workspace (32 S bytes); the images stay in LDS while they
+ *          fit in 64 KB with the vectors, else they too are read from the workspace (reported as ws_gram).
+ * No form asks for more than 160 KB of LDS.  NNF_NTD_DEBUG: "[nnf ntd] pgn d=(..) S=.. form=.." on stderr per call. */
+int nnf_ntd_core_pgn_f32(nnf_ctx* ctx, float* core, const float* MtX, const float* const* M, int ndim, const int* dims,
+                         double sparse, double delta, int max_iter, double norm_sq, double* status_f64, void* stream);
+
 /* *out_f64 = sum_ij A[i,j]*B[i,j]   (fp64 accumulate)  -- inner products of ntf.py:470 */
 int nnf_dot_f32(nnf_ctx* ctx, const float* A, int64_t lda, const float* B, int64_t ldb, int64_t rows, int64_t cols,
                 double* out_f64, void* stream);

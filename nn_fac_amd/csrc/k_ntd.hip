@@ -13,6 +13,8 @@
 //     norm falls below delta times the first one; then the Gram-form reconstruction error.  The core has a few hundred
 //     to a few thousand entries, so the whole loop runs in one workgroup with the core in LDS, in fp64 (the reference's
 //     arithmetic: the 300-step loop is a recurrence, and the error expression cancels to ~1e-8 of its terms).
+//   nnf_ntd_core_pgn_f32  the same update for a core of order 3..8, mode by mode: both entries fill a pg_modes and share
+//     pg_launch and the kernels below (a mode is the middle axis of a (left, d, right) view of the core).
 #include <cstdio>
 #include <cstdlib>
 
@@ -112,25 +114,35 @@ __device__ double pg_sigma_max(const float* M, int r, double* x, double* y, doub
     return lam;
 }
 
-// dst = src x_mode M  (dst[.., a', ..] = sum_a M[a'][a] src[.., a, ..]),  dims d0 x d1 x d2, M is d_mode x d_mode.
-// Mt is the TRANSPOSE of M with rows padded to dmp = roundup(d_mode, 4) floats (zero padding): Mt[a*dmp + a'] = M[a'][a].
+// The modes of one core update: extents, Grams (device pointers, d_i x d_i, dense) and their number.  Passed to the kernels
+// by value; both C entries (three modes, n modes) fill one.
+#define PG_MAX_MODES 8
+struct pg_modes {
+    const float* M[PG_MAX_MODES];
+    int d[PG_MAX_MODES];
+    int n;
+};
+__host__ __device__ __forceinline__ int pg_pad4(int d) { return (d + 3) & ~3; }
+
+// dst = src x_mode M  (dst[.., a', ..] = sum_a M[a'][a] src[.., a, ..]) for one mode of extent dm, seen as the middle axis of
+// a (left, dm, right) view of the tensor: `right` is the mode's stride, a fibre is one (left index, right index) pair.
+// Mt is the TRANSPOSE of M with rows padded to dmp = roundup(dm, 4) floats (zero padding): Mt[a*dmp + a'] = M[a'][a].
 // Work item = (fibre along the mode, group of four outputs a'..a'+3): the fibre element is read once per group and
 // feeds four fp64 FMAs whose Gram operands come from one 16-byte LDS read at an address shared by neighbouring
 // threads.  (One output per thread read the fibre AND a Gram row element for every FMA: 33 us per projected-gradient
 // step on a 20^3 core.)  Items are ordered group-major so that consecutive threads walk consecutive fibres (unit stride
-// in LDS) for modes 0 and 1; for the last mode a fibre IS contiguous, so there the threads of a fibre's groups are
-// neighbours (one broadcast read of the fibre element, consecutive 16-byte Gram reads).
+// in LDS) while right > 1; with right == 1 (the last mode) a fibre IS contiguous, so there the threads of a fibre's groups
+// are neighbours (one broadcast read of the fibre element, consecutive 16-byte Gram reads).  Every output is one sum in
+// index order whatever the item order, so the result does not depend on the view a mode is reached through.
 template <typename ST>
-__device__ void pg_mode_dot(const ST* src, ST* dst, const float* Mt, int d0, int d1, int d2, int mode) {
-    const int S = d0 * d1 * d2;
-    const int dm = mode == 0 ? d0 : (mode == 1 ? d1 : d2);
-    const int dmp = (dm + 3) & ~3;
-    const int stride = mode == 0 ? d1 * d2 : (mode == 1 ? d2 : 1);
-    const int nf = S / dm, ng = dmp >> 2;
+__device__ __forceinline__ void pg_mode_dot(const ST* src, ST* dst, const float* Mt, int left, int dm, int right) {
+    const int dmp = pg_pad4(dm);
+    const int stride = right;
+    const int nf = left * right, ng = dmp >> 2;
     for (int it = threadIdx.x; it < nf * ng; it += blockDim.x) {
-        const int grp = mode == 2 ? it % ng : it / nf, f = mode == 2 ? it / ng : it - grp * nf;
-        // fibre f: the other two indices, in memory order
-        const int base = mode == 0 ? f : (mode == 1 ? (f / d2) * (d1 * d2) + (f % d2) : f * d2);
+        const int grp = right == 1 ? it % ng : it / nf, f = right == 1 ? it / ng : it - grp * nf;
+        // fibre f: the other indices, in memory order
+        const int base = right == 1 ? f * dm : (f / right) * (dm * right) + (f % right);
         const float* mt = Mt + 4 * grp;
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
         for (int t = 0; t < dm; ++t) {
@@ -150,53 +162,81 @@ __device__ void pg_mode_dot(const ST* src, ST* dst, const float* Mt, int d0, int
     __syncthreads();
 }
 
+// fin = src x_first M_first ... x_{n-1} M_{n-1}, mode by mode in mode order, for a tensor of S entries with the extents
+// d[first..n-1] (the whole core with first = 0, one mode-0 slab with first = 1).  The products alternate between `oth` and
+// `fin` so that the last one lands in `fin`; img holds the Gram images of these modes one after the other.
+template <typename ST>
+__device__ __forceinline__ void pg_chain(const ST* src, ST* fin, ST* oth, const float* img, const pg_modes& sh, int first, int S) {
+    const int k = sh.n - first;
+    int left = 1, right = S;
+    for (int j = 0; j < k; ++j) {
+        const int dm = sh.d[first + j];
+        right /= dm;
+        ST* dst = ((k - 1 - j) & 1) ? oth : fin;
+        pg_mode_dot(src, dst, img, left, dm, right);
+        left *= dm;
+        img += dm * pg_pad4(dm);
+        src = dst;
+    }
+}
+
+// the transposed, row-padded images of the Grams of modes first..n-1, one after the other (a multiple of four floats each)
+__device__ __forceinline__ void pg_fill_images(float* img, const pg_modes& sh, int first) {
+    for (int i = first; i < sh.n; ++i) {
+        const int dm = sh.d[i], p = pg_pad4(dm);
+        const float* Mg = sh.M[i];
+        for (int e = threadIdx.x; e < dm * p; e += blockDim.x) { const int a = e / p, b = e - a * p; img[e] = b < dm ? Mg[b * dm + a] : 0.f; }
+        img += dm * p;
+    }
+}
+
+// ntd.py:592-596: one power iteration per mode, in mode order (the originals, from global memory)
+__device__ __forceinline__ double pg_step(const pg_modes& sh, double* vx, double* vy, double* red) {
+    double step = 1.0;
+    for (int i = 0; i < sh.n; ++i) step *= 1.0 / pg_sigma_max(sh.M[i], sh.d[i], vx, vy, red);
+    return rint(step * 1e6) / 1e6;
+}
+
 // ST: storage type of the four core-sized arrays.  double (the reference's arithmetic) while they fit in LDS; float -- with
 // every dot product and the update still accumulated in fp64 -- for cores up to ~9000 entries; beyond that (gbuf != 0)
-// double again, in the context workspace.
+// double again, in the context workspace.  gimg != 0: the Gram images live in the workspace too.
 template <typename ST>
 __global__ __launch_bounds__(1024) void nnf_ntd_core_pg_kernel(float* __restrict__ core_g, const float* __restrict__ mtx_g,
-                                                               const float* __restrict__ M0g, const float* __restrict__ M1g,
-                                                               const float* __restrict__ M2g, int d0, int d1, int d2,
-                                                               double sparse, double delta, int max_iter, double norm_sq,
-                                                               double* __restrict__ status, double* gbuf) {
+                                                               pg_modes sh, int S, double sparse, double delta, int max_iter,
+                                                               double norm_sq, double* __restrict__ status, double* gbuf,
+                                                               float* gimg) {
     // working set: LDS when it fits (the usual few-hundred-entry core), else a slice of the context workspace -- still
     // one workgroup (its waves share the CU's L1, and every phase ends in a barrier), just with L2 latency per access
     extern __shared__ __attribute__((aligned(16))) double lds_all[];
-    const int S = d0 * d1 * d2;
-    // LDS: [vx 128][vy 128][red 16] doubles, [T0][T1][T2] floats (transposed Grams, fp32 values), then (unless gbuf) the four
+    // LDS: [vx 128][vy 128][red 16] doubles, the transposed Grams (fp32 values, unless gimg), then (unless gbuf) the four
     // core-sized arrays of ST, 8-byte aligned
     double* vx = lds_all;
-    // the Grams live in LDS transposed and row-padded for the mode products (16-byte aligned: 272 doubles in front, every
-    // block a multiple of four floats); the three power iterations read the originals from global memory
-    const int p0 = (d0 + 3) & ~3, p1 = (d1 + 3) & ~3, p2 = (d2 + 3) & ~3;
-    float* T0 = reinterpret_cast<float*>(lds_all + 272);
-    float* T1 = T0 + d0 * p0;
-    float* T2 = T1 + d1 * p1;
-    const int tfl = d0 * p0 + d1 * p1 + d2 * p2;      // multiple of 4
-    ST* core = gbuf ? reinterpret_cast<ST*>(gbuf) : reinterpret_cast<ST*>(T0 + tfl);
+    // the Grams live transposed and row-padded for the mode products (16-byte aligned: 272 doubles in front, every
+    // block a multiple of four floats); the power iterations read the originals from global memory
+    float* Tl = reinterpret_cast<float*>(lds_all + 272);
+    int tfl = 0;                                      // multiple of 4
+    for (int i = 0; i < sh.n; ++i) tfl += sh.d[i] * pg_pad4(sh.d[i]);
+    ST* core = gbuf ? reinterpret_cast<ST*>(gbuf) : reinterpret_cast<ST*>(Tl + (gimg ? 0 : tfl));
     ST* mtx = core + S;
     ST* ta = mtx + S;
     ST* tb = ta + S;
     double* vy = vx + 128;
     double* red = vy + 128;   // 16 doubles
     for (int e = threadIdx.x; e < S; e += blockDim.x) { core[e] = (ST)core_g[e]; mtx[e] = (ST)mtx_g[e]; }
-    for (int e = threadIdx.x; e < d0 * p0; e += blockDim.x) { const int a = e / p0, b = e - a * p0; T0[e] = b < d0 ? M0g[b * d0 + a] : 0.f; }
-    for (int e = threadIdx.x; e < d1 * p1; e += blockDim.x) { const int a = e / p1, b = e - a * p1; T1[e] = b < d1 ? M1g[b * d1 + a] : 0.f; }
-    for (int e = threadIdx.x; e < d2 * p2; e += blockDim.x) { const int a = e / p2, b = e - a * p2; T2[e] = b < d2 ? M2g[b * d2 + a] : 0.f; }
+    if (gimg) pg_fill_images(gimg, sh, 0);
+    else pg_fill_images(Tl, sh, 0);
     __syncthreads();
-    // ntd.py:592-596
-    double step = 1.0;
-    step *= 1.0 / pg_sigma_max(M0g, d0, vx, vy, red);
-    step *= 1.0 / pg_sigma_max(M1g, d1, vx, vy, red);
-    step *= 1.0 / pg_sigma_max(M2g, d2, vx, vy, red);
-    step = rint(step * 1e6) / 1e6;
+    // ta = core x_0 M0 x_1 M1 ... (one call site per address space of the images: LDS reads stay LDS reads)
+    auto product = [&]() {
+        if (gimg) pg_chain<ST>(core, ta, tb, gimg, sh, 0, S);
+        else pg_chain<ST>(core, ta, tb, Tl, sh, 0, S);
+    };
+    const double step = pg_step(sh, vx, vy, red);
     // ntd.py:609-619
     int cnt = 1;
     double upd0 = 0.0, upd = 1.0;
     while (cnt <= max_iter && upd >= delta * upd0) {
-        pg_mode_dot(core, ta, T0, d0, d1, d2, 0);
-        pg_mode_dot(ta, tb, T1, d0, d1, d2, 1);
-        pg_mode_dot(tb, ta, T2, d0, d1, d2, 2);
+        product();
         double s2 = 0.0;
         for (int e = threadIdx.x; e < S; e += blockDim.x) {
             const double c = (double)core[e];
@@ -211,9 +251,7 @@ __global__ __launch_bounds__(1024) void nnf_ntd_core_pg_kernel(float* __restrict
     }
     // ntd.py:639 (the caller adds the sparsity terms and divides by norm_sq; it recomputes this itself if it normalises
     // the core first)
-    pg_mode_dot(core, ta, T0, d0, d1, d2, 0);
-    pg_mode_dot(ta, tb, T1, d0, d1, d2, 1);
-    pg_mode_dot(tb, ta, T2, d0, d1, d2, 2);
+    product();
     double ip = 0.0, qf = 0.0;
     for (int e = threadIdx.x; e < S; e += blockDim.x) { ip += (double)mtx[e] * (double)core[e]; qf += (double)ta[e] * (double)core[e]; }
     ip = pg_block_sum(ip, red);
@@ -231,8 +269,8 @@ __global__ __launch_bounds__(1024) void nnf_ntd_core_pg_kernel(float* __restrict
 
 // ---------------------------------------------------------------------------------------------------------
 // The same loop on d0 workgroups (one per mode-0 slab of the core) for cores of a few thousand entries, where one CU spends
-// ~18 us per step (300 steps = most of an NTD iteration at 300^3 / 20^3).  The three mode products of the gradient commute:
-// a workgroup forms  y = slab x_1 M1 x_2 M2  locally (two small products on its d1 x d2 slab), publishes it, and after ONE grid
+// ~18 us per step (300 steps = most of an NTD iteration at 300^3 / 20^3).  The mode products of the gradient commute:
+// a workgroup forms  y = slab x_1 M1 x_2 M2 ...  locally (small products on its slab), publishes it, and after ONE grid
 // barrier combines everybody's y with its row of M0:  (core x M)[a] = sum_a'' M0[a][a''] y[a''].  The squared norm of the previous
 // step's update travels with y, so the stopping test of ntd.py:609 is taken right after the barrier -- BEFORE the update of the
 // step it decides about is applied: no speculation, no roll-back, one barrier per step.  fp64 throughout, every workgroup
@@ -272,44 +310,36 @@ __device__ __forceinline__ bool pg_grid_barrier(unsigned* counter, unsigned epis
 }
 
 __global__ __launch_bounds__(256) void nnf_ntd_core_pg_multi_kernel(float* __restrict__ core_g, const float* __restrict__ mtx_g,
-                                                                   const float* __restrict__ M0g, const float* __restrict__ M1g,
-                                                                   const float* __restrict__ M2g, int d0, int d1, int d2,
-                                                                   double sparse, double delta, int max_iter, double norm_sq,
-                                                                   double* __restrict__ status, pg_multi_sync sy) {
+                                                                   pg_modes sh, int S1, double sparse, double delta, int max_iter,
+                                                                   double norm_sq, double* __restrict__ status, pg_multi_sync sy) {
     extern __shared__ __attribute__((aligned(16))) double lds_all[];
-    const int a = blockIdx.x, S1 = d1 * d2;
+    const int a = blockIdx.x, d0 = sh.d[0];
     const unsigned nwg = gridDim.x;
     double* vx = lds_all;            // 128
     double* vy = vx + 128;           // 128
     double* red = vy + 128;          // 16
     double* m0 = red + 16;           // d0 doubles: row a of M0 (padded to 128)
-    const int p1 = (d1 + 3) & ~3, p2 = (d2 + 3) & ~3;
-    float* T1 = reinterpret_cast<float*>(m0 + 128);
-    float* T2 = T1 + d1 * p1;
-    double* c = reinterpret_cast<double*>(T2 + d2 * p2 + ((d1 * p1 + d2 * p2) & 1));   // 8-byte aligned (both blocks are multiples of 4 floats)
+    float* Tl = reinterpret_cast<float*>(m0 + 128);   // images of the Grams of modes 1..n-1
+    int tfl = 0;
+    for (int i = 1; i < sh.n; ++i) tfl += sh.d[i] * pg_pad4(sh.d[i]);
+    double* c = reinterpret_cast<double*>(Tl + tfl);   // 8-byte aligned (every image is a multiple of 4 floats)
     double* mx = c + S1;
     double* y = mx + S1;
     double* ta = y + S1;
     __shared__ unsigned flag;
     for (int e = threadIdx.x; e < S1; e += blockDim.x) { c[e] = (double)core_g[(size_t)a * S1 + e]; mx[e] = (double)mtx_g[(size_t)a * S1 + e]; }
-    for (int e = threadIdx.x; e < d0; e += blockDim.x) m0[e] = (double)M0g[a * d0 + e];
-    for (int e = threadIdx.x; e < d1 * p1; e += blockDim.x) { const int r_ = e / p1, b = e - r_ * p1; T1[e] = b < d1 ? M1g[b * d1 + r_] : 0.f; }
-    for (int e = threadIdx.x; e < d2 * p2; e += blockDim.x) { const int r_ = e / p2, b = e - r_ * p2; T2[e] = b < d2 ? M2g[b * d2 + r_] : 0.f; }
+    for (int e = threadIdx.x; e < d0; e += blockDim.x) m0[e] = (double)sh.M[0][a * d0 + e];
+    pg_fill_images(Tl, sh, 1);
     __syncthreads();
-    double step = 1.0;   // ntd.py:592-596, every workgroup the same arithmetic
-    step *= 1.0 / pg_sigma_max(M0g, d0, vx, vy, red);
-    step *= 1.0 / pg_sigma_max(M1g, d1, vx, vy, red);
-    step *= 1.0 / pg_sigma_max(M2g, d2, vx, vy, red);
-    step = rint(step * 1e6) / 1e6;
+    const double step = pg_step(sh, vx, vy, red);   // every workgroup the same arithmetic
 
     unsigned episode = 0;
     bool ok = true;
     double s2_mine = 0.0, upd0 = 0.0, upd = 1.0;
     int t = 1;
-    // gradient of the current core: ta = (core x_0 M0 x_1 M1 x_2 M2)[a]; brings back the sum of the partials p0 published with it
+    // gradient of the current core: ta = (core x_0 M0 x_1 M1 ...)[a]; brings back the sum of the partials p0 published with it
     auto full_product = [&](double pub0, double pub1, double& sum0, double& sum1) -> bool {
-        pg_mode_dot<double>(c, ta, T1, 1, d1, d2, 1);          // (ends with a barrier)
-        pg_mode_dot<double>(ta, y, T2, 1, d1, d2, 2);
+        pg_chain<double>(c, y, ta, Tl, sh, 1, S1);             // (every product ends with a barrier)
         ++episode;
         unsigned long long* Yp = sy.Y + (size_t)(episode & 1) * nwg * S1;
         for (int e = threadIdx.x; e < S1; e += blockDim.x) pg_st(Yp + (size_t)a * S1 + e, y[e]);
@@ -391,27 +421,37 @@ __global__ __launch_bounds__(256) void nnf_ntd_core_pg_multi_kernel(float* __res
     }
 }
 
-extern "C" int nnf_ntd_core_pg_f32(nnf_ctx* ctx, float* core, const float* MtX, const float* M0, const float* M1, const float* M2,
-                                   int d0, int d1, int d2, double sparse, double delta, int max_iter, double norm_sq,
-                                   double* status_f64, void* stream) {
-    if (!ctx || !core || !MtX || !M0 || !M1 || !M2 || !status_f64 || d0 < 1 || d1 < 1 || d2 < 1 || max_iter < 0) return NNF_ERR_ARG;
-    if (d0 > 128 || d1 > 128 || d2 > 128) return NNF_ERR_UNSUPPORTED;
-    const int64_t S = (int64_t)d0 * d1 * d2;
-    if (S > ((int64_t)1 << 22)) return NNF_ERR_UNSUPPORTED;
-    const size_t fixed = (size_t)272 * 8 + ((size_t)d0 * ((d0 + 3) & ~3) + (size_t)d1 * ((d1 + 3) & ~3) + (size_t)d2 * ((d2 + 3) & ~3)) * 4;
+// Form selection and launch for both entries.  `native` is the n-mode entry: it names itself "pgn" in the debug line, and in
+// the `ws` form it keeps the Gram images in LDS only while the launch stays within the 64 KiB a kernel gets without asking
+// (beyond that they are read from the workspace, like the arrays), so that it never asks for more than 160 KiB.
+static int pg_launch(nnf_ctx* ctx, float* core, const float* MtX, const pg_modes& sh, bool native, double sparse, double delta,
+                     int max_iter, double norm_sq, double* status_f64, hipStream_t st) {
+    int64_t S = 1;
+    size_t img = 0, img_tail = 0;                  // floats: Gram images of every mode, of modes 1..n-1
+    for (int i = 0; i < sh.n; ++i) {
+        S *= sh.d[i];
+        img += (size_t)sh.d[i] * pg_pad4(sh.d[i]);
+        if (S > ((int64_t)1 << 22)) return NNF_ERR_UNSUPPORTED;
+    }
+    const int d0 = sh.d[0];
+    img_tail = img - (size_t)d0 * pg_pad4(d0);
+    const size_t fixed = (size_t)272 * 8 + img * 4;
     const size_t lim = (size_t)160 * 1024;
     const int threads = S >= 1024 ? 1024 : (S >= 512 ? 512 : 256);
-    hipStream_t st = (hipStream_t)stream;
-    // NNF_NTD_DEBUG: one stderr line per call naming the form the selection below takes (tests/test_gpu_ntd.py keys on it)
+    // NNF_NTD_DEBUG: one stderr line per call naming the form the selection below takes (tests/test_gpu_ntd.py and
+    // tests/test_gpu_ntd_core_order_n.py key on it)
     static const bool dbg = getenv("NNF_NTD_DEBUG") != nullptr;
     auto report = [&](const char* form) {
-        if (dbg) fprintf(stderr, "[nnf ntd] pg d=(%d,%d,%d) S=%lld form=%s\n", d0, d1, d2, (long long)S, form);
+        if (!dbg) return;
+        char dims[PG_MAX_MODES * 12];
+        int at = 0;
+        for (int i = 0; i < sh.n; ++i) at += snprintf(dims + at, sizeof(dims) - at, i ? ",%d" : "%d", sh.d[i]);
+        fprintf(stderr, "[nnf ntd] %s d=(%s) S=%lld form=%s\n", native ? "pgn" : "pg", dims, (long long)S, form);
     };
     {   // a few thousand entries and several mode-0 slabs: one workgroup per slab (NNF_NTD_PG_MULTI=0: the one-workgroup form)
         static const bool multi_ok = !(getenv("NNF_NTD_PG_MULTI") && getenv("NNF_NTD_PG_MULTI")[0] == '0');
-        const int64_t S1 = (int64_t)d1 * d2;
-        const size_t shm = (size_t)(128 + 128 + 16 + 128) * 8 + ((size_t)d1 * ((d1 + 3) & ~3) + (size_t)d2 * ((d2 + 3) & ~3) + 2) * 4 +
-                           (size_t)4 * S1 * 8;
+        const int64_t S1 = S / d0;
+        const size_t shm = (size_t)(128 + 128 + 16 + 128) * 8 + (img_tail + 2) * 4 + (size_t)4 * S1 * 8;
         if (multi_ok && S >= 2048 && d0 >= 4 && d0 <= ctx->num_cus && shm <= (size_t)150 * 1024) {
             report("multi");
             nnf_ws_cursor cur(ctx);
@@ -423,8 +463,8 @@ extern "C" int nnf_ntd_core_pg_f32(nnf_ctx* ctx, float* core, const float* MtX, 
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_ntd_core_pg_multi_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
                 return NNF_ERR_LAUNCH;
-            hipLaunchKernelGGL(nnf_ntd_core_pg_multi_kernel, dim3(d0), dim3(256), shm, st, core, MtX, M0, M1, M2, d0, d1, d2, sparse,
-                               delta, max_iter, norm_sq, status_f64, pg_multi_sync{counter, Y, part});
+            hipLaunchKernelGGL(nnf_ntd_core_pg_multi_kernel, dim3(d0), dim3(256), shm, st, core, MtX, sh, (int)S1, sparse, delta,
+                               max_iter, norm_sq, status_f64, pg_multi_sync{counter, Y, part});
             NNF_CHECK_LAUNCH();
             return NNF_OK;
         }
@@ -435,27 +475,57 @@ extern "C" int nnf_ntd_core_pg_f32(nnf_ctx* ctx, float* core, const float* MtX, 
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_ntd_core_pg_kernel<double>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
             return NNF_ERR_LAUNCH;
-        hipLaunchKernelGGL(nnf_ntd_core_pg_kernel<double>, dim3(1), dim3(threads), shm, st, core, MtX, M0, M1, M2, d0, d1, d2, sparse,
-                           delta, max_iter, norm_sq, status_f64, (double*)nullptr);
+        hipLaunchKernelGGL(nnf_ntd_core_pg_kernel<double>, dim3(1), dim3(threads), shm, st, core, MtX, sh, (int)S, sparse, delta,
+                           max_iter, norm_sq, status_f64, (double*)nullptr, (float*)nullptr);
     } else if (fixed + (size_t)4 * S * 4 <= lim) {   // everything in LDS, fp32 storage, fp64 accumulation
         const size_t shm = fixed + (size_t)4 * S * 4;
         report("lds32");
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_ntd_core_pg_kernel<float>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
             return NNF_ERR_LAUNCH;
-        hipLaunchKernelGGL(nnf_ntd_core_pg_kernel<float>, dim3(1), dim3(threads), shm, st, core, MtX, M0, M1, M2, d0, d1, d2, sparse,
-                           delta, max_iter, norm_sq, status_f64, (double*)nullptr);
+        hipLaunchKernelGGL(nnf_ntd_core_pg_kernel<float>, dim3(1), dim3(threads), shm, st, core, MtX, sh, (int)S, sparse, delta,
+                           max_iter, norm_sq, status_f64, (double*)nullptr, (float*)nullptr);
     } else {                                          // core-sized arrays in the context workspace (slow: L2 latency per access)
-        report("ws");
+        const bool img_ws = native && fixed > (size_t)64 * 1024;
+        report(img_ws ? "ws_gram" : "ws");
         nnf_ws_cursor cur(ctx);
         double* gbuf = (double*)cur.take((size_t)4 * S * 8);
-        if (!gbuf) return NNF_ERR_WORKSPACE;
+        float* gimg = img_ws ? (float*)cur.take(img * 4) : nullptr;
+        if (!gbuf || (img_ws && !gimg)) return NNF_ERR_WORKSPACE;
+        const size_t shm = img_ws ? (size_t)272 * 8 : fixed;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_ntd_core_pg_kernel<double>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)fixed) != hipSuccess)
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm) != hipSuccess)
             return NNF_ERR_LAUNCH;
-        hipLaunchKernelGGL(nnf_ntd_core_pg_kernel<double>, dim3(1), dim3(threads), fixed, st, core, MtX, M0, M1, M2, d0, d1, d2, sparse,
-                           delta, max_iter, norm_sq, status_f64, gbuf);
+        hipLaunchKernelGGL(nnf_ntd_core_pg_kernel<double>, dim3(1), dim3(threads), shm, st, core, MtX, sh, (int)S, sparse, delta,
+                           max_iter, norm_sq, status_f64, gbuf, gimg);
     }
     NNF_CHECK_LAUNCH();
     return NNF_OK;
+}
+
+extern "C" int nnf_ntd_core_pg_f32(nnf_ctx* ctx, float* core, const float* MtX, const float* M0, const float* M1, const float* M2,
+                                   int d0, int d1, int d2, double sparse, double delta, int max_iter, double norm_sq,
+                                   double* status_f64, void* stream) {
+    if (!ctx || !core || !MtX || !M0 || !M1 || !M2 || !status_f64 || d0 < 1 || d1 < 1 || d2 < 1 || max_iter < 0) return NNF_ERR_ARG;
+    if (d0 > 128 || d1 > 128 || d2 > 128) return NNF_ERR_UNSUPPORTED;
+    pg_modes sh = {};
+    sh.n = 3;
+    sh.M[0] = M0, sh.M[1] = M1, sh.M[2] = M2;
+    sh.d[0] = d0, sh.d[1] = d1, sh.d[2] = d2;
+    return pg_launch(ctx, core, MtX, sh, false, sparse, delta, max_iter, norm_sq, status_f64, (hipStream_t)stream);
+}
+
+extern "C" int nnf_ntd_core_pgn_f32(nnf_ctx* ctx, float* core, const float* MtX, const float* const* M, int ndim, const int* dims,
+                                    double sparse, double delta, int max_iter, double norm_sq, double* status_f64, void* stream) {
+    if (!ctx || !core || !MtX || !M || !dims || !status_f64 || ndim < 1 || max_iter < 0) return NNF_ERR_ARG;
+    if (ndim < 3 || ndim > PG_MAX_MODES) return NNF_ERR_UNSUPPORTED;
+    pg_modes sh = {};
+    sh.n = ndim;
+    for (int i = 0; i < ndim; ++i) {
+        if (!M[i] || dims[i] < 1) return NNF_ERR_ARG;
+        if (dims[i] > 128) return NNF_ERR_UNSUPPORTED;
+        sh.M[i] = M[i];
+        sh.d[i] = dims[i];
+    }
+    return pg_launch(ctx, core, MtX, sh, true, sparse, delta, max_iter, norm_sq, status_f64, (hipStream_t)stream);
 }

@@ -630,6 +630,29 @@ class Engine:
                                                 self._stream()), "nnf_ntd_core_pg_f32")
         return st
 
+    def ntd_core_pgn(self, core, MtX, grams, sparse, delta, max_iter, norm_sq, status=None):
+        """ntd_core_pg for a core of any order 3..8 (nnf_ntd_core_pgn_f32: the mode products run mode by mode, no merged
+        trailing mode); in place on `core`, returns the same 6-double status block."""
+        if not core.is_contiguous() or core.dtype != torch.float32:
+            raise err.ArgumentException("ntd_core_pgn updates a contiguous float32 core in place")
+        if len(grams) != core.dim() or tuple(MtX.shape) != tuple(core.shape):
+            raise err.ArgumentException("ntd_core_pgn needs one Gram per core mode and an MtX of the core's shape")
+        for g, d in zip(grams, core.shape):
+            if tuple(g.shape) != (d, d) or g.dtype != torch.float32:
+                raise err.ArgumentException("ntd_core_pgn: the Gram of a mode of extent d is a float32 d x d matrix")
+        st = status if status is not None else torch.empty(6, dtype=torch.float64, device=core.device)
+        MtX = MtX.contiguous()
+        if MtX.dtype != torch.float32:
+            raise err.ArgumentException("ntd_core_pgn: MtX must be float32")
+        M = [g.contiguous() for g in grams]
+        n = core.dim()
+        ptrs = (C.c_void_p * n)(*[g.data_ptr() for g in M])
+        dims = (C.c_int * n)(*[int(d) for d in core.shape])
+        _lib.check(self.lib.nnf_ntd_core_pgn_f32(self.ctx, _ptr(core), _ptr(MtX), ptrs, n, dims, float(sparse), float(delta),
+                                                 int(max_iter), float(norm_sq), _ptr(st), self._stream()),
+                   "nnf_ntd_core_pgn_f32")
+        return st
+
     def betadiv(self, X, Ut, V, beta, out=None):
         _chk2d(X, "betadiv X"), _chk2d(Ut, "betadiv Ut"), _chk2d(V, "betadiv V")
         m, n = X.shape

@@ -1,7 +1,8 @@
 """NTD (nonnegative Tucker decomposition) driver on the MI355X engine -- drop-in for nn_fac/ntd.py
 (ntd :27-246, compute_ntd :248-433, one_ntd_step :436-645, one_ntd_step_mu :658-698), tensors of any order >= 3 (every mode
-product runs through the 3-way kernel on a VIEW (left, I_n, right) of the tensor; the core update merges the trailing core
-modes into one -- their Gram is the Kronecker product -- so that nnf_ntd_core_pg_f32's three-mode loop serves it).
+product runs through the 3-way kernel on a VIEW (left, I_n, right) of the tensor; the core update of an order above 3 merges
+the trailing core modes into one -- their Gram is the Kronecker product -- for nnf_ntd_core_pg_f32's three-mode loop while that
+merged extent is <= 128, and goes mode by mode through nnf_ntd_core_pgn_f32 beyond).
 
 HALS step, per updated mode n (factors kept transposed, r_n x I_n; statement -> C ABI):
 
@@ -22,6 +23,7 @@ nnf_betadiv_f32 on the mode-0 problem.
 Tensor-sized work goes through the C ABI; what stays in torch is core-sized (prod(ranks) entries) plumbing.
 """
 import math
+import os
 import time
 import warnings
 
@@ -249,19 +251,22 @@ def _one_ntd_step_dev(st, core_in, Ft_in, sparsity_coefficients, fixed_modes, no
     if N == 3:
         eng.ntd_core_pg(core, all_MtX, grams, sparse, delta, 300, st.norm_sq(), status=pg)
     else:
-        # the projected-gradient kernel loops over three modes: the trailing core modes are merged into one, whose Gram is
-        # the Kronecker product of theirs (core x_2 M_2 x_3 M_3 ... = merged core x_2 (M_2 (x) M_3 ...), row-major merge;
-        # sigma_max of a Kronecker product is the product of the sigma_max: same step, ntd.py:588-596)
+        # Two routes.  While the product of the core's trailing extents is <= 128 the trailing modes are merged into one,
+        # whose Gram is the Kronecker product of theirs (core x_2 M_2 x_3 M_3 ... = merged core x_2 (M_2 (x) M_3 ...),
+        # row-major merge; sigma_max of a Kronecker product is the product of the sigma_max: same step, ntd.py:588-596), and
+        # the three-mode kernel serves it.  Beyond that -- or with NNF_NTD_CORE_NATIVE=1 -- the n-mode entry takes the core
+        # as it is, mode by mode.
         tail = 1
         for d in core.shape[2:]:
             tail *= int(d)
-        if tail > 128:
-            raise NotImplementedError("NTD of order > 3: the product of the core's trailing extents must be <= 128")
-        Mk = grams[2]
-        for g in grams[3:]:
-            Mk = torch.kron(Mk.contiguous(), g.contiguous())
-        c3 = core.view(core.shape[0], core.shape[1], tail)
-        eng.ntd_core_pg(c3, all_MtX.view(c3.shape), [grams[0], grams[1], Mk], sparse, delta, 300, st.norm_sq(), status=pg)
+        if tail > 128 or os.environ.get("NNF_NTD_CORE_NATIVE") == "1":
+            eng.ntd_core_pgn(core, all_MtX, grams, sparse, delta, 300, st.norm_sq(), status=pg)
+        else:
+            Mk = grams[2]
+            for g in grams[3:]:
+                Mk = torch.kron(Mk.contiguous(), g.contiguous())
+            c3 = core.view(core.shape[0], core.shape[1], tail)
+            eng.ntd_core_pg(c3, all_MtX.view(c3.shape), [grams[0], grams[1], Mk], sparse, delta, 300, st.norm_sq(), status=pg)
     cost = st.block[st.cost_at:st.cost_at + 1]
     if normalize[-1]:
         core = _normalize_core(core, mode_core_norm)
