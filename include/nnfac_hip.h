@@ -260,6 +260,18 @@ int nnf_hals_stop_restore_f32(nnf_ctx* ctx, const double* sums_f64, int nsweeps,
 int nnf_mu_left_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
                     const float* V, int64_t ldv, int r, double beta, float* Ut_out, int64_t lduo, void* stream);
 
+/* mu_betadivmin (mu.py:79-97) for the factor of ONE mode of a tensor, on the tensor's own layout -- no unfolding is formed.
+ * T is contiguous and seen as (L, I, K): for mode n of an order-N tensor L is the product of the extents before n, I = I_n,
+ * K the product of those behind.  Ft (r x I, pitch ldf) is the mode's transposed factor, V (r x L*K, pitch ldv) the other
+ * operand -- khatri_rao(others)^T or the expanded core -- whose column l*K + k belongs to the entries T[l, :, k]:
+ *   out[k,i] = max(Ft[k,i] * (num[k,i]/den[k,i])^gamma(beta), 1e-12),  P[l,i,j] = sum_k Ft[k,i] V[k, l*K+j],
+ *   num[k,i] = sum_{l,j} T[l,i,j] P^(beta-2) V[k, l*K+j],  den[k,i] = sum_{l,j} P^(beta-1) V[k, l*K+j]  (beta=1: rowsum(V), fp64)
+ * One pass over T in place; the partial sums of the column splits go to the context workspace and are added in a fixed order
+ * in fp64 (two calls are bitwise equal).  Any beta >= 0, any L, I, K >= 1.  r <= 64 (else NNF_ERR_UNSUPPORTED); a workspace
+ * that cannot hold one set of r x I partial sums is refused with NNF_ERR_WORKSPACE; `out` must not alias Ft. */
+int nnf_mu_mode_f32(nnf_ctx* ctx, const float* T, int64_t L, int64_t I, int64_t K, const float* Ft, int64_t ldf,
+                    const float* V, int64_t ldv, int r, double beta, float* out, int64_t ldo, void* stream);
+
 /* nnf_mu_left_f32 with beta = 1 that also returns *cost_f64 = beta_divergence(X, U V, 1) of the factors it STARTS from
  * (mu.py:84-88 + nmf.py:455): the update forms every entry of U V anyway, so the cost of outer iteration i is a by-product of
  * the left update of iteration i+1 and the separate pass over X (nnf_betadiv_f32) is only needed after the last one.

@@ -15,6 +15,8 @@ The drivers supply what is theirs: how a step is enqueued, where cost and sweep 
 exception changes in their own switches.  Nothing here asks which driver it serves.
 """
 import dataclasses
+import math
+import os
 import time
 
 import torch
@@ -22,6 +24,18 @@ import torch
 from .utils import errors as err
 from . import engine as _engine
 from . import dist as _dist
+
+
+def mode_view(T, mode):
+    """The contiguous tensor as (prod of the extents before `mode`, I_mode, prod of those behind): a view."""
+    shape = [int(d) for d in T.shape]
+    return T.view(math.prod(shape[:mode]), shape[mode], math.prod(shape[mode + 1:]))
+
+
+def mu_on_layout(eng, r):
+    """Whether the MU update of a mode other than the last (whose unfolding is a view) runs on the tensor's own layout
+    (Engine.mu_mode) instead of a materialised unfolding: up to the kernel's rank, unless NNF_MU_UNFOLD=1 (read at call time)."""
+    return r <= eng.MU_MODE_MAX_RANK and os.environ.get("NNF_MU_UNFOLD") != "1"
 
 
 class StatusRing:

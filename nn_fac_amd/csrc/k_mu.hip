@@ -346,6 +346,21 @@ extern "C" int nnf_mu_right_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t
 }
 
 
+// the finishing step and the fp64 row sums for the other units (nnf_internal.h; k_mu_mode.hip)
+int nnf_launch_rowsum_f64(double* part, int np, const float* A, int64_t lda, int r, int64_t K, double* out, hipStream_t st) {
+    return nnf_launch_rowsum(part, np, A, lda, r, K, out, st);
+}
+int nnf_launch_mu_finish(const float* F, int64_t ldf, int r, int64_t cols, const float* snum, const float* sden, int nslab,
+                         int64_t slab_stride, int64_t lds, const double* den_vec, double beta, float* out, int64_t ldo,
+                         hipStream_t st) {
+    int64_t fg = nnf_cdiv((int64_t)r * cols, 256);
+    if (fg > 2048) fg = 2048;
+    hipLaunchKernelGGL(nnf_mu_finish_kernel, dim3((int)fg), dim3(256), 0, st, F, ldf, r, cols, snum, sden, nslab, slab_stride, lds,
+                       den_vec, gamma_of(beta), out, ldo);
+    NNF_CHECK_LAUNCH();
+    return NNF_OK;
+}
+
 // ---- two-phase right update for row-sharded runs: every rank accumulates the numerator / denominator
 // of its row block, the host all-reduces them, nnf_mu_apply_f32 finishes.  beta = 2 goes through the Gram form
 // (num = Ut X, den = (Ut U) V, both linear in the row blocks); beta = 1 has den[k] = colsum(U)[k] (r doubles).

@@ -126,3 +126,75 @@ inline void mu_report_left(FILE* f, int64_t m, int64_t n, int r, nnf_rank_tiles 
             (long long)m, (long long)n, r, t.MT, t.REM, (int)vec, mu_bm_name(BM), p.form, (long long)p.grid, (long long)p.n_hi,
             (long long)p.n_mid, more);
 }
+
+// ---- mode update on the tensor's own layout (k_mu_mode.hip) ----
+// T seen as (L, I, K): a workgroup owns MU_MODE_ROWS rows of I and a contiguous range of "units" -- one unit is 16 consecutive k
+// of one l (the last unit of an l is ragged when K % 16 != 0), so that no MFMA tile straddles two slabs of T.  A workgroup stages
+// MU_MODE_CHUNK units of V at a time in LDS.  The units are cut into `nsplit` ranges whose r x I partial numerators (and
+// denominators, beta != 1) go to slabs in the workspace and are added in split order in fp64.
+constexpr int MU_MODE_ROWS = 64;            // rows of I per workgroup: 4 waves x one 16-row tile
+constexpr int MU_MODE_UNIT = 16;            // k per unit: one MFMA tile
+constexpr int MU_MODE_CHUNK = 4;            // units per staged chunk of V
+// resident workgroups per CU the split count aims at: what the registers of an instantiation hold (build/k_mu_mode.s) -- four
+// 4-wave workgroups up to 128 VGPRs (beta = 1 up to MT = 3, and MT = 4 with 16-byte loads: 128; beta != 1 up to MT = 2: 108),
+// three beyond (beta = 1, MT = 4, scalar loads: 132; beta != 1, MT = 3 and 4: 136 .. 152).  LDS (4 KiB per rank tile) never binds.
+constexpr int mu_mode_wgpc(int MT, bool kl, bool vec) { return (kl ? (MT <= 3 || vec) : MT <= 2) ? 4 : 3; }
+// a workgroup sums its columns in fp32 MFMA accumulators: at most 256 units = 4096 columns, a chain of 1024 MFMA steps (the
+// W^T X kernel's 2048-row cap is a chain of 512; its notes in k_stream_plan.h say what longer chains cost)
+constexpr int64_t MU_MODE_UNITS_CAP = 256;
+constexpr int MU_MODE_MAX_RANK = 64;
+constexpr size_t mu_mode_shm(int MT) { return (size_t)MU_MODE_CHUNK * 16 * MT * MU_MODE_UNIT * 4; }
+struct mu_mode_plan {
+    int status;
+    int64_t nrb;        // row blocks of MU_MODE_ROWS rows
+    int64_t kt;         // units per l: ceil(K / 16)
+    int64_t units;      // L * kt
+    int64_t nsplit;     // column splits
+    int64_t ups;        // units per split (a multiple of MU_MODE_CHUNK)
+    const char* bound;  // which bound set the split count
+    int64_t ws_max;     // splits the free workspace holds
+    int pieces;         // of the row sums of V (beta = 1; else 0)
+    int64_t ldp;        // pitch of a slab row
+};
+// `cur`: a copy of the caller's cursor -- the update takes r doubles, the row sums' partials, then one (beta = 1) or two sets of
+// nsplit slabs of r x ldp floats
+inline mu_mode_plan mu_plan_mode(nnf_ws_cursor cur, int cus, int64_t L, int64_t I, int64_t K, int r, bool kl, bool vec) {
+    mu_mode_plan p{NNF_ERR_UNSUPPORTED, nnf_cdiv(I, MU_MODE_ROWS), nnf_cdiv(K, MU_MODE_UNIT), 0, 0, 0, "occupancy", 0, 0, nnf_rup(I, 4)};
+    if (r > MU_MODE_MAX_RANK) return p;
+    // element and column indices are 64-bit in the kernel; keep the products well inside them
+    if ((double)L * (double)I * (double)K >= 4.0e18 || (double)L * (double)p.kt >= 4.0e18) return p;
+    p.units = L * p.kt;
+    p.pieces = kl ? nnf_rowsum_pieces(L * K) : 0;
+    p.status = NNF_ERR_WORKSPACE;
+    if (!cur.reserve((size_t)r * 8) || (p.pieces > 1 && !cur.reserve((size_t)r * p.pieces * 8))) return p;
+    const int nsets = kl ? 1 : 2;
+    const int64_t slab_bytes = (int64_t)r * p.ldp * 4, free = (int64_t)cur.remaining();
+    p.ws_max = free / (slab_bytes * nsets);
+    while (nsets > 1 && p.ws_max >= 1 && nnf_rup(p.ws_max * slab_bytes, 256) + p.ws_max * slab_bytes > free) --p.ws_max;
+    if (p.ws_max < 1) return p;
+    p.nsplit = (int64_t)mu_mode_wgpc((r + 15) / 16, kl, vec) * cus / p.nrb;
+    if (p.nsplit < 1) p.nsplit = 1;
+    if (p.nsplit < nnf_cdiv(p.units, MU_MODE_UNITS_CAP)) { p.nsplit = nnf_cdiv(p.units, MU_MODE_UNITS_CAP); p.bound = "chain"; }
+    if (p.nsplit > nnf_cdiv(p.units, MU_MODE_CHUNK)) { p.nsplit = nnf_cdiv(p.units, MU_MODE_CHUNK); p.bound = "min_cols"; }
+    if (p.nsplit > p.ws_max) { p.nsplit = p.ws_max; p.bound = "workspace"; }
+    p.ups = nnf_rup(nnf_cdiv(p.units, p.nsplit), MU_MODE_CHUNK);
+    p.nsplit = nnf_cdiv(p.units, p.ups);
+    p.status = NNF_ERR_UNSUPPORTED;
+    if ((double)p.nrb * (double)p.nsplit > 2147483647.0) return p;   // one-dimensional grid
+    p.status = NNF_OK;
+    return p;
+}
+// bytes the launcher carves for a plan (tools/nnf_plan.cpp prints it; tests/test_mu_mode_plan.py checks it against a cursor)
+inline size_t mu_mode_ws_bytes(const mu_mode_plan& p, int r, bool kl) {
+    nnf_ws_cursor c(nullptr, ~size_t(0) >> 1);
+    c.reserve((size_t)r * 8);
+    if (p.pieces > 1) c.reserve((size_t)r * p.pieces * 8);
+    for (int s = 0; s < (kl ? 1 : 2); ++s) c.reserve((size_t)p.nsplit * r * p.ldp * 4);
+    return c.off;
+}
+inline void mu_report_mode(FILE* f, int64_t L, int64_t I, int64_t K, int r, int MT, bool vec, bool kl, const mu_mode_plan& p,
+                           const char* more = "") {
+    fprintf(f, "[nnf plan] mu_mode L=%lld I=%lld K=%lld r=%d mt=%d vec=%d bm=%s nrb=%lld nsplit=%lld ups=%lld units=%lld bound=%s%s\n",
+            (long long)L, (long long)I, (long long)K, r, MT, (int)vec, kl ? "KL" : "GEN", (long long)p.nrb, (long long)p.nsplit,
+            (long long)p.ups, (long long)p.units, p.bound, more);
+}

@@ -131,6 +131,15 @@ int nnf_small_gemm_launch(const float* A, int64_t lda, int p, int q, const float
 // out[0] = scale * sum of `count` doubles, index order, one workgroup
 int nnf_launch_sum_f64(const double* partial, int64_t count, double scale, double* out, hipStream_t st);
 
+// the fused MU updates' fp64 row sums and finishing step (k_mu.hip), shared with k_mu_mode.hip:
+// out[k] = sum_j A[k][j], np = nnf_rowsum_pieces(K) pieces, part: r x np doubles when np > 1
+int nnf_launch_rowsum_f64(double* part, int np, const float* A, int64_t lda, int r, int64_t K, double* out, hipStream_t st);
+// out = max(F * (num/den)^gamma(beta), 1e-12), num / den = the nslab slabs added in slab order in fp64 (den_vec: a per-row
+// denominator instead of sden)
+int nnf_launch_mu_finish(const float* F, int64_t ldf, int r, int64_t cols, const float* snum, const float* sden, int nslab,
+                         int64_t slab_stride, int64_t lds, const double* den_vec, double beta, float* out, int64_t ldo,
+                         hipStream_t st);
+
 int nnf_xty_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut,
                  int r, int64_t ldu, float* out, int64_t ldo, hipStream_t st);
 int nnf_xht_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V,

@@ -450,6 +450,28 @@ class Engine:
                    "nnf_mu_left_f32")
         return O
 
+    MU_MODE_MAX_RANK = 64   # the mode update on the tensor's own layout (mu_mode)
+
+    def mu_mode(self, T3, Ft, V, beta, out=None):
+        """mu_betadivmin of one mode's factor against tl.unfold(T, n) without forming it: `T3` is the contiguous tensor seen
+        as (L, I_n, K), `Ft` the mode's transposed factor (r x I_n), `V` the other operand (r x L*K, column l*K + k for the
+        entries T3[l, :, k]).  r <= 64 (nnf_mu_mode_f32)."""
+        _chk2d(Ft, "mu Ft"), _chk2d(V, "mu V")
+        if T3.dim() != 3 or T3.dtype != torch.float32 or not T3.is_cuda or not T3.is_contiguous():
+            raise EngineError("mu_mode: T3 must be a contiguous float32 device tensor seen as (L, I, K)")
+        L, I, K = (int(d) for d in T3.shape)
+        r = Ft.shape[0]
+        if Ft.shape[1] != I or tuple(V.shape) != (r, L * K):
+            raise EngineError("mu_mode: shape mismatch")
+        if r > self.MU_MODE_MAX_RANK:
+            raise EngineError("mu_mode: built for r <= 64")
+        if out is not None and (_chk2d(out, "mu out").shape != Ft.shape or out.device != Ft.device):
+            raise EngineError("mu_mode: out must be an r x I float32 tensor on the factor's device")
+        O = out if out is not None else torch.empty_like(Ft)
+        _lib.check(self.lib.nnf_mu_mode_f32(self.ctx, _ptr(T3), L, I, K, _ptr(Ft), _ld(Ft), _ptr(V), _ld(V), r, float(beta),
+                                            _ptr(O), _ld(O), self._stream()), "nnf_mu_mode_f32")
+        return O
+
     def mu_right(self, X, Ut, V, beta, out=None):
         _chk2d(X, "mu X"), _chk2d(Ut, "mu Ut"), _chk2d(V, "mu V")
         m, n = X.shape

@@ -15,8 +15,9 @@ HALS step, per updated mode n (factors kept transposed, r_n x I_n; statement -> 
     F_n = hals_nnls_acc(UtM, UtU, F_n^T)^T               (ntd.py:571-573)  nnf_hals_solve_f32
     core: step, <= 300 projected-gradient steps, error   (ntd.py:581-619,639) nnf_ntd_core_pg_f32 (one launch, fp64 in LDS)
 
-MU step: the factor updates are mu_betadivmin on the transposed unfoldings (nnf_mu_right_f32 on (prod other dims) x I_n:
-the last mode is a view of T, modes 0 and 1 are materialised once per run), the core update mu_tensorial (mu.py:99-159) is the right-update accumulation of the mode-0 problem
+MU step: the factor updates are mu_betadivmin on the tensor's own layout (nnf_mu_mode_f32 on the (before, I_n, behind) view of T;
+the last mode is nnf_mu_right_f32 on the (prod other dims) x I_n view it already is, and above rank 64 the other modes'
+transposed unfoldings are materialised once per run as before), the core update mu_tensorial (mu.py:99-159) is the right-update accumulation of the mode-0 problem
 (nnf_mu_right_accum_f32 -- U V is never materialised) followed by two core-sized contractions, and the cost is
 nnf_betadiv_f32 on the mode-0 problem.
 
@@ -100,7 +101,7 @@ class _NtdState(_loop.StatusRing):
 
     def unfolded_t(self, mode):
         """tl.unfold(T, mode)^T as a contiguous (prod(other dims)) x I_mode matrix (MU path).  The last mode is a view of T;
-        modes 0 and 1 are materialised once per run."""
+        the others are materialised once per run -- only above rank 64 or under NNF_MU_UNFOLD=1 (_outer_loop.mu_on_layout)."""
         if mode not in self._unf_t:
             self._unf_t[mode] = torch.movedim(self.T, mode, -1).reshape(-1, self.T.shape[mode]).contiguous()
         return self._unf_t[mode]
@@ -363,7 +364,14 @@ def _one_ntd_step_mu_dev(st, core_in, Ft_in, beta, fixed_modes, normalize, mode_
             V = V.reshape(V.shape[0], -1).contiguous()
         # mu_betadivmin(F, V, unfold(T, mode)) (ntd.py:672) on the TRANSPOSED problem unfold^T ~ V^T F^T: the unfolding is
         # short and fat (I_mode rows), its transpose gives the streaming kernel prod(other dims) rows to split over
-        Ft[mode] = eng.mu_right(st.unfolded_t(mode), V, Ft[mode], beta)
+        # (the last mode's is a view of T).  Every other mode is updated on the tensor's own layout against the same V
+        # (nnf_mu_mode_f32, r_mode <= 64): no transposed copy of T; NNF_MU_UNFOLD=1 restores the unfolding.
+        if mode == N - 1:
+            Ft[mode] = eng.mu_right(st.T.view(-1, st.T.shape[mode]), V, Ft[mode], beta)
+        elif _loop.mu_on_layout(eng, Ft[mode].shape[0]):
+            Ft[mode] = eng.mu_mode(_loop.mode_view(st.T, mode), Ft[mode], V, beta)
+        else:
+            Ft[mode] = eng.mu_right(st.unfolded_t(mode), V, Ft[mode], beta)
     core = _mu_tensorial_dev(st, core, Ft, beta)
     if normalize[-1]:
         core = _normalize_core(core, mode_core_norm)

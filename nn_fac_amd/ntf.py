@@ -7,7 +7,8 @@ Per updated mode the reference statements map to the C ABI as follows (factors k
     krao ; rhs = unfolded[mode] @ krao             (ntf.py:448-449) -> nnf_mttkrp3_f32 (one pass over the tensor IN PLACE:
                                                      neither the unfoldings nor the Khatri-Rao matrix are materialised)
     hals_nnls_acc(rhs^T, cross, F[mode]^T)         (ntf.py:454-456) -> nnf_hals_solve_f32
-    mu_betadivmin(F[mode], krao^T, unfolded[mode]) (ntf.py:459-460) -> nnf_mu_right_f32 on the transposed unfolding (MU path only)
+    mu_betadivmin(F[mode], krao^T, unfolded[mode]) (ntf.py:459-460) -> nnf_mu_mode_f32 on the tensor's own layout (r <= 64; the
+                                                      last mode, and larger ranks: nnf_mu_right_f32 on the transposed unfolding)
     cost                                           (ntf.py:462-475) -> HALS loops: the reference's own form
         ||T||^2 - 2<F,rhs> + sum_k f_k^T cross f_k on the last updated mode's operands, inner products in fp64, with the
         kernel's error estimate as a guard (nnf_nmf_gram_cost_f32: no pass over T); wherever that form cannot carry the
@@ -148,7 +149,8 @@ class _NtfState(_loop.StatusRing):
         return G
 
     def unfolded_t(self, mode):
-        """tl.unfold(T, mode)^T = moveaxis(mode -> last).reshape(-1, dim), contiguous (MU path; the last mode is a view)."""
+        """tl.unfold(T, mode)^T = moveaxis(mode -> last).reshape(-1, dim), contiguous (MU path; the last mode is a view).
+        The other modes are only materialised above rank 64 or under NNF_MU_UNFOLD=1 (_outer_loop.mu_on_layout)."""
         if mode not in self._unf:
             self._unf[mode] = torch.movedim(self.T, mode, -1).reshape(-1, self.T.shape[mode]).contiguous()
         return self._unf[mode]
@@ -315,7 +317,15 @@ def _one_ntf_step_dev(st, rank, Ft_in, update_rule, beta, sparsity_coefficients,
         else:
             # mu_betadivmin(F, krao^T, unfold) (ntf.py:459-460) on the transposed problem unfold^T ~ krao F^T: the unfolding
             # has only I_mode rows, its transpose gives the streaming kernel prod(other dims) rows to split over
-            Ft[mode] = eng.mu_right(st.unfolded_t(mode), _krao_t(Ft, mode), Ft[mode], beta)
+            # (the last mode's unfolding is a view of T).  Every other mode is updated on the tensor's own layout, seen as
+            # (extents before) x I_mode x (extents behind), against the same operand (nnf_mu_mode_f32, r <= 64): no transposed
+            # copy of T.  NNF_MU_UNFOLD=1 (read at call time) takes the unfolding for every mode, for A/B runs.
+            if mode == st.T.dim() - 1:
+                Ft[mode] = eng.mu_right(st.T.view(-1, st.T.shape[mode]), _krao_t(Ft, mode), Ft[mode], beta)
+            elif _loop.mu_on_layout(eng, Ft[mode].shape[0]):
+                Ft[mode] = eng.mu_mode(_loop.mode_view(st.T, mode), Ft[mode], _krao_t(Ft, mode), beta)
+            else:
+                Ft[mode] = eng.mu_right(st.unfolded_t(mode), _krao_t(Ft, mode), Ft[mode], beta)
 
     if not skip_cost:
         _ntf_cost(eng, st, Ft, update_rule, beta, sparsity_coefficients, st.block[st.cost_at:st.cost_at + 3],

@@ -2,12 +2,15 @@
 // k_mu_plan.h) for any CU count, printed as the library reports them under NNF_PLAN_DEBUG.
 //
 //   nnf_plan < cases     one case per line:  <launcher> <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [key=value ...]
-//                        launcher: xht | xty | mu_left | mu_right | mttkrp_rows; the factors are contiguous (r x m, r x n);
+//                        launcher: xht | xty | mu_left | mu_right | mu_mode | mttkrp_rows; the factors are contiguous (r x m, r x n);
 //                        optional keys: align= (offset of X from a 16-byte boundary, in floats; default 0) and, for mttkrp_rows
 //                        (m x n = the unfolded tensor, pitch n), nb= lda= ldb= (Khatri-Rao inner length, factor pitches).
 //                        Answer, one line per case: the "[nnf plan] ..." line of that launch, followed on the same line by the
 //                        fields of the plan the report leaves out (slots, ncb, ws_max), or "status=<code>" for a refusal.
 //                        beta = 2 (the Gram form of the MU updates: X H^T / W^T X + a Gram) is not a plan of these launchers.
+//                        mu_mode (the mode update on the tensor's own layout, any beta) reads the same eight fields as
+//                          mu_mode <CUs> <L> <I> <r> <K> <beta> <workspace bytes> [align=] [ldv=]
+//                        and adds kt= wgpc= ws_max= pieces= ldp= ws_bytes= (what the launcher carves for the plan).
 //   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
 //                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
 //
@@ -35,7 +38,7 @@ static int print_shm() {
 
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "shm") == 0) return print_shm();
-    char line[512], name[32], more[96];
+    char line[512], name[32], more[160];
     while (fgets(line, sizeof line, stdin)) {
         long long C, m, n, r, ld, ws;
         double beta;
@@ -51,7 +54,19 @@ int main(int argc, char** argv) {
         const bool left = strcmp(name, "mu_left") == 0;
         int status = NNF_ERR_UNSUPPORTED;   // (ranks above 128 run in passes of 128: ask for one pass)
         more[0] = 0;
-        if (m < 1 || n < 1 || r < 1 || ld < n) {
+        if (strcmp(name, "mu_mode") == 0) {   // m = L, n = I, ld = K
+            const long long ldv = key_of(rest, "ldv", m * ld);
+            const bool kl = beta == 1.0, mvec = key_of(rest, "align", 0) % 4 == 0 && ld % 4 == 0 && ldv % 4 == 0;
+            if (m < 1 || n < 1 || ld < 1 || r < 1 || !(beta >= 0.0) || ldv < m * ld) {
+                status = NNF_ERR_ARG;
+            } else {
+                const mu_mode_plan p = mu_plan_mode(cur, (int)C, m, n, ld, (int)r, kl, mvec);
+                snprintf(more, sizeof more, " kt=%lld wgpc=%d ws_max=%lld pieces=%d ldp=%lld ws_bytes=%zu", (long long)p.kt,
+                         mu_mode_wgpc((int)(r + 15) / 16, kl, mvec), (long long)p.ws_max,
+                         p.pieces, (long long)p.ldp, p.status == NNF_OK ? mu_mode_ws_bytes(p, (int)r, kl) : (size_t)0);
+                if ((status = p.status) == NNF_OK) mu_report_mode(stdout, m, n, ld, (int)r, (int)(r + 15) / 16, mvec, kl, p, more);
+            }
+        } else if (m < 1 || n < 1 || r < 1 || ld < n) {
             status = NNF_ERR_ARG;
         } else if (r > NNF_MAX_RANK) {
         } else if (strcmp(name, "xty") == 0) {
