@@ -59,7 +59,8 @@ typedef struct nnf_ctx nnf_ctx;
 #define NNF_HALS_ST_CNT 1     /* cnt as returned by the reference = sweeps done + 1 (:196)     */
 #define NNF_HALS_ST_EPS0 2    /* nodelta of the first sweep                (nnls.py:188)       */
 #define NNF_HALS_ST_ERR 3     /* 0 ok; 1 = grid barrier timed out (result invalid);
-                                 2 = zero Gram diagonal met with NONZERO set (nnls.py:176-177) */
+                                 2 = zero Gram diagonal met with NONZERO set (nnls.py:176-177);
+                                 5 = nnf_hals_solve_group_f32: the group's column range is not valid */
 #define NNF_HALS_ST_WORDS 8
 
 int nnf_version(void);
@@ -396,6 +397,55 @@ int nnf_dot_f32(nnf_ctx* ctx, const float* A, int64_t lda, const float* B, int64
                 double* out_f64, void* stream);
 /* C = A .* B elementwise, r x r  (Hadamard of Grams, ntf.py:442-445) */
 int nnf_hadamard_f32(nnf_ctx* ctx, const float* A, const float* B, float* C, int64_t count, void* stream);
+
+/* ---- grouped kernels: the K slices of nonnegative PARAFAC2 (nn_fac/parafac2.py:509-600) in one launch each --------------
+ * Group g owns the columns [off[g], off[g+1]) of stacked operands with `total_cols` columns; `off` is a DEVICE array of
+ * ngroups + 1 int64 (non-decreasing, within [0, total_cols]).  The host cannot see it, so the caller declares what it needs to
+ * know (max_group_cols) and the kernels check each group against that: a group whose range is not valid is skipped whole --
+ * nothing of it is read or written (the solve marks its status block with NNF_HALS_ST_ERR = 5).  fp32 storage, sums in a
+ * fixed order (two calls are bitwise equal), r <= NNF_MAX_RANK (NNF_ERR_UNSUPPORTED above), every refusal before anything is
+ * launched or written.  No kernel here exchanges anything between workgroups (no grid barrier, no flag in memory), and none
+ * asks for more than 132 KB of LDS. */
+
+/* The longest group nnf_hals_solve_group_f32 takes.  One workgroup of 128 threads owns a group and walks its columns in
+ * tiles of 128 once per sweep, so a group is r*r*len/128 dependent FMAs per sweep on ONE compute unit, and what it re-reads
+ * per sweep, r*len floats, is 4 MiB -- one XCD's L2 -- at r = 128 and 8192 columns.  A longer group belongs to
+ * nnf_hals_solve_f32, which spreads one solve over all compute units. */
+#define NNF_HALS_GROUP_MAX_COLUMNS 8192
+int nnf_hals_group_max_columns(nnf_ctx* ctx, int r, int64_t* columns_out);
+
+/* ngroups independent solves with the semantics of nnf_hals_solve_f32 without flags (Gauss-Seidel over the rows, projection,
+ * rows with a zero Gram diagonal left alone, eps0 from the first sweep, on while eps >= delta*eps0 and sweeps < max_sweeps;
+ * fp32 row dots in index order, squared steps summed in fp64).  UtM and V: r x total_cols (ldm, ldv), V in/out; the Gram of
+ * group g is the dense r x r matrix at UtU + g*gstride (row stride ldg); status_f64: ngroups blocks of NNF_HALS_ST_WORDS
+ * doubles in the NNF_HALS_ST_* layout.  One workgroup per group: the stopping rule is a sum over that workgroup.
+ * max_group_cols: the caller's bound on the group lengths, <= NNF_HALS_GROUP_MAX_COLUMNS (else NNF_ERR_UNSUPPORTED).  Groups of
+ * one column (K diagonal updates in one launch) and empty groups are fine; max_sweeps = 1 on a copy is a probe sweep. */
+int nnf_hals_solve_group_f32(nnf_ctx* ctx, const float* UtM, int64_t ldm, const float* UtU, int64_t ldg, int64_t gstride,
+                             float* V, int64_t ldv, int r, const int64_t* off, int ngroups, int64_t max_group_cols,
+                             int64_t total_cols, int max_sweeps, double delta, double* status_f64, void* stream);
+
+/* Per group, one pass over A (r x total_cols): G (may be NULL) receives A_g A_g^T as fp32 at G + g*gstride (row stride ldg)
+ * and G64 (may be NULL; needs G) the same sums before their rounding, ngroups contiguous r x r blocks of doubles (as
+ * nnf_gram_f64_f32 gives them: the Gram of a product A = W W*^T carries the square of its condition number);
+ * dots_f64 (may be NULL; then B is ignored) receives c_g[q] = sum_i A[q,i] B[q,i] at dots_f64[g*r + q]; err_f64 (may be NULL;
+ * then T is ignored) receives ||A_g - T_g||_F^2 at err_f64[g].  All sums in fp64.  Any group length. */
+int nnf_group_gram_f32(nnf_ctx* ctx, const float* A, int64_t lda, int r, const int64_t* off, int ngroups, int64_t total_cols,
+                       float* G, int64_t ldg, int64_t gstride, double* G64, const float* B, int64_t ldb, double* dots_f64,
+                       const float* T, int64_t ldt, double* err_f64, void* stream);
+
+/* out[:, seg g] = M_g A[:, seg g]:  M_g is p x q at M + g*mstride (row stride ldm), A q x total_cols, out p x total_cols (must
+ * not alias A), p, q <= 128 (NNF_ERR_UNSUPPORTED above).  max_group_cols sizes the launch only (longer groups are still
+ * computed).  fp32 FMAs in index order. */
+int nnf_group_gemm_f32(nnf_ctx* ctx, const float* M, int64_t ldm, int64_t mstride, int p, int q, const float* A, int64_t lda,
+                       const int64_t* off, int ngroups, int64_t max_group_cols, int64_t total_cols, float* out, int64_t ldo,
+                       void* stream);
+
+/* rows_f64[i] = sum_j (X[i,j] - sum_k Ut[k,i] V[k,j])^2, i < m: the per-row form of nnf_frob_resid_f32 in one streaming pass
+ * over X; the model tile comes from the 16x16x4 fp32 MFMA and is never stored.  Per-slice costs of stacked slices are segment
+ * sums of it.  r <= NNF_MAX_RANK. */
+int nnf_frob_resid_rows_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
+                            const float* V, int64_t ldv, int r, double* rows_f64, void* stream);
 
 #ifdef __cplusplus
 }

@@ -386,6 +386,98 @@ class Engine:
             hit = self._resident_cols[int(r)] = int(out.value)
         return hit
 
+    # ---- grouped kernels (PARAFAC2: K per-slice problems per launch) ------------------------------------
+    @staticmethod
+    def _chk_off(off, what):
+        if off.dtype != torch.int64 or not off.is_cuda or off.dim() != 1 or not off.is_contiguous() or off.numel() < 2:
+            raise EngineError(f"{what}: the segment table must be a contiguous int64 device vector of ngroups + 1 entries")
+        return off.numel() - 1
+
+    @staticmethod
+    def _chk_stack(M, what):
+        if M.dim() != 3 or M.dtype != torch.float32 or not M.is_cuda or (M.shape[2] > 1 and M.stride(2) != 1):
+            raise EngineError(f"{what}: expected a float32 device stack [groups, rows, cols] with unit inner stride")
+        return M
+
+    def hals_group_max_columns(self, r):
+        """Longest group hals_solve_group takes (nnf_hals_group_max_columns); longer ones go through hals_solve."""
+        out = C.c_int64(0)
+        _lib.check(self.lib.nnf_hals_group_max_columns(self.ctx, int(r), C.byref(out)), "nnf_hals_group_max_columns")
+        return int(out.value)
+
+    def hals_solve_group(self, UtM, UtU, V, off, max_group_cols, max_sweeps, delta=0.01, status=None):
+        """One accelerated-HALS solve per group in ONE launch, in place on V (r x total): group g owns the columns
+        [off[g], off[g+1]), its Gram is UtU[g] (a [groups, r, r] stack).  `max_group_cols`: the caller's bound on the group
+        lengths (the table lives on the device).  Returns the [groups, 8] float64 status tensor (device, not synced)."""
+        _chk2d(UtM, "group UtM"), _chk2d(V, "group V"), self._chk_stack(UtU, "group UtU")
+        ng = self._chk_off(off, "hals_solve_group")
+        r, total = V.shape
+        if UtM.shape != (r, total) or UtU.shape[0] != ng or UtU.shape[1] < r or UtU.shape[2] < r:
+            raise EngineError("hals_solve_group: shape mismatch")
+        st = status if status is not None else torch.zeros((ng, ST_WORDS), dtype=torch.float64, device=V.device)
+        if st.dtype != torch.float64 or not st.is_contiguous() or st.numel() < ng * ST_WORDS:
+            raise EngineError("hals_solve_group: status must be a contiguous float64 tensor of 8 doubles per group")
+        _lib.check(self.lib.nnf_hals_solve_group_f32(self.ctx, _ptr(UtM), _ld(UtM), _ptr(UtU), UtU.stride(1), UtU.stride(0),
+                                                     _ptr(V), _ld(V), r, _ptr(off), ng, int(max_group_cols), total,
+                                                     int(max_sweeps), float(delta), _ptr(st), self._stream()),
+                   "nnf_hals_solve_group_f32")
+        return st
+
+    def group_gram(self, A, off, B=None, T=None, gram=True, out64=None):
+        """Per group of columns of A (r x total), one pass: (G [groups, r, r] float32 = A_g A_g^T or None, dots [groups, r] float64
+        = sum_i A[q,i] B[q,i] or None, err [groups] float64 = ||A_g - T_g||_F^2 or None).  out64 (optional, contiguous
+        [groups, r, r] float64 device tensor): also receives the Gram sums before they are rounded to fp32."""
+        _chk2d(A, "group_gram A")
+        ng = self._chk_off(off, "group_gram")
+        r, total = A.shape
+        for t, nm in ((B, "B"), (T, "T")):
+            if t is not None and _chk2d(t, "group_gram " + nm).shape != A.shape:
+                raise EngineError("group_gram: shape mismatch")
+        if not gram and B is None and T is None:
+            raise EngineError("group_gram: nothing asked for")
+        if out64 is not None and (not gram or out64.dtype != torch.float64 or not out64.is_contiguous() or not out64.is_cuda
+                                  or out64.numel() < ng * r * r):
+            raise EngineError("group_gram: out64 must be a contiguous float64 device tensor of groups*r*r elements (with gram=True)")
+        G = torch.empty((ng, r, r), dtype=torch.float32, device=A.device) if gram else None
+        dots = torch.empty((ng, r), dtype=torch.float64, device=A.device) if B is not None else None
+        errs = torch.empty(ng, dtype=torch.float64, device=A.device) if T is not None else None
+        _lib.check(self.lib.nnf_group_gram_f32(self.ctx, _ptr(A), _ld(A), r, _ptr(off), ng, total,
+                                               _ptr(G) if gram else None, r, r * r, _ptr(out64) if out64 is not None else None,
+                                               _ptr(B) if B is not None else None, _ld(B) if B is not None else 0,
+                                               _ptr(dots) if dots is not None else None,
+                                               _ptr(T) if T is not None else None, _ld(T) if T is not None else 0,
+                                               _ptr(errs) if errs is not None else None, self._stream()), "nnf_group_gram_f32")
+        return G, dots, errs
+
+    def group_gemm(self, M, A, off, max_group_cols, out=None):
+        """out[:, seg g] = M[g] @ A[:, seg g] for a [groups, p, q] stack M (p, q <= 128) and A (q x total)."""
+        _chk2d(A, "group_gemm A"), self._chk_stack(M, "group_gemm M")
+        ng = self._chk_off(off, "group_gemm")
+        q, total = A.shape
+        p = M.shape[1]
+        if M.shape[0] != ng or M.shape[2] != q:
+            raise EngineError("group_gemm: shape mismatch")
+        O = out if out is not None else torch.empty((p, total), dtype=torch.float32, device=A.device)
+        if _chk2d(O, "group_gemm out").shape != (p, total) or O.data_ptr() == A.data_ptr():
+            raise EngineError("group_gemm: out must be a p x total float32 tensor that does not alias A")
+        _lib.check(self.lib.nnf_group_gemm_f32(self.ctx, _ptr(M), M.stride(1), M.stride(0), p, q, _ptr(A), _ld(A), _ptr(off), ng,
+                                               int(max_group_cols), total, _ptr(O), _ld(O), self._stream()), "nnf_group_gemm_f32")
+        return O
+
+    def frob_resid_rows(self, X, Ut, V, out=None):
+        """Per-row ||x_i - (Ut^T V)_i||^2 as m float64 on the device (one streaming pass, nnf_frob_resid_rows_f32)."""
+        _chk2d(X, "frob X"), _chk2d(Ut, "frob Ut"), _chk2d(V, "frob V")
+        m, n = X.shape
+        r = Ut.shape[0]
+        if Ut.shape[1] != m or V.shape != (r, n):
+            raise EngineError("frob_resid_rows: shape mismatch")
+        o = out if out is not None else torch.empty(m, dtype=torch.float64, device=X.device)
+        if o.dtype != torch.float64 or not o.is_contiguous() or o.numel() < m:
+            raise EngineError("frob_resid_rows: out must be a contiguous float64 tensor of m elements")
+        _lib.check(self.lib.nnf_frob_resid_rows_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V), _ld(V), r,
+                                                    _ptr(o), self._stream()), "nnf_frob_resid_rows_f32")
+        return o
+
     def hals_stop_restore(self, sums, head, budget, delta, V, snapshots, status):
         """Device-side replay of the stopping rule over the all-reduced per-sweep sums of a blind chunk (dist.py)."""
         _chk2d(V, "hals V")

@@ -172,3 +172,40 @@ def ntd_initialization(tensor, ranks, init_type, deterministic=False, seed=0):
         factors[0] = np.identity(12)
         return core, factors
     raise err.InvalidInitializationType("Initialization type not understood.")
+
+
+def parafac2_initialization(tensor_slices, rank, init_type, init_with_P, deterministic=False, seed=0):
+    """Initial factors of nonnegative PARAFAC2 -- nn_fac/utils/initialize_factors.py:111-156.  Returns NumPy arrays
+    ``(W_list, H, D_list, P_list, W_star)`` like the reference.
+
+    "random" draws from the reference's legacy global stream in the reference's order (:121-137: H, then W_k and diag D_k
+    per slice, then W*), with each slice's own row count where the reference takes that of the first slice: bit-identical to
+    the reference for equal-shaped slices.  P_k is the zero-padded identity of m_k rows; W* is m_0 x rank, as there.
+    "nndsvd": the reference's branch (:139-156) ends without a return statement, so its caller fails to unpack None; said
+    here instead."""
+    K = len(tensor_slices)
+    rows = [int(s.shape[0]) for s in tensor_slices]
+    n = int(tensor_slices[0].shape[1])
+    if deterministic:
+        np.random.seed(seed)
+        random.seed(seed)
+    kind = init_type.lower()
+    if kind == "random":
+        H = np.random.rand(rank, n)
+        W_list, D_list = [], []
+        for k in range(K):
+            W_list.append(np.random.rand(rows[k], rank))
+            D_list.append(np.diag(np.random.rand(rank)))
+        D_list = np.array(D_list)
+        if init_with_P:
+            P_list = [np.identity(rows[k])[:, 0:rank] for k in range(K)]
+            W_star = None
+        else:
+            W_star = np.random.rand(rows[0], rank)
+            P_list = None
+        return W_list, H, D_list, P_list, W_star
+    if kind == "nndsvd":
+        raise NotImplementedError('parafac2_initialization(init_type="nndsvd"): the reference\'s branch '
+                                  "(nn_fac/utils/initialize_factors.py:139-156) builds the factors and returns nothing, so "
+                                  "parafac_2 cannot run from it there either; use \"random\" or \"custom\"")
+    raise err.InvalidInitializationType("Initialization type not understood.")
