@@ -368,38 +368,26 @@ __global__ __launch_bounds__(256, (MT <= 4 ? 2 : 1)) void nnf_mttkrp_rows_kernel
     }
 }
 
+// plan (k_stream_plan.h; a refusal launches nothing), report, carve, launch, reduce
 template <int MT, bool VEC>
 static int launch_seg(nnf_ctx* ctx, const float* T, int64_t nrows, int64_t ldrow, int64_t nseg, int64_t segstride,
                       int64_t klen, const float* Fs, int64_t lds_, const float* Fk, int64_t ldk, int r, float* out,
                       int64_t ldo, hipStream_t st) {
-    if ((64 * ldrow + klen + 256) * 4 >= (int64_t)0x7fff0000 || (int64_t)(16 * MT) * lds_ * 4 >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;
-    const int nrb = (int)nnf_cdiv(nrows, 256);
-    const int64_t ldp = nnf_rup(nrows, 4);
-    int64_t nsplit = 2 * (int64_t)ctx->num_cus / nrb;
-    const char* bound = "occupancy";      // (report only, NNF_PLAN_DEBUG)
-    if (nsplit < 1) { nsplit = 1; bound = "one"; }
-    if (nsplit > nseg) { nsplit = nseg; bound = "segments"; }
     nnf_ws_cursor cur(ctx);
-    const int64_t slab_elems = (int64_t)r * ldp;
-    const int64_t ws_max = (int64_t)(cur.remaining() / 4) / slab_elems;
-    if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
-    const int64_t sps = nnf_cdiv(nseg, nsplit);
-    nsplit = nnf_cdiv(nseg, sps);
+    const nnf_seg_plan pl = nnf_plan_seg(ctx->num_cus, nrows, ldrow, nseg, klen, r, lds_, cur.remaining());
+    if (pl.status != NNF_OK) return pl.status;
+    const int fk_vec_ok = x_vec_ok(Fk, ldk) ? 1 : 0;
+    if (nnf_plan_debug()) nnf_report_seg(stderr, nrows, nseg, klen, r, MT, VEC, fk_vec_ok, MT <= 2, pl);
+    const int nrb = (int)nnf_cdiv(nrows, 256), nsplit = (int)pl.nsplit;
+    const int64_t ldp = nnf_rup(nrows, 4), slab_elems = (int64_t)r * ldp;
     float* slabs = (float*)cur.take((size_t)nsplit * slab_elems * 4);
-    if (!slabs) return NNF_ERR_WORKSPACE;
-    const int fk_vec_ok = ((((uintptr_t)Fk) & 15) == 0 && (ldk & 3) == 0) ? 1 : 0;
-    const int grid = 8 * (int)nnf_cdiv(nsplit, 8) * nrb;
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] mttkrp_seg nrows=%lld nseg=%lld klen=%lld r=%d mt=%d VEC=%d fkvec=%d pp=%d nsplit=%lld sps=%lld bound=%s\n",
-                (long long)nrows, (long long)nseg, (long long)klen, r, MT, (int)VEC, fk_vec_ok, (int)(MT <= 2), (long long)nsplit,
-                (long long)sps, bound);
+    if (!slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
     nnf_probe(ctx, NNF_PROBE_MTTKRP, 0, st);
-    hipLaunchKernelGGL((nnf_mttkrp_seg_kernel<MT, VEC>), dim3(grid), dim3(256), 0, st, T, nrows, ldrow, nseg, segstride,
-                       klen, Fs, lds_, Fk, ldk, r, slabs, ldp, nrb, (int)nsplit, sps, fk_vec_ok);
+    hipLaunchKernelGGL((nnf_mttkrp_seg_kernel<MT, VEC>), dim3(nnf_split_grid(nsplit, nrb)), dim3(256), 0, st, T, nrows, ldrow,
+                       nseg, segstride, klen, Fs, lds_, Fk, ldk, r, slabs, ldp, nrb, nsplit, pl.sps, fk_vec_ok);
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_MTTKRP, 1, st);
-    return nnf_launch_reduce_slabs(slabs, (int)nsplit, slab_elems, r, nrows, ldp, out, ldo, st);
+    return nnf_launch_reduce_slabs(slabs, nsplit, slab_elems, r, nrows, ldp, out, ldo, st);
 }
 
 // plan (k_stream_plan.h; a refusal launches nothing), report, carve, launch, reduce
@@ -443,7 +431,7 @@ static int seg_dispatch(nnf_ctx* ctx, const float* T, int64_t nrows, int64_t ldr
                         int64_t klen, const float* Fs, int64_t lds_, const float* Fk, int64_t ldk, int R, float* out,
                         int64_t ldo, hipStream_t st) {
     const int MT = (R + 15) / 16;
-    const bool vec = ((((uintptr_t)T) & 15) == 0) && (ldrow % 4 == 0) && (segstride % 4 == 0);
+    const bool vec = x_vec_ok(T, ldrow) && segstride % 4 == 0;
     if (vec) { MTTKRP_MT(launch_seg, true, ctx, T, nrows, ldrow, nseg, segstride, klen, Fs, lds_, Fk, ldk, R, out, ldo, st) }
     else { MTTKRP_MT(launch_seg, false, ctx, T, nrows, ldrow, nseg, segstride, klen, Fs, lds_, Fk, ldk, R, out, ldo, st) }
 }
@@ -569,34 +557,22 @@ extern "C" int nnf_mttkrp3_from_partial_f32(nnf_ctx* ctx, const float* Y, int64_
     }
     hipStream_t st = (hipStream_t)stream;
     if (axis == 2) {
-        int64_t grid = nnf_cdiv((int64_t)R * A, 4);
-        if (grid > 8192) grid = 8192;
-        if (nnf_plan_debug())
-            fprintf(stderr, "[nnf plan] partial_last A=%lld B=%lld r=%d grid=%lld strided=%d\n", (long long)A, (long long)B, R,
-                    (long long)grid, (int)((int64_t)R * A > 4 * grid));
-        hipLaunchKernelGGL(nnf_partial_last_kernel, dim3((int)grid), dim3(256), 0, st, Y, A, B, Ft, ldf, R, out, ldo);
+        const nnf_partial_last_plan pl = nnf_plan_partial_last(A, R);
+        if (nnf_plan_debug()) nnf_report_partial_last(stderr, A, B, R, pl);
+        hipLaunchKernelGGL(nnf_partial_last_kernel, dim3((int)pl.grid), dim3(256), 0, st, Y, A, B, Ft, ldf, R, out, ldo);
         NNF_CHECK_LAUNCH();
         return NNF_OK;
     }
-    // axis 1: enough a-chunks to fill the chip, at least 16 rows each
-    const int64_t cb = nnf_cdiv(B, 256);
-    int64_t nchunk = nnf_cdiv((int64_t)4 * ctx->num_cus, cb * R);
-    const char* bound = "occupancy";      // (report only, NNF_PLAN_DEBUG)
-    if (nchunk < 1) nchunk = 1;
-    if (nchunk > nnf_cdiv(A, 16)) { nchunk = nnf_cdiv(A, 16); bound = "rows16"; }
-    if (nchunk > 65535) { nchunk = 65535; bound = "grid"; }
-    const int64_t a_per = nnf_cdiv(A, nchunk);
-    nchunk = nnf_cdiv(A, a_per);
-    const int64_t ldp = nnf_rup(B, 4);
+    // axis 1: plan (a refusal launches nothing), report, carve, launch, reduce
     nnf_ws_cursor cur(ctx);
+    const nnf_partial_mid_plan pl = nnf_plan_partial_mid(ctx->num_cus, A, B, R, cur.remaining());
+    if (pl.status != NNF_OK) return pl.status;
+    if (nnf_plan_debug()) nnf_report_partial_mid(stderr, A, B, R, pl);
+    const int64_t cb = nnf_cdiv(B, 256), ldp = nnf_rup(B, 4), nchunk = pl.nchunk;
     float* slabs = (float*)cur.take((size_t)nchunk * R * ldp * 4);
-    if (!slabs) return NNF_ERR_WORKSPACE;
-    if (cb > 65535) return NNF_ERR_UNSUPPORTED;
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] partial_mid A=%lld B=%lld r=%d nchunk=%lld a_per=%lld bound=%s\n", (long long)A, (long long)B, R,
-                (long long)nchunk, (long long)a_per, bound);
+    if (!slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
     hipLaunchKernelGGL(nnf_partial_mid_kernel, dim3((unsigned)cb, (unsigned)nchunk, (unsigned)R), dim3(256), 0, st, Y, A, B, Ft,
-                       ldf, a_per, slabs, ldp, R);
+                       ldf, pl.a_per, slabs, ldp, R);
     NNF_CHECK_LAUNCH();
     return nnf_launch_reduce_slabs(slabs, (int)nchunk, (int64_t)R * ldp, R, B, ldp, out, ldo, st);
 }

@@ -165,7 +165,7 @@ static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int
     float* snum = (float*)cur.take((size_t)nsplit * slab_elems * 4);
     float* sden = nacc == 2 ? (float*)cur.take((size_t)nsplit * slab_elems * 4) : nullptr;
     if (!dvec || (pl.pieces > 1 && !part) || !snum || (nacc == 2 && !sden)) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan took the same)
-    const int a_vec_ok = ((((uintptr_t)Ut) & 15) == 0 && (ldu & 3) == 0) ? 1 : 0;
+    const int a_vec_ok = x_vec_ok(Ut, ldu) ? 1 : 0;
     const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, BM == BM_GEN));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_mu_right_kernel<MT, REM, BM, VEC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
@@ -205,7 +205,7 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
     double* part = pl.pieces > 1 ? (double*)cur.take((size_t)r * pl.pieces * 8) : nullptr;
     if (with_cost) ex.partial = (double*)cur.take((size_t)pl.grid * 8);
     if (!dvec || (pl.pieces > 1 && !part) || (with_cost && (!ex.partial || !cost_out))) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan took the same)
-    const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
+    const int a_vec_ok = x_vec_ok(V, ldv) ? 1 : 0;
     const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, BM == BM_GEN));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_mu_left_kernel<MT, REM, BM, VEC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);

@@ -235,7 +235,7 @@ extern "C" int nnf_mu_mode_f32(nnf_ctx* ctx, const float* T, int64_t L, int64_t 
     if (ldf < I || ldv < L * K || ldo < I) return NNF_ERR_ARG;
     if (r > MU_MODE_MAX_RANK) return NNF_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = ((((uintptr_t)T) | ((uintptr_t)V)) & 15) == 0 && (K & 3) == 0 && (ldv & 3) == 0;
+    const bool vec = x_vec_ok(T, K) && x_vec_ok(V, ldv);
     const bool kl = beta == 1.0;
     if (kl) return vec ? mu_mode_by_rank<true, true>(r, ctx, T, L, I, K, Ft, ldf, V, ldv, r, beta, out, ldo, st)
                        : mu_mode_by_rank<true, false>(r, ctx, T, L, I, K, Ft, ldf, V, ldv, r, beta, out, ldo, st);

@@ -296,7 +296,7 @@ static int launch_xty(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
     const int64_t ldp = nnf_rup(n, 4), slab_elems = (int64_t)r * ldp;
     float* slabs = (float*)cur.take((size_t)nsplit * slab_elems * 4);
     if (!slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
-    const int a_vec_ok = ((((uintptr_t)Ut) & 15) == 0 && (ldu & 3) == 0) ? 1 : 0;
+    const int a_vec_ok = x_vec_ok(Ut, ldu) ? 1 : 0;
     nnf_probe(ctx, NNF_PROBE_XTY, 0, st);   // measurement hook: the main kernel alone (bench.py)
     hipLaunchKernelGGL((nnf_xty_kernel<MT, REM, VEC>), dim3(nnf_split_grid(nsplit, ncb)), dim3(256), 0, st, X, m, n, ldx, Ut, ldu, r,
                        slabs, ldp, ncb, nsplit, pl.rows_per_split, a_vec_ok);
@@ -480,7 +480,7 @@ static int launch_xht(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
     if (nnf_plan_debug()) nnf_report_xht(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, false, pl);
     float* tail_slabs = pl.tail_parts > 0 ? (float*)cur.take((size_t)pl.tail_parts * r * pl.tail_ld * 4) : nullptr;
     if (pl.tail_parts > 0 && !tail_slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
-    const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
+    const int a_vec_ok = x_vec_ok(V, ldv) ? 1 : 0;
     nnf_probe(ctx, NNF_PROBE_XHT, 0, st);
 #define NNF_XHT_GO(NTH)                                                                                                          \
     hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, NTH>), dim3((int)pl.grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo, \
@@ -668,57 +668,30 @@ static int launch_gram_widen(const float* G, int64_t ldg, int r, double* G64, hi
     return NNF_OK;
 }
 
+// plan (nnf_plan_gram, k_stream_plan.h; a refusal launches nothing), report, carve, launch, reduce
 template <int MT>
 static int launch_gram(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* A, int r, int64_t K, int64_t lda, float* G, int64_t ldg,
                        hipStream_t st, double* G64) {
+    const int a_vec_ok = x_vec_ok(A, lda) ? 1 : 0;
+    const nnf_gram_plan pl = nnf_plan_gram(ctx->num_cus, r, K, ldg == r, a_vec_ok, cur.remaining());
+    if (pl.status != NNF_OK) return pl.status;
+    if (nnf_plan_debug()) nnf_report_gram(stderr, r, K, pl);
     if constexpr (MT <= 4) {
-        if (K <= 1024 && (K & 3) == 0 && ldg == r && ((((uintptr_t)A) & 15) == 0) && (lda & 3) == 0) {
-            if (nnf_plan_debug())
-                fprintf(stderr, "[nnf plan] gram r=%d K=%lld form=small nsplit=1 kps=%lld bound=none\n", r, (long long)K, (long long)K);
+        if (pl.form == NNF_GRAM_SMALL) {
             const int rc = launch_gram_small<MT>(A, r, K, lda, G, st);
             return rc != NNF_OK ? rc : launch_gram_widen(G, ldg, r, G64, st);
         }
     }
-    // one split per CU (the slab reduction spreads every output element over up to 16 threads, so its cost grows slowly
-    // with the split count): 64 splits left a 50 x 100000 Gram at 22 us and a 100 x 125000 one at 127 us
-    // (a workgroup walks its split in 64-wide LDS-staged chunks, one memory round trip each: with one split per CU the Gram of a
-    // 50 x 100000 factor was 7 dependent round trips = 15.7 us in front of W^T X; two resident workgroups per CU halve the
-    // chain and overlap each other's waits)
-    int64_t nsplit = ctx->num_cus > 8 ? 2 * (int64_t)ctx->num_cus : 8;
-    const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
-    const int64_t max_split = nnf_cdiv(K, 64);
-    if (nsplit > max_split) { nsplit = max_split; bound = "min_cols"; }
-    if (nsplit < 1) nsplit = 1;
-    // short factors (the I_mode x R factors of NTF / NTD, K <= 1024): one workgroup, no split, written straight into G -- the
-    // whole Gram is a few microseconds of work and the slab reduction would be a second launch of the same length
-    if (K <= 1024 && ldg == r) { nsplit = 1; bound = "short"; }
-    // keep the fp32 chain inside a split short (<= 512 columns; r*r*4 bytes of slab each): what the chains leave is all the error
-    // the fp64 copy of the sums has (nnf_gram_f64_f32).  The same plan with and without the copy: the fp32 Gram does not depend
-    // on which entry point formed it.
-    // (a workspace without room for one slab is refused, as in launch_gram_blocks, rather than run as one chain over all of K)
-    if (nsplit > 1 && nsplit < nnf_cdiv(K, 512)) {
-        nsplit = nnf_cdiv(K, 512);
-        bound = "chain512";
-        const int64_t ws_max = (int64_t)(cur.remaining() / 4) / ((int64_t)r * r);
-        if (ws_max < 1) return NNF_ERR_WORKSPACE;
-        if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
-    }
-    const int64_t kps = nnf_rup(nnf_cdiv(K, nsplit), 64);
-    nsplit = nnf_cdiv(K, kps);
-    const int a_vec_ok = ((((uintptr_t)A) & 15) == 0 && (lda & 3) == 0) ? 1 : 0;
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] gram r=%d K=%lld form=%s nsplit=%lld kps=%lld bound=%s\n", r, (long long)K,
-                nsplit == 1 && ldg == r ? "single" : "slabs", (long long)nsplit, (long long)kps, bound);
-    if (nsplit == 1 && ldg == r) {
-        hipLaunchKernelGGL((nnf_gram_kernel<MT>), dim3(1), dim3(256), 0, st, A, r, K, lda, G, kps, a_vec_ok);
+    if (pl.form == NNF_GRAM_SINGLE) {
+        hipLaunchKernelGGL((nnf_gram_kernel<MT>), dim3(1), dim3(256), 0, st, A, r, K, lda, G, pl.kps, a_vec_ok);
         NNF_CHECK_LAUNCH();
         return launch_gram_widen(G, ldg, r, G64, st);
     }
-    float* slabs = (float*)cur.take((size_t)nsplit * r * r * 4);
-    if (!slabs) return NNF_ERR_WORKSPACE;
-    hipLaunchKernelGGL((nnf_gram_kernel<MT>), dim3((int)nsplit), dim3(256), 0, st, A, r, K, lda, slabs, kps, a_vec_ok);
+    float* slabs = (float*)cur.take((size_t)pl.nsplit * r * r * 4);
+    if (!slabs) return NNF_ERR_WORKSPACE;   // (the plan caps the slabs to the workspace only where it raised their number)
+    hipLaunchKernelGGL((nnf_gram_kernel<MT>), dim3((int)pl.nsplit), dim3(256), 0, st, A, r, K, lda, slabs, pl.kps, a_vec_ok);
     NNF_CHECK_LAUNCH();
-    return nnf_launch_reduce_slabs(slabs, (int)nsplit, (int64_t)r * r, r, r, r, G, ldg, st, G64);
+    return nnf_launch_reduce_slabs(slabs, (int)pl.nsplit, (int64_t)r * r, r, r, r, G, ldg, st, G64);
 }
 
 // Ranks above NNF_MAX_RANK: the Gram in 64 x 64 blocks.  Workgroup (split ks, block pair (bi, bj)) multiplies the k range of
@@ -779,28 +752,15 @@ __global__ __launch_bounds__(256) void nnf_gram_blocks_kernel(const float* __res
 
 static int launch_gram_blocks(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* A, int r, int64_t K, int64_t lda, float* G, int64_t ldg,
                               hipStream_t st, double* G64) {
-    const int nb = (r + 63) / 64;
-    // splits: about two workgroups per CU over all block pairs, 64-column chunks, as many slabs as the workspace holds
-    int64_t nsplit = nnf_cdiv((int64_t)2 * ctx->num_cus, (int64_t)nb * nb);
-    const char* bound = "occupancy";   // which bound set the split count (NNF_PLAN_DEBUG)
-    const int64_t max_split = nnf_cdiv(K, 64);
-    if (nsplit > max_split) { nsplit = max_split; bound = "min_cols"; }
-    const int64_t ws_max = (int64_t)(cur.remaining() / 4) / ((int64_t)r * r);
-    if (ws_max < 1) return NNF_ERR_WORKSPACE;
-    if (nsplit < nnf_cdiv(K, 512)) { nsplit = nnf_cdiv(K, 512); bound = "chain512"; }   // (short fp32 chains, as in launch_gram)
-    if (nsplit > ws_max) { nsplit = ws_max; bound = "workspace"; }
-    if (nsplit < 1) nsplit = 1;
-    const int64_t kps = nnf_rup(nnf_cdiv(K, nsplit), 64);
-    nsplit = nnf_cdiv(K, kps);
-    const int a_vec_ok = ((((uintptr_t)A) & 15) == 0 && (lda & 3) == 0) ? 1 : 0;
-    if (nnf_plan_debug())
-        fprintf(stderr, "[nnf plan] gram r=%d K=%lld form=blocks nsplit=%lld kps=%lld bound=%s\n", r, (long long)K, (long long)nsplit,
-                (long long)kps, bound);
-    float* slabs = (float*)cur.take((size_t)nsplit * r * r * 4);
-    if (!slabs) return NNF_ERR_WORKSPACE;
-    hipLaunchKernelGGL(nnf_gram_blocks_kernel, dim3((int)nsplit, nb * nb), dim3(256), 0, st, A, r, K, lda, slabs, kps, a_vec_ok, nb);
+    const int nb = (r + 63) / 64, a_vec_ok = x_vec_ok(A, lda) ? 1 : 0;
+    const nnf_gram_plan pl = nnf_plan_gram(ctx->num_cus, r, K, ldg == r, a_vec_ok, cur.remaining());
+    if (pl.status != NNF_OK) return pl.status;
+    if (nnf_plan_debug()) nnf_report_gram(stderr, r, K, pl);
+    float* slabs = (float*)cur.take((size_t)pl.nsplit * r * r * 4);
+    if (!slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
+    hipLaunchKernelGGL(nnf_gram_blocks_kernel, dim3((int)pl.nsplit, nb * nb), dim3(256), 0, st, A, r, K, lda, slabs, pl.kps, a_vec_ok, nb);
     NNF_CHECK_LAUNCH();
-    return nnf_launch_reduce_slabs(slabs, (int)nsplit, (int64_t)r * r, r, r, r, G, ldg, st, G64);
+    return nnf_launch_reduce_slabs(slabs, (int)pl.nsplit, (int64_t)r * r, r, r, r, G, ldg, st, G64);
 }
 
 // =========================================================================================================
@@ -1288,47 +1248,32 @@ static int launch_cost(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64
                        const float* Vb = nullptr, int64_t ldvb = 0, int64_t nb = 1, const float* Ub = nullptr,
                        int64_t ldub = 0, int64_t nbu = 1, float* R1 = nullptr, float* R2 = nullptr, int64_t ldr = 0,
                        const float* Pin = nullptr, size_t ws_cap = 0) {
-    const int grid = (int)nnf_cdiv(m, 128);
-    // column splits: aim at ~8 workgroups per resident slot, keep at least 4 column blocks per workgroup
-    const int nblk_all = (int)nnf_cdiv(n, 64);
-    int csplit = (int)nnf_cdiv((int64_t)8 * 2 * ctx->num_cus, grid);
-    if (csplit > nblk_all / 4) csplit = nblk_all / 4;
-    // every column split stages the workgroup's 128 x r tile of U again: keep that re-read below ~5 % of the pass over X
-    // (config B: 6 splits moved 1.02 GB for 0.82 GB algorithmic, PMC; the launch time is flat over 2..8 splits, so the
-    // splits buy nothing there) -- as long as the grid still fills the resident slots twice over
-    {
-        int cap = (int)((0.05 * (double)n) / (double)(r > 0 ? r : 1));
-        if (cap < 1) cap = 1;
-        const int need = (int)nnf_cdiv((int64_t)2 * 3 * ctx->num_cus, grid);   // two rounds of 3 workgroups per CU
-        if (cap < need) cap = need;
-        if (Ub == nullptr && csplit > cap) csplit = cap;
-    }
-    {   // tuning knob (tools/cost_probe.py): NNF_COST_CSPLIT overrides the number of column splits
-        static const int forced = [] { const char* e = getenv("NNF_COST_CSPLIT"); return e ? atoi(e) : 0; }();
-        if (forced > 0) csplit = forced < nblk_all ? forced : nblk_all;
-    }
-    if (csplit < 1) csplit = 1;
+    // plan (nnf_plan_cost, k_stream_plan.h; a refusal launches nothing), report, carve, launch, sum
+    if (Pin != nullptr && ldr < n) return NNF_ERR_ARG;
+    // tuning knob (tools/cost_probe.py): NNF_COST_CSPLIT overrides the number of column splits
+    static const int forced = [] { const char* e = getenv("NNF_COST_CSPLIT"); return e ? atoi(e) : 0; }();
     nnf_ws_cursor cur(ctx);
     if (ws_cap) cur.cap = ws_cap;          // (the tail of the workspace holds the model of the earlier rank chunks)
-    double* partial = (double*)cur.take((size_t)grid * csplit * 8);
-    if (!partial) return NNF_ERR_WORKSPACE;
-    const int KS = (r + 3) / 4;
-    const int64_t vf_total = (int64_t)nblk_all * KS * 64;
-    f32x4* Vf = (f32x4*)cur.take((size_t)vf_total * 16);
-    if (!Vf) return NNF_ERR_WORKSPACE;
+    const nnf_cost_plan pl = nnf_plan_cost(ctx->num_cus, m, n, r, Ub != nullptr, forced, Pin != nullptr, OP == NNF_PROD, cur.remaining());
+    if (pl.status != NNF_OK) return pl.status;
+    // (a later rank chunk of a rank above 128, launch_cost_any_rank, reads the model next to X: one load width for both)
+    const bool vec = x_vec_ok(X, ldx) && (Pin == nullptr || x_vec_ok(Pin, ldr));
+    if (nnf_plan_debug()) {
+        static const char* const ops[] = {"frob", "kl", "is", "gen", "ratio_kl", "ratio_gen", "prod"};
+        nnf_report_cost(stderr, m, n, r, ops[OP], vec, Pin != nullptr, Ub ? nbu : 0, pl);
+    }
+    const int grid = pl.grid, csplit = pl.csplit, KS = pl.KS, vdb = pl.vdb, u_vec_ok = x_vec_ok(Ut, ldu) ? 1 : 0;
+    const size_t shm = pl.shm;
+    double* partial = (double*)cur.take(pl.partial_bytes);
+    f32x4* Vf = (f32x4*)cur.take(pl.vf_bytes);
+    if (!partial || !Vf) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
     {
+        const int64_t vf_total = (int64_t)(pl.vf_bytes / 16);
         int64_t pg = nnf_cdiv(vf_total, 256);
         if (pg > 1024) pg = 1024;
         hipLaunchKernelGGL(nnf_cost_prepv_kernel, dim3((int)pg), dim3(256), 0, st, V, ldv, r, n, KS, Vb, ldvb, nb, Vf, vf_total);
         NNF_CHECK_LAUNCH();
     }
-    const int u_vec_ok = ((((uintptr_t)Ut) & 15) == 0 && (ldu & 3) == 0) ? 1 : 0;
-    // two V buffers unless dropping one lets another workgroup onto the CU (ranks 53..64: a third, 77..104: a second; see the kernel)
-    const size_t shm2 = (size_t)4 * 2 * KS * 64 * 4 + (size_t)2 * KS * 64 * 16 + 64, shm1 = shm2 - (size_t)KS * 64 * 16;
-    const size_t lds_cu = 160 * 1024;
-    auto wg_per_cu = [&](size_t b) { const size_t w = lds_cu / b; return w > 3 ? (size_t)3 : w; };   // (launch bound: 3)
-    const int vdb = wg_per_cu(shm1) > wg_per_cu(shm2) ? 0 : 1;
-    const size_t shm = vdb ? shm2 : shm1;
 #define NNF_COST_LAUNCH(VV, NN, PP)                                                                                          \
     do {                                                                                                                     \
         if (shm > 48 * 1024)                                                                                                 \
@@ -1337,26 +1282,18 @@ static int launch_cost(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64
         hipLaunchKernelGGL((nnf_cost_kernel<OP, VV, NN, PP>), dim3(grid, csplit), dim3(256), shm, st, X, m, n, ldx, Ut, ldu, Vf, r, \
                            beta, partial, Ub, ldub, nbu, R1, R2, ldr, u_vec_ok, vdb, Pin);                                   \
     } while (0)
-    if (nnf_plan_debug()) {
-        static const char* const ops[] = {"frob", "kl", "is", "gen", "ratio_kl", "ratio_gen", "prod"};
-        const bool vv = Pin != nullptr ? x_vec_ok(X, ldx) && ldr >= n && x_vec_ok(Pin, ldr) : x_vec_ok(X, ldx);
-        const int nn = (Pin != nullptr || OP == NNF_PROD || KS > 16) ? 8 : 4;
-        fprintf(stderr, "[nnf plan] cost m=%lld n=%lld r=%d op=%s grid=%d csplit=%d NN=%d vdb=%d VEC=%d pin=%d kr=%lld\n", (long long)m,
-                (long long)n, r, ops[OP], grid, csplit, nn, vdb, (int)vv, (int)(Pin != nullptr), (long long)(Ub ? nbu : 0));
-    }
     nnf_probe(ctx, NNF_PROBE_COST, 0, st);
-    if (Pin != nullptr) {           // a later rank chunk of a rank above 128 (launch_cost_chunked): one instance per load width
-        if (ldr < n) return NNF_ERR_ARG;
-        if (x_vec_ok(X, ldx) && x_vec_ok(Pin, ldr)) NNF_COST_LAUNCH(true, 8, true);
+    if (Pin != nullptr) {           // one instance per load width
+        if (vec) NNF_COST_LAUNCH(true, 8, true);
         else NNF_COST_LAUNCH(false, 8, true);
     } else if (OP == NNF_PROD) {
-        if (x_vec_ok(X, ldx)) NNF_COST_LAUNCH(true, 8, false);
+        if (vec) NNF_COST_LAUNCH(true, 8, false);
         else NNF_COST_LAUNCH(false, 8, false);
-    } else if (x_vec_ok(X, ldx)) {
-        if (KS <= 16) NNF_COST_LAUNCH(true, 4, false);
+    } else if (vec) {
+        if (pl.NN == 4) NNF_COST_LAUNCH(true, 4, false);
         else NNF_COST_LAUNCH(true, 8, false);
     } else {
-        if (KS <= 16) NNF_COST_LAUNCH(false, 4, false);
+        if (pl.NN == 4) NNF_COST_LAUNCH(false, 4, false);
         else NNF_COST_LAUNCH(false, 8, false);
     }
 #undef NNF_COST_LAUNCH
@@ -1371,8 +1308,7 @@ static int launch_cost(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64
 static int cost_args_ok(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
                         const float* V, int64_t ldv, int r, double* out) {
     if (!ctx || !X || !Ut || !V || !out || m < 1 || n < 1 || r < 1 || ldx < n || ldu < m || ldv < n) return NNF_ERR_ARG;
-    if (32 * ldx * 4 + 4 * (n + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;
-    return NNF_OK;
+    return nnf_cost_offsets_ok(ldx, n) ? NNF_OK : NNF_ERR_UNSUPPORTED;
 }
 
 // The cost / ratio pass at any rank.  Up to NNF_MAX_RANK: one launch.  Above: the model U V is built up over rank chunks of
@@ -1400,7 +1336,7 @@ static int launch_cost_any_rank(nnf_ctx* ctx, const float* X, int64_t m, int64_t
             P = (float*)(ctx->ws + cap);
         }
     }
-    if (ldp * 4 * 32 + 4 * (n + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;
+    if (!nnf_cost_offsets_ok(ldp, n)) return NNF_ERR_UNSUPPORTED;
     for (int k0 = 0; k0 < r; k0 += NNF_MAX_RANK) {
         const int rc = r - k0 < NNF_MAX_RANK ? r - k0 : NNF_MAX_RANK;
         const float* Uc = Ut + (int64_t)k0 * ldu;
@@ -1467,7 +1403,7 @@ extern "C" int nnf_cp3_betadiv_f32(nnf_ctx* ctx, const float* T, int64_t I, int6
     // the right operand is F2^T as is.  I*J rows give the kernel its parallelism (one workgroup per 128 rows).
     // (ranks above 128: the model is built up over rank chunks in a tensor-sized buffer, launch_cost_any_rank)
     const int64_t m = I * J;
-    if (32 * K * 4 + 4 * (K + 128) >= (int64_t)0x7fff0000) return NNF_ERR_UNSUPPORTED;
+    if (!nnf_cost_offsets_ok(K, K)) return NNF_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
 #define CP3(OP, B, SC) launch_cost_any_rank<OP>(ctx, T, m, K, K, Ft0, ld0, Ft2, ld2, R, B, SC, out_f64, st, nullptr, nullptr, 0, Ft1, ld1, J)
     if (beta == 2.0) return CP3(NNF_COST_FROB, 2.f, 0.5);

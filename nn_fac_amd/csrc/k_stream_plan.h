@@ -1,6 +1,7 @@
-// Launch plans of the streaming and MTTKRP launchers (k_stream.hip, k_xht_lds.hip, k_mttkrp.hip; k_mu_plan.h builds on them):
+// Launch plans of the streaming and MTTKRP launchers (k_stream.hip: W^T X, X H^T, the Gram, the cost pass; k_xht_lds.hip;
+// k_mttkrp.hip: the segment and rows kernels, the two dimension-tree contractions; k_mu_plan.h builds on them):
 // what a call will launch, decided from sizes alone before anything is carved from the workspace or launched, and the
-// NNF_PLAN_DEBUG line that reports it.  No HIP in here: tools/nnf_plan.cpp is a plain host program that prints the same plans
+// NNF_PLAN_DEBUG line that reports it (every "[nnf plan]" line of the library is formatted in these two headers).  No HIP in here: tools/nnf_plan.cpp is a plain host program that prints the same plans
 // for any CU count (tests/test_mu_plan_table.py).
 #pragma once
 #include <stddef.h>
@@ -220,4 +221,183 @@ inline bool nnf_xht_lds_narrow(int64_t ldx, int pin) {
 // the tail
 inline nnf_xht_plan nnf_plan_xht_lds(int cus, int64_t m, int64_t n, int r, nnf_rank_tiles t, int64_t ldx, int pin) {
     return nnf_plan_xht(m, n, r, (int64_t)2 * cus, t.MT + (t.REM > 0), 0, 0, 0, nnf_xht_lds_narrow(ldx, pin));
+}
+
+// ---- MTTKRP modes 0 and 1: the segments of a row cut into splits (launch_seg) ----
+struct nnf_seg_plan {
+    int status;                // NNF_OK, or the refusal
+    int64_t nsplit, sps;       // splits, segments per split
+    const char* bound;
+    int64_t ws_max;            // slabs the free workspace holds
+};
+// nrows rows of nseg segments of klen entries (row pitch ldrow), the segment-side factor at pitch fs_ld: a wave's 64 rows and the
+// padded rank rows of that factor inside 31-bit offsets; two workgroups per CU shared among the 256-row blocks, at least one
+// split, at most one per segment and what free_bytes hold of slabs (r x rup(nrows, 4) floats), then segments per split re-rounded
+inline nnf_seg_plan nnf_plan_seg(int cus, int64_t nrows, int64_t ldrow, int64_t nseg, int64_t klen, int r, int64_t fs_ld,
+                                 size_t free_bytes) {
+    nnf_seg_plan p{NNF_OK, 2 * (int64_t)cus / nnf_cdiv(nrows, 256), 0, "occupancy", 0};
+    if ((64 * ldrow + klen + 256) * 4 >= NNF_OFFSET32_END || (int64_t)(16 * ((r + 15) / 16)) * fs_ld * 4 >= NNF_OFFSET32_END) {
+        p.status = NNF_ERR_UNSUPPORTED;
+        return p;
+    }
+    if (p.nsplit < 1) { p.nsplit = 1; p.bound = "one"; }
+    if (p.nsplit > nseg) { p.nsplit = nseg; p.bound = "segments"; }
+    p.ws_max = (int64_t)(free_bytes / 4) / ((int64_t)r * nnf_rup(nrows, 4));
+    if (p.ws_max < 1) { p.status = NNF_ERR_WORKSPACE; return p; }
+    if (p.nsplit > p.ws_max) { p.nsplit = p.ws_max; p.bound = "workspace"; }
+    p.sps = nnf_cdiv(nseg, p.nsplit);
+    p.nsplit = nnf_cdiv(nseg, p.sps);
+    return p;
+}
+// vec / fkvec: 16-byte loads of the tensor / of the inner factor; pp: the two-register-set pipeline (up to two rank tiles)
+inline void nnf_report_seg(FILE* f, int64_t nrows, int64_t nseg, int64_t klen, int r, int MT, bool vec, bool fkvec, bool pp,
+                           const nnf_seg_plan& p, const char* more = "") {
+    fprintf(f, "[nnf plan] mttkrp_seg nrows=%lld nseg=%lld klen=%lld r=%d mt=%d VEC=%d fkvec=%d pp=%d nsplit=%lld sps=%lld bound=%s%s\n",
+            (long long)nrows, (long long)nseg, (long long)klen, r, MT, (int)vec, (int)fkvec, (int)pp, (long long)p.nsplit,
+            (long long)p.sps, p.bound, more);
+}
+
+// ---- MTTKRP from a partial product Y (r x A x B): nnf_mttkrp3_from_partial_f32 ----
+// axis 2: one wave per (r, a) row, four to a workgroup, at most 8192 workgroups (beyond that the waves stride the rows)
+struct nnf_partial_last_plan { int64_t grid; bool strided; };
+inline nnf_partial_last_plan nnf_plan_partial_last(int64_t A, int r) {
+    const int64_t rows = (int64_t)r * A, grid = nnf_cdiv(rows, 4) < 8192 ? nnf_cdiv(rows, 4) : 8192;
+    return {grid, rows > 4 * grid};
+}
+inline void nnf_report_partial_last(FILE* f, int64_t A, int64_t B, int r, const nnf_partial_last_plan& p, const char* more = "") {
+    fprintf(f, "[nnf plan] partial_last A=%lld B=%lld r=%d grid=%lld strided=%d%s\n", (long long)A, (long long)B, r,
+            (long long)p.grid, (int)p.strided, more);
+}
+// axis 1: enough a-chunks to fill the chip (four workgroups per CU over column blocks x ranks), at least 16 rows each; one slab
+// (r x rup(B, 4) floats) per chunk
+struct nnf_partial_mid_plan {
+    int status;
+    int64_t nchunk, a_per;
+    const char* bound;
+};
+inline nnf_partial_mid_plan nnf_plan_partial_mid(int cus, int64_t A, int64_t B, int r, size_t free_bytes) {
+    const int64_t cb = nnf_cdiv(B, 256);
+    nnf_partial_mid_plan p{NNF_OK, nnf_cdiv((int64_t)4 * cus, cb * r), 0, "occupancy"};
+    if (p.nchunk < 1) p.nchunk = 1;
+    if (p.nchunk > nnf_cdiv(A, 16)) { p.nchunk = nnf_cdiv(A, 16); p.bound = "rows16"; }
+    if (p.nchunk > 65535) { p.nchunk = 65535; p.bound = "grid"; }
+    p.a_per = nnf_cdiv(A, p.nchunk);
+    p.nchunk = nnf_cdiv(A, p.a_per);
+    if ((size_t)p.nchunk * r * nnf_rup(B, 4) * 4 > free_bytes) p.status = NNF_ERR_WORKSPACE;
+    else if (cb > 65535) p.status = NNF_ERR_UNSUPPORTED;   // (grid.x)
+    return p;
+}
+inline void nnf_report_partial_mid(FILE* f, int64_t A, int64_t B, int r, const nnf_partial_mid_plan& p, const char* more = "") {
+    fprintf(f, "[nnf plan] partial_mid A=%lld B=%lld r=%d nchunk=%lld a_per=%lld bound=%s%s\n", (long long)A, (long long)B, r,
+            (long long)p.nchunk, (long long)p.a_per, p.bound, more);
+}
+
+// ---- the Gram A A^T of an r x K factor (launch_gram, launch_gram_blocks) ----
+enum nnf_gram_form { NNF_GRAM_SMALL, NNF_GRAM_SINGLE, NNF_GRAM_SLABS, NNF_GRAM_BLOCKS };
+struct nnf_gram_plan {
+    int status;
+    nnf_gram_form form;
+    int64_t nsplit, kps;       // splits of K (one slab of r x r floats each, but for small and single), columns per split
+    const char* bound;
+    int64_t ws_max;            // slabs the free workspace holds
+};
+// small: one 512-thread workgroup, straight into G (at most four rank tiles, K <= 1024 in whole float4s, a contiguous G and
+// 16-byte loads of A: vec).  Otherwise splits of K.  Up to NNF_MAX_RANK: one split per two resident workgroups per CU (the slab
+// reduction spreads every output element over up to 16 threads, so its cost grows slowly with the split count: 64 splits left a
+// 50 x 100000 Gram at 22 us and a 100 x 125000 one at 127 us; a workgroup walks its split in 64-wide LDS-staged chunks, one
+// memory round trip each: with one split per CU the Gram of a 50 x 100000 factor was 7 dependent round trips = 15.7 us in front
+// of W^T X; two resident workgroups per CU halve the chain and overlap each other's waits); short factors (the I_mode x R factors
+// of NTF / NTD, K <= 1024) with a contiguous G: one workgroup, no split, written straight into G -- the whole Gram is a few
+// microseconds of work and the slab reduction would be a second launch of the same length (single).  The fp32 chain inside a
+// split stays short (<= 512 columns): what the chains leave is all the error the fp64 copy of the sums has (nnf_gram_f64_f32);
+// the same plan with and without the copy.  A workspace without room for one slab is refused there rather than run as one chain
+// over all of K.  (Only there: with fewer splits asked for than the workspace holds nothing is capped, and the launcher's carve
+// is what refuses.)  Ranks above NNF_MAX_RANK (blocks: 64 x 64 blocks of G, a workgroup per split and block pair): about two
+// workgroups per CU over all block pairs, 64-column chunks, chains of 512, as many slabs as the workspace holds.
+inline nnf_gram_plan nnf_plan_gram(int cus, int r, int64_t K, bool ldg_is_r, bool vec, size_t free_bytes) {
+    const int64_t max_split = nnf_cdiv(K, 64), chain = nnf_cdiv(K, 512);
+    nnf_gram_plan p{NNF_OK, NNF_GRAM_SMALL, 1, K, "none", (int64_t)(free_bytes / 4) / ((int64_t)r * r)};
+    if (r > NNF_MAX_RANK) {
+        const int64_t nb = (r + 63) / 64;
+        p.form = NNF_GRAM_BLOCKS;
+        p.nsplit = nnf_cdiv((int64_t)2 * cus, nb * nb);
+        p.bound = "occupancy";
+        if (p.nsplit > max_split) { p.nsplit = max_split; p.bound = "min_cols"; }
+        if (p.ws_max < 1) { p.status = NNF_ERR_WORKSPACE; return p; }
+        if (p.nsplit < chain) { p.nsplit = chain; p.bound = "chain512"; }
+        if (p.nsplit > p.ws_max) { p.nsplit = p.ws_max; p.bound = "workspace"; }
+        if (p.nsplit < 1) p.nsplit = 1;
+    } else {
+        if ((r + 15) / 16 <= 4 && K <= 1024 && (K & 3) == 0 && ldg_is_r && vec) return p;
+        p.nsplit = cus > 8 ? 2 * (int64_t)cus : 8;
+        p.bound = "occupancy";
+        if (p.nsplit > max_split) { p.nsplit = max_split; p.bound = "min_cols"; }
+        if (p.nsplit < 1) p.nsplit = 1;
+        if (K <= 1024 && ldg_is_r) { p.nsplit = 1; p.bound = "short"; }
+        if (p.nsplit > 1 && p.nsplit < chain) {
+            p.nsplit = chain;
+            p.bound = "chain512";
+            if (p.ws_max < 1) { p.status = NNF_ERR_WORKSPACE; return p; }
+            if (p.nsplit > p.ws_max) { p.nsplit = p.ws_max; p.bound = "workspace"; }
+        }
+    }
+    p.kps = nnf_rup(nnf_cdiv(K, p.nsplit), 64);
+    p.nsplit = nnf_cdiv(K, p.kps);
+    if (p.form != NNF_GRAM_BLOCKS) p.form = p.nsplit == 1 && ldg_is_r ? NNF_GRAM_SINGLE : NNF_GRAM_SLABS;
+    return p;
+}
+inline void nnf_report_gram(FILE* f, int r, int64_t K, const nnf_gram_plan& p, const char* more = "") {
+    static const char* const forms[] = {"small", "single", "slabs", "blocks"};
+    fprintf(f, "[nnf plan] gram r=%d K=%lld form=%s nsplit=%lld kps=%lld bound=%s%s\n", r, (long long)K, forms[p.form],
+            (long long)p.nsplit, (long long)p.kps, p.bound, more);
+}
+
+// ---- the cost / ratio pass (launch_cost): 128-row workgroups x column splits ----
+// 32 rows of X (or of the model buffer of a rank above 128) at pitch ld and a factor chunk inside 32-bit offsets
+constexpr bool nnf_cost_offsets_ok(int64_t ld, int64_t n) { return 32 * ld * 4 + 4 * (n + 128) < NNF_OFFSET32_END; }
+struct nnf_cost_plan {
+    int status;
+    int grid, csplit;          // row tiles, column splits
+    int KS, NN, vdb;           // k-steps of 4 rank rows, rank rows per load group, two V buffers
+    size_t shm;                // dynamic LDS
+    size_t partial_bytes, vf_bytes;   // the two carves: a double per workgroup, the staged right operand
+};
+// kr: Khatri-Rao rows on the left (the CP cost); forced: NNF_COST_CSPLIT (0: unset); pin: a later rank chunk of a rank above
+// 128, which reads the model so far; prod: the pass only writes the model (NNF_PROD)
+inline nnf_cost_plan nnf_plan_cost(int cus, int64_t m, int64_t n, int r, bool kr, int forced, bool pin, bool prod,
+                                   size_t free_bytes) {
+    nnf_cost_plan p{NNF_OK, (int)nnf_cdiv(m, 128), 0, (r + 3) / 4, 0, 0, 0, 0, 0};
+    // column splits: aim at ~8 workgroups per resident slot, keep at least 4 column blocks per workgroup
+    const int nblk_all = (int)nnf_cdiv(n, 64);
+    p.csplit = (int)nnf_cdiv((int64_t)8 * 2 * cus, p.grid);
+    if (p.csplit > nblk_all / 4) p.csplit = nblk_all / 4;
+    // every column split stages the workgroup's 128 x r tile of U again: keep that re-read below ~5 % of the pass over X
+    // (config B: 6 splits moved 1.02 GB for 0.82 GB algorithmic, PMC; the launch time is flat over 2..8 splits, so the
+    // splits buy nothing there) -- as long as the grid still fills the resident slots twice over
+    int cap = (int)((0.05 * (double)n) / (double)(r > 0 ? r : 1));
+    if (cap < 1) cap = 1;
+    const int need = (int)nnf_cdiv((int64_t)2 * 3 * cus, p.grid);   // two rounds of 3 workgroups per CU
+    if (cap < need) cap = need;
+    if (!kr && p.csplit > cap) p.csplit = cap;
+    if (forced > 0) p.csplit = forced < nblk_all ? forced : nblk_all;
+    if (p.csplit < 1) p.csplit = 1;
+    p.NN = (pin || prod || p.KS > 16) ? 8 : 4;
+    // two V buffers unless dropping one lets another workgroup onto the CU (ranks 53..64: a third, 77..104: a second; see the kernel)
+    const size_t shm2 = (size_t)4 * 2 * p.KS * 64 * 4 + (size_t)2 * p.KS * 64 * 16 + 64, shm1 = shm2 - (size_t)p.KS * 64 * 16;
+    const size_t lds_cu = 160 * 1024;
+    auto wg_per_cu = [&](size_t b) { const size_t w = lds_cu / b; return w > 3 ? (size_t)3 : w; };   // (launch bound: 3)
+    p.vdb = wg_per_cu(shm1) > wg_per_cu(shm2) ? 0 : 1;
+    p.shm = p.vdb ? shm2 : shm1;
+    p.partial_bytes = (size_t)p.grid * p.csplit * 8;
+    p.vf_bytes = (size_t)nblk_all * p.KS * 64 * 16;
+    nnf_ws_cursor cur(nullptr, free_bytes);
+    if (!cur.reserve(p.partial_bytes) || !cur.reserve(p.vf_bytes)) p.status = NNF_ERR_WORKSPACE;
+    return p;
+}
+// op: the pass (frob, kl, is, gen, ratio_kl, ratio_gen, prod); vec: 16-byte loads of X (and of the model buffer); kr: the
+// Khatri-Rao inner length (0: none)
+inline void nnf_report_cost(FILE* f, int64_t m, int64_t n, int r, const char* op, bool vec, bool pin, int64_t kr,
+                            const nnf_cost_plan& p, const char* more = "") {
+    fprintf(f, "[nnf plan] cost m=%lld n=%lld r=%d op=%s grid=%d csplit=%d NN=%d vdb=%d VEC=%d pin=%d kr=%lld%s\n", (long long)m,
+            (long long)n, r, op, p.grid, p.csplit, p.NN, p.vdb, (int)vec, (int)pin, (long long)kr, more);
 }

@@ -169,7 +169,7 @@ static int launch_xht_lds(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, in
     const nnf_xht_plan pl = nnf_plan_xht_lds(ctx->num_cus, m, n, r, nnf_rank_tiles{MT, REM}, ldx, pin);
     if (!pl.covers(m)) return NNF_ERR_UNSUPPORTED;   // (the split covers m by construction)
     if (nnf_plan_debug()) nnf_report_xht(stderr, m, n, r, nnf_rank_tiles{MT, REM}, true, true, pl);
-    const int a_vec_ok = ((((uintptr_t)V) & 15) == 0 && (ldv & 3) == 0) ? 1 : 0;
+    const int a_vec_ok = x_vec_ok(V, ldv) ? 1 : 0;
     nnf_probe(ctx, NNF_PROBE_XHT, 0, st);
 #define NNF_XHT_LDS_GO(NTH)                                                                                                           \
     hipLaunchKernelGGL((nnf_xht_lds_kernel<MT, REM, NTH>), dim3((int)pl.grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo, \

@@ -5,9 +5,10 @@ launch_seg (MTTKRP modes 0 and 1), launch_rows (mode 2), nnf_mttkrp3_from_partia
 Khatri-Rao rows (nnf_cp3_betadiv_f32) pick a plan from the shape, the rank, the alignment and strides of the operands, the CU
 count and the free workspace.  tensor_cases(C) names the plan every case must take, with its shape written from the CU count so
 that each case sits on the side of a threshold it says it does.  test_tensor_cases_reach_required checks the table against a
-Python restatement of the four plan formulas (no GPU; tests/test_mu_plan_table.py checks the mttkrp_rows rows, and that
-restatement of them, against the library's own plan arithmetic through tools/nnf_plan.cpp), test_tensor_plan_table against the library's own report
-(NNF_PLAN_DEBUG), test_tensor_values / test_cp3_cost check every case against a plain fp64 evaluation on the device.
+Python restatement of the four plan formulas (no GPU; tests/test_mu_plan_table.py checks every row, and the restatement of it,
+against the library's own plan arithmetic through tools/nnf_plan.cpp, without a GPU either), test_tensor_plan_table against the
+library's own report (NNF_PLAN_DEBUG), test_tensor_values / test_cp3_cost check every case against a plain fp64 evaluation on the
+device.
 
 Bounds, and where each comes from:
   * exact inputs (small integers of both signs, sum |T| |Fa| |Fb| < 2^24 for every output, asserted on the fp64 reference of

@@ -1,5 +1,6 @@
-"""The MU, X H^T and W^T X rows of test_gpu_launch_plans.plan_cases and the mttkrp_rows rows of test_gpu_tensor_plans.tensor_cases
-against the library's own plan arithmetic, at 256 and at 304 compute units.  No GPU: the launchers take their plans from HIP-free
+"""Every row of test_gpu_launch_plans.plan_cases (MU, X H^T, W^T X, Gram, cost; cp3_partial_cost is a left MU update at a fixed
+shape and has its plan checked on the device only) and every row of test_gpu_tensor_plans.tensor_cases (MTTKRP by segments and by
+rows, the two dimension-tree contractions, the CP cost) against the library's own plan arithmetic, at 256 and at 304 compute units.  No GPU: the launchers take their plans from HIP-free
 headers (nn_fac_amd/csrc/k_stream_plan.h, k_mu_plan.h), and tools/nnf_plan.cpp, a plain host program over the same headers,
 prints the plan of a case as the library reports it under NNF_PLAN_DEBUG.  This is what keeps the tables' shapes on the side of
 the thresholds they name on a machine that cannot ask the library (test_plan_table and test_tensor_plan_table do, on the device)."""
@@ -18,7 +19,8 @@ from test_gpu_launch_plans import REQUIRED, REQUIRED_BIG, ROOT, _cdiv, note_plan
 
 WS_DEFAULT = 1024 << 20         # get_engine's context
 CUS = (256, 304)
-LAUNCHER = {"mu_left": "mu_left", "mu_right": "mu_right", "mu_accum": "mu_right", "xht": "xht", "xty": "xty"}
+LAUNCHER = {"mu_left": "mu_left", "mu_right": "mu_right", "mu_accum": "mu_right", "xht": "xht", "xty": "xty", "gram": "gram",
+            "cost": "cost"}
 
 
 @functools.lru_cache(maxsize=None)
@@ -46,6 +48,8 @@ def ask(lines):
 
 
 def case_line(C, case):
+    if case.kernel == "gram":       # the factor is r x m, contiguous, and so is G
+        return "gram %d %d %d %d %d 0 %d" % (C, case.m, case.m, case.r, case.m, WS_DEFAULT if case.ws is None else case.ws)
     return "%s %d %d %d %d %d %r %d" % (LAUNCHER[case.kernel], C, case.m, case.n, case.r, case.ld or case.n, case.beta or 0.0,
                                         WS_DEFAULT if case.ws is None else case.ws)
 
@@ -190,3 +194,90 @@ def test_mttkrp_rows_cases_take_the_plans_they_name(C):
         if key[0] == "mttkrp_rows":
             assert want <= seen[key], (C, key, want - seen[key])
     assert tensor.ERR_WORKSPACE in refused
+
+
+def tensor_line(C, case):
+    """A mode-0 or mode-1 MTTKRP, dimension-tree or CP-cost case of tensor_cases as its launcher sees it: its first rank pass, for
+    the CP cost its last (the pass that reads the model of the earlier ones)."""
+    ld, al = case.ld or {}, case.align or {}
+    ws = WS_DEFAULT if case.ws is None else case.ws
+    if case.kernel == "partial":
+        A, B = case.shape
+        return "%s %d %d %d %d %d 0 %d" % (tensor.launcher_of(case), C, A, B, min(case.R, 128), B, ws)
+    I, J, K = case.shape
+    if case.kernel == "cp3":
+        return "cost %d %d %d %d %d %r %d kr=%d pin=%d align=%d" % (
+            C, I * J, K, case.R - 128 * ((case.R - 1) // 128), K, float(case.beta), ws, J, case.R > 128, al.get("T", 0))
+    # mode 0: rows i, segments j (stride K) against factors 1 and 2; mode 1: rows j, segments i (stride J K) against factors 0 and 2
+    nrows, ldrow, nseg, segstride, fsld = ((I, J * K, J, K, J + ld.get("f1", 0)) if case.mode == 0
+                                           else (J, K, I, J * K, I + ld.get("f0", 0)))
+    return "mttkrp_seg %d %d %d %d %d 0 %d nseg=%d segstride=%d fsld=%d fkld=%d fkalign=%d align=%d" % (
+        C, nrows, K, min(case.R, 128), ldrow, ws, nseg, segstride, fsld, K + ld.get("f2", 0), al.get("f2", 0), al.get("T", 0))
+
+
+@pytest.mark.parametrize("C", CUS)
+def test_tensor_cases_take_the_plans_they_name(C):
+    """Every field (or refusal) a mode-0 / mode-1 MTTKRP, dimension-tree or CP-cost case of test_gpu_tensor_plans lists is what the
+    library's plan gives, which is also what that file's own formulas give, field by field; these rows reach what its REQUIRED and
+    REQUIRED_REFUSALS name for their four launchers (the large cases need no memory here)."""
+    cases = {nm: c for nm, c in tensor.tensor_cases(C).items() if not (c.kernel == "mttkrp" and c.mode == 2)}
+    plans = dict(zip(cases, ask([tensor_line(C, c) for c in cases.values()])))
+    seen, refused, bad = collections.defaultdict(set), set(), []
+    for name, case in cases.items():
+        plan, launcher = plans[name], tensor.launcher_of(case)
+        formula = tensor.plan_of(C, case)
+        if {k: str(v) for k, v in formula.items()} != {k: str(plan.get(k)) for k in formula}:
+            bad.append((name, "formula", formula, plan))
+        if "status" in plan or "status" in case.expect:
+            if plan != case.expect:
+                bad.append((name, plan, case.expect))
+            refused.add((launcher, plan.get("status")))
+            continue
+        for key, want in case.expect.items():
+            if str(plan.get(key)) != str(want):
+                bad.append((name, key, plan.get(key), want))
+        tensor._note(seen, launcher, plan)
+        if plan.get("bound") == "workspace":
+            assert launcher == "mttkrp_seg" and plan["nsplit"] == _cdiv(plan["nseg"], _cdiv(plan["nseg"], plan["ws_max"])), (name, plan)
+    assert not bad, "\n".join(map(str, bad))
+    assert {tensor.launcher_of(c) for c in cases.values()} == {"mttkrp_seg", "partial_last", "partial_mid", "cost"}
+    for key, want in tensor.REQUIRED.items():
+        if key[0] != "mttkrp_rows":
+            assert want <= seen[key], (C, key, want - seen[key])
+    # (the refusal of the rows launcher: test_mttkrp_rows_cases_take_the_plans_they_name)
+    want = {(l, st) for (l, st) in tensor.REQUIRED_REFUSALS if l != "mttkrp_rows"}
+    assert len(want) == len(tensor.REQUIRED_REFUSALS) - 1 and want <= refused, want - refused
+    assert {nm for nm in cases if tensor._is_big(nm)} == {"big_seg0_offset_limit"} and "status" not in plans["big_seg0_offset_limit"]
+    assert plans["part1_grid_refused"] == {"status": tensor.ERR_UNSUPPORTED}       # enough workspace, too many column blocks
+
+
+@pytest.mark.parametrize("C", CUS)
+def test_gram_and_cost_cases_take_the_plans_they_name(C):
+    """Every field a Gram or cost case lists is what the library's plan gives; the rows reach what REQUIRED names for the two
+    launchers and column splits of one and of more; a Gram plan bound by the workspace has the splits that workspace holds, and no
+    plan carves more than there is."""
+    cases = {nm: c for nm, c in plan_cases(C).items() if c.kernel in ("gram", "cost")}
+    seen, bad = collections.defaultdict(set), []
+    for name, case in cases.items():
+        plan = plan_of(C, case)
+        assert "status" not in plan, (name, plan)
+        assert plan["K" if case.kernel == "gram" else "m"] == case.m and plan["r"] == case.r, (name, plan)
+        for key, want in case.expect.items():
+            if str(plan.get(key)) != str(want):
+                bad.append((name, key, plan.get(key), want))
+        note_plan(seen, collections.defaultdict(set), case.kernel, plan)
+        ws = WS_DEFAULT if case.ws is None else case.ws
+        if case.kernel == "cost":
+            seen[("cost", "csplit")].add("1" if plan["csplit"] == 1 else ">1")
+            assert plan["partial_bytes"] == 8 * plan["grid"] * plan["csplit"] and plan["vf_bytes"] == 1024 * _cdiv(case.n, 64) * plan["KS"]
+            assert 256 * _cdiv(plan["partial_bytes"], 256) + plan["vf_bytes"] <= ws, (name, plan)
+        else:
+            assert plan["ws_bytes"] == (4 * case.r ** 2 * plan["nsplit"] if plan["form"] in ("slabs", "blocks") else 0) <= ws, (name, plan)
+            assert plan["nsplit"] == _cdiv(case.m, plan["kps"]) and plan["kps"] % 64 == 0 or plan["form"] == "small", (name, plan)
+            if plan["bound"] == "workspace":
+                assert plan["ws_max"] == ws // (4 * case.r ** 2), (name, plan)
+                assert plan["nsplit"] == _cdiv(case.m, 64 * _cdiv(_cdiv(case.m, plan["ws_max"]), 64)), (name, plan)
+    assert not bad, "\n".join(map(str, bad))
+    for key in (("gram", "form"), ("gram", "bound"), ("cost", "NN"), ("cost", "vdb"), ("cost", "VEC")):
+        assert REQUIRED[key] <= seen[key], (key, REQUIRED[key] - seen[key])
+    assert seen[("cost", "csplit")] == {"1", ">1"}

@@ -2,7 +2,8 @@
 // k_mu_plan.h) for any CU count, printed as the library reports them under NNF_PLAN_DEBUG.
 //
 //   nnf_plan < cases     one case per line:  <launcher> <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [key=value ...]
-//                        launcher: xht | xty | mu_left | mu_right | mu_mode | mttkrp_rows; the factors are contiguous (r x m, r x n);
+//                        launcher: xht | xty | mu_left | mu_right | mu_mode | mttkrp_rows | mttkrp_seg | partial_last |
+//                        partial_mid | gram | cost; the factors are contiguous (r x m, r x n);
 //                        optional keys: align= (offset of X from a 16-byte boundary, in floats; default 0) and, for mttkrp_rows
 //                        (m x n = the unfolded tensor, pitch n), nb= lda= ldb= (Khatri-Rao inner length, factor pitches).
 //                        Answer, one line per case: the "[nnf plan] ..." line of that launch, followed on the same line by the
@@ -11,6 +12,21 @@
 //                        mu_mode (the mode update on the tensor's own layout, any beta) reads the same eight fields as
 //                          mu_mode <CUs> <L> <I> <r> <K> <beta> <workspace bytes> [align=] [ldv=]
 //                        and adds kt= wgpc= ws_max= pieces= ldp= ws_bytes= (what the launcher carves for the plan).
+//                        The tensor and Gram launchers read the eight fields as
+//                          mttkrp_seg <CUs> <rows> <segment length> <r> <row pitch> 0 <workspace bytes> [align=] [nseg=] [segstride=]
+//                                     [fsld=] [fkld=] [fkalign=]     (segments per row, their stride, the pitches of the segment-side
+//                                     and the inner factor, the inner factor's offset from a 16-byte boundary; default: one
+//                                     segment, contiguous factors); adds ws_max=
+//                          partial_last | partial_mid <CUs> <A> <B> <r> <B> 0 <workspace bytes>     (Y is r x A x B); partial_mid
+//                                     adds ws_bytes=
+//                          gram <CUs> <K> <K> <r> <pitch of A> 0 <workspace bytes> [align=] [ldg=]     (any rank; ldg: the pitch of
+//                                     G, default r); adds ws_max= ws_bytes=
+//                          cost <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [align=] [op=] [kr=] [pin=] [csplit=]
+//                                     op: ratio_kl | ratio_gen | prod (default: the cost of that beta); kr: the Khatri-Rao inner
+//                                     length of the CP cost (T as an (I J) x K matrix: m = I J, n = K, kr = J); pin=1: a later
+//                                     rank pass of a rank above 128 (the model buffer aligned, as the library's own is; the CP
+//                                     cost of rank R is asked for its last pass: pin=1, r = R - 128 ((R - 1) / 128)); csplit:
+//                                     NNF_COST_CSPLIT; adds KS= shm= partial_bytes= vf_bytes=
 //   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
 //                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
 //
@@ -28,6 +44,15 @@ static long long key_of(const char* rest, const char* key, long long dflt) {
     return at ? atoll(at + strlen(pat)) : dflt;
 }
 
+// the pass of a cost line: op= if given, else the cost of beta
+static const char* cost_op(const char* rest, double beta) {
+    static const char* const named[] = {"ratio_kl", "ratio_gen", "prod"};
+    const char* at = strstr(rest, " op=");
+    for (const char* nm : named)
+        if (at && strncmp(at + 4, nm, strlen(nm)) == 0 && strchr(" \t\r\n", at[4 + strlen(nm)])) return nm;
+    return at ? nullptr : beta == 2.0 ? "frob" : beta == 1.0 ? "kl" : beta == 0.0 ? "is" : "gen";
+}
+
 static int print_shm() {
     for (int MT = 5; MT <= 8; ++MT)
         for (int gen = 0; gen < 2; ++gen)
@@ -38,7 +63,7 @@ static int print_shm() {
 
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "shm") == 0) return print_shm();
-    char line[512], name[32], more[160];
+    char line[512], name[32], more[192];
     while (fgets(line, sizeof line, stdin)) {
         long long C, m, n, r, ld, ws;
         double beta;
@@ -68,7 +93,40 @@ int main(int argc, char** argv) {
             }
         } else if (m < 1 || n < 1 || r < 1 || ld < n) {
             status = NNF_ERR_ARG;
+        } else if (strcmp(name, "gram") == 0 && key_of(rest, "ldg", r) < r) {
+            status = NNF_ERR_ARG;
+        } else if (strcmp(name, "gram") == 0) {   // m = n = K, ld = the pitch of A
+            const nnf_gram_plan p = nnf_plan_gram((int)C, (int)r, m, key_of(rest, "ldg", r) == r, vec, cur.remaining());
+            snprintf(more, sizeof more, " ws_max=%lld ws_bytes=%zu", (long long)p.ws_max,
+                     p.status == NNF_OK && p.form >= NNF_GRAM_SLABS ? (size_t)(p.nsplit * r * r * 4) : (size_t)0);
+            if ((status = p.status) == NNF_OK) nnf_report_gram(stdout, (int)r, m, p, more);
         } else if (r > NNF_MAX_RANK) {
+        } else if (strcmp(name, "mttkrp_seg") == 0) {   // m = rows, n = segment length, ld = row pitch
+            const long long nseg = key_of(rest, "nseg", 1), segstride = key_of(rest, "segstride", n);
+            const int MT = (int)(r + 15) / 16;
+            const nnf_seg_plan p = nnf_plan_seg((int)C, m, ld, nseg, n, (int)r, key_of(rest, "fsld", nseg), cur.remaining());
+            snprintf(more, sizeof more, " ws_max=%lld", (long long)p.ws_max);
+            if ((status = p.status) == NNF_OK)
+                nnf_report_seg(stdout, m, nseg, n, (int)r, MT, vec && segstride % 4 == 0,
+                               key_of(rest, "fkalign", 0) % 4 == 0 && key_of(rest, "fkld", n) % 4 == 0, MT <= 2, p, more);
+        } else if (strcmp(name, "partial_last") == 0) {   // m = A, n = B
+            status = NNF_OK;
+            nnf_report_partial_last(stdout, m, n, (int)r, nnf_plan_partial_last(m, (int)r));
+        } else if (strcmp(name, "partial_mid") == 0) {
+            const nnf_partial_mid_plan p = nnf_plan_partial_mid((int)C, m, n, (int)r, cur.remaining());
+            snprintf(more, sizeof more, " ws_bytes=%zu", (size_t)(p.nchunk * r * nnf_rup(n, 4) * 4));
+            if ((status = p.status) == NNF_OK) nnf_report_partial_mid(stdout, m, n, (int)r, p, more);
+        } else if (strcmp(name, "cost") == 0) {
+            const char* op = cost_op(rest, beta);
+            const bool pin = key_of(rest, "pin", 0) != 0;
+            if (!op || !(beta >= 0.0)) {
+                status = NNF_ERR_ARG;
+            } else if (nnf_cost_offsets_ok(ld, n)) {
+                const nnf_cost_plan p = nnf_plan_cost((int)C, m, n, (int)r, key_of(rest, "kr", 0) > 0, (int)key_of(rest, "csplit", 0), pin,
+                                                      strcmp(op, "prod") == 0, cur.remaining());
+                snprintf(more, sizeof more, " KS=%d shm=%zu partial_bytes=%zu vf_bytes=%zu", p.KS, p.shm, p.partial_bytes, p.vf_bytes);
+                if ((status = p.status) == NNF_OK) nnf_report_cost(stdout, m, n, (int)r, op, vec, pin, key_of(rest, "kr", 0), p, more);
+            }
         } else if (strcmp(name, "xty") == 0) {
             const nnf_rank_tiles t = nnf_xty_tiles((int)r, vec);
             const nnf_split_plan p = nnf_plan_xty((int)C, m, n, ld, (int)r, t, 2, cur.remaining());   // (XTY_BIG_WG: the product's 2)
