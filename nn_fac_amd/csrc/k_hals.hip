@@ -14,7 +14,7 @@
 //   If ncols exceeds the resident thread count the same kernel strides over column sets, re-reading its own
 //   stores (no cross-workgroup hand-off of V is ever needed).
 // Generic path (NORMALIZE / NONZERO, and every rank above 128): the column in LDS (or, GCOL, in global memory), run-time rank
-// loop, one grid reduction per row.  Which kernel runs a call: the plan (make_plan, below).
+// loop, one grid reduction per row.  Which kernel runs a call: the plan (hals_make_plan, k_hals_plan.h).
 #include "k_hals_common.h"
 #include <cstdlib>
 
@@ -236,17 +236,9 @@ __global__ __launch_bounds__(256) void nnf_hals_sum_sweeps_kernel(const double* 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The plan: which kernel runs a call, on which grid and after which preparation, decided in ONE place from the shape of the
-// call -- the launch (hals_entry) and the capacity queries (nnf_hals_resident_columns, nnf_hals_resid_floats) read the same
-// answer.  It launches nothing and takes no workspace; the occupancy answers it uses are cached per instantiation.
+// The plan of a call (which kernel, which grid, which launches in front of it) is hals_make_plan, k_hals_plan.h.  Here: the
+// request with its pointers, and the occupancy answers the plan asks for.
 // ---------------------------------------------------------------------------------------------------------
-static int pick_rp(int r) {
-    static const int opts[] = {8, 16, 24, 32, 40, 48, 50, 52, 56, 64, 80, 96, 100, 104, 112, 128};   // 100: config E's rank
-    for (int o : opts)
-        if (r <= o) return o;
-    return (r + 7) & ~7;      // above NNF_MAX_RANK: the generic kernel only (its padded Gram has one row per 8)
-}
-
 struct hals_request {
     int mode;                      // 0: solve (stopping rule on the device)  1: fixed sweep count, per-sweep sums
     const float* UtM; int64_t ldm;
@@ -259,26 +251,17 @@ struct hals_request {
     double* status; double* nodelta;
     float* snapshots; int64_t snap_stride; int snap_first;
     const float* resid_in; float* resid_out;
+    hals_shape shape(char force) const {
+        return {mode, r, ncols, ldm, ldv, ldvs, nsweeps, sweep0, flags, UtU2 != nullptr, Vsrc != V, snapshots != nullptr, force};
+    }
 };
 
-enum hals_layout { HL_WAVE, HL_QUAD, HL_MFMA, HL_LANE_RES, HL_LANE_STREAM, HL_GENERIC_LDS, HL_GENERIC_BIG, HL_GENERIC_GCOL };
-static const char* const hals_layout_name[] = {"wave", "quad", "mfma", "lane-resident", "lane-streaming", "generic-lds",
-                                               "generic-lds-big", "generic-gcol"};
+// first letter of NNF_HALS_FORCE (hals_shape::force); read on every call: the tests change it inside one process
+static char hals_force() {
+    const char* fenv = getenv("NNF_HALS_FORCE");
+    return fenv ? fenv[0] : 0;
+}
 
-struct hals_plan {
-    int err = NNF_OK;              // else: what the call is refused with
-    hals_layout layout = HL_LANE_RES;
-    int RP = 0, nblocks = 0, per_cu = 0;   // padded rank (lane, mfma, generic); grid; workgroups per CU it relies on
-    int cpw = 0, nw = 0, ch = 0;   // wave: columns per compute wave, compute waves per workgroup; quad: rows per lane
-    size_t lds = 0;                // generic: dynamic LDS bytes
-    bool hadamard = false, copy = false, prep = true;   // launches in front of the sweep
-    bool gs = false;               // lane, mfma: the row-scaled Gram next to the padded one
-    size_t gram_floats = 0, mfma_floats = 0, snap_floats = 0;   // workspace
-};
-
-// The generic kernel: three forms (column in LDS; four lanes per column in LDS, above rank 128; GCOL) per mode
-constexpr size_t HALS_GENERIC_LDS_MAX = (size_t)150 * 1024;   // columns in LDS up to here
-constexpr size_t HALS_GENERIC_SHM_FIXED = 16 + 3 * 2 * 8 + 64;
 typedef decltype(&nnf_hals_generic_kernel<0, false>) hals_generic_fn;
 static hals_generic_fn generic_kernel(int mode, hals_layout l) {
     static const hals_generic_fn k[2][3] = {
@@ -303,147 +286,11 @@ static int generic_per_cu(int mode, hals_layout l, int r, size_t lds, int cap) {
     }
     return c - 1;
 }
+static const hals_occupancy hals_device_occupancy = {nnf_hals_wave_per_cu, nnf_hals_quad_per_cu, nnf_hals_fast_per_cu,
+                                                     nnf_hals_mfma_per_cu, generic_per_cu};
 
-static int64_t hals_cap(nnf_ctx* ctx, int per_cu) {   // workgroups that stay resident at per_cu per CU
-    const int64_t c = (int64_t)per_cu * ctx->num_cus;
-    return c < NNF_HALS_MAX_BLOCKS ? c : NNF_HALS_MAX_BLOCKS;
-}
-// The buffer offsets of rows 0 .. rows-1 of an operand with row stride ld fit 32 bits.  The lane and mfma kernels load (and
-// store) all RP padded rows of a column and rely on the rows >= r falling outside the descriptor: checked with rows = RP, so
-// that no padded row's offset wraps back into the rows of the operand.
-static bool hals_32bit(int rows, int64_t ld, int64_t ncols) {
-    return (((int64_t)(rows - 1) * ld + ncols) * 4) < (int64_t)0x7fff0000;
-}
-
-// the padded Gram (RP x RS, RS = RP rounded up to 32) and the RP (1/diag, nz) pairs + the all-live flag, then (64-byte
-// aligned) the row-scaled Gram of the lane kernel
-static size_t hals_gs_off(int RP) { return ((((size_t)RP * (32 * ((RP + 31) / 32)) + 2 * RP + 1) + 15) & ~(size_t)15); }
-
-static hals_plan refuse(hals_plan p, int err) { p.err = err; return p; }
-
-static hals_plan make_plan(nnf_ctx* ctx, const hals_request& q) {
-    hals_plan p;
-    const int r = q.r; const int64_t n = q.ncols;
-    const bool rowsync = (q.flags & (NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) != 0;
-    const bool generic = r > NNF_MAX_RANK || rowsync;
-    const bool sweeps = q.nsweeps > 0;
-    p.RP = pick_rp(r);
-    // NNF_HALS_FORCE pins the layout (tests run every kernel on the same fixtures); its first letter counts:
-    //   l lane only;  q no wave, no mfma, quad beyond 32768 columns;  w no mfma, a solve wave cannot hold is refused;
-    //   m mfma ahead of wave and quad where it covers the padded rank
-    const char* fenv = getenv("NNF_HALS_FORCE");
-    const char force = fenv ? fenv[0] : 0;
-    // many columns at ranks 64..100: the push form on the matrix cores; below rank 64 a k-block has too few MFMAs to cover its
-    // own gather -> update -> scatter chain (measured: 9.7-10.6 against 9.4-9.6 us per sweep at rank 50)
-    const bool mfma = !generic && sweeps && force != 'l' && force != 'q' && force != 'w' && nnf_hals_mfma_supported(p.RP) &&
-                      (force == 'm' || (p.RP >= 64 && n > 32768));
-    const bool pin_mfma = force == 'm' && mfma;
-
-    // few columns, a persistent solve from its first sweep: one wave per column, 1 or 2 columns per compute wave
-    const bool wave_shape = !generic && q.mode == 0 && q.sweep0 == 0;
-    if (wave_shape && force != 'l' && force != 'q' && !pin_mfma) {
-        for (int cpw = 1; cpw <= 2; ++cpw) {
-            int nw = 0;
-            const int need = nnf_hals_wave_grid(n, cpw, &nw);
-            if (need < 1 || need > NNF_HALS_MAX_BLOCKS) continue;
-            const int pc = nnf_hals_wave_per_cu(r, cpw, nw);
-            if (pc < 1) break;
-            if (need <= (int64_t)pc * ctx->num_cus) {
-                p.layout = HL_WAVE, p.cpw = cpw, p.nw = nw, p.nblocks = need, p.per_cu = pc;
-                p.prep = !sweeps;           // (the sweep kernel builds its Gram image itself)
-                p.copy = !sweeps && q.Vsrc != q.V;
-                p.gram_floats = nnf_hals_wave_gram_floats(r);
-                p.snap_floats = nnf_hals_wave_snap_floats(r, n);
-                return p;
-            }
-        }
-    }
-    if (force == 'w' && wave_shape) return refuse(p, NNF_ERR_UNSUPPORTED);
-
-    // few columns (<= 32768: at most two waves per SIMD): four lanes per column, 16 columns per workgroup.  Its buffer
-    // offsets reach row r + 15 of V, UtM and the start values in 32 bits: start values beyond that are copied into V first.
-    auto quad_32bit = [&](int64_t ld) { return (int64_t)(r + 16) * ld * 4 < (int64_t)0x7fff0000; };
-    if (!generic && force != 'l' && !pin_mfma && (n <= 32768 || force == 'q') && quad_32bit(q.ldv > q.ldm ? q.ldv : q.ldm)) {
-        const int ch = (r + 3) / 4, pc = nnf_hals_quad_per_cu(ch);
-        const int64_t need = nnf_cdiv(n, 16);
-        if (pc > 0 && need <= hals_cap(ctx, pc)) {
-            p.layout = HL_QUAD, p.ch = ch, p.nblocks = (int)need, p.per_cu = pc;
-            // (the sweep kernel reads the start values and forms the Hadamard Gram itself)
-            p.copy = q.Vsrc != q.V && (!sweeps || !quad_32bit(q.ldvs));
-            p.gram_floats = nnf_hals_quad_gram_floats(r);
-            return p;
-        }
-    }
-
-    // the padded Gram, 1/diag and the barrier words (nnf_hals_prep_kernel) in front of the lane, mfma and generic kernels; the
-    // Hadamard Gram and separate start values come from two small launches -- except that the resident lane kernel reads its
-    // start values itself (once)
-    const int RS = 32 * ((p.RP + 31) / 32);
-    p.gs = !generic && p.RP > 32 && p.RP <= 52;
-    p.gram_floats = hals_gs_off(p.RP) + (p.gs ? (size_t)p.RP * RS : 0);
-    p.hadamard = q.UtU2 != nullptr;
-    const int lane_pc = generic ? 0 : nnf_hals_fast_per_cu(p.RP, true);
-    const bool lane_fits = lane_pc > 0 && nnf_cdiv(n, 256) <= hals_cap(ctx, lane_pc);
-    p.copy = q.Vsrc != q.V && !(!generic && sweeps && lane_fits && hals_32bit(p.RP, q.ldvs, n));
-    if (!sweeps) {   // the prep kernel only (the status defaults of a solve with no sweep to run)
-        p.layout = generic ? HL_GENERIC_LDS : HL_LANE_RES;
-        return p;
-    }
-
-    if (generic) {
-        // one column per thread; when the workgroups exchange (mode 0, or a row-level reduction per row update) all of them are
-        // resident.  The column in LDS (r x 128 floats per workgroup; above rank 128 four lanes per column, r x 32 floats) while
-        // that fits and -- when the workgroups exchange -- all of them stay resident with it; else (ranks above ~1200, or more
-        // columns than that holds) the column stays in global memory (GCOL).  Measured at rank 200
-        // (tools/probes/bigrank_sweep_probe.py): LDS 3-5x faster per sweep.
-        const bool exchanges = q.mode == 0 || rowsync;
-        if (r > NNF_MAX_RANK) {
-            p.layout = HL_GENERIC_BIG;
-            p.lds = (size_t)r * 32 * 4 + HALS_GENERIC_SHM_FIXED;
-            p.per_cu = p.lds <= HALS_GENERIC_LDS_MAX ? generic_per_cu(q.mode, HL_GENERIC_BIG, r, p.lds, 0) : 0;
-            if (p.per_cu < 1 || (exchanges && nnf_cdiv(n, 32) > hals_cap(ctx, p.per_cu))) {
-                p.layout = HL_GENERIC_GCOL;
-                p.lds = HALS_GENERIC_SHM_FIXED;
-                p.per_cu = generic_per_cu(q.mode, HL_GENERIC_GCOL, r, p.lds, 4);
-            }
-        } else {
-            p.layout = HL_GENERIC_LDS;
-            p.lds = (size_t)r * 128 * 4 + HALS_GENERIC_SHM_FIXED;
-            p.per_cu = generic_per_cu(q.mode, HL_GENERIC_LDS, r, p.lds, 4);
-        }
-        if (p.per_cu < 1) return refuse(p, NNF_ERR_LAUNCH);
-        const int64_t grid = nnf_cdiv(n, p.layout == HL_GENERIC_BIG ? 32 : 128);
-        // blind sweeps without row-level reductions exchange nothing: no residency needed (any number of columns)
-        if (grid > (exchanges ? hals_cap(ctx, p.per_cu) : (int64_t)0x7fffffff)) return refuse(p, NNF_ERR_UNSUPPORTED);
-        p.nblocks = (int)grid;
-        return p;
-    }
-
-    if (!hals_32bit(p.RP, q.ldv, n) || !hals_32bit(p.RP, q.ldm, n)) return refuse(p, NNF_ERR_UNSUPPORTED);
-    const int64_t need = nnf_cdiv(n, 256);
-    if (mfma) {   // when every column stays resident; else the lane kernel
-        const int pc = nnf_hals_mfma_per_cu(p.RP);
-        if (pc > 0 && need <= hals_cap(ctx, pc)) {
-            p.layout = HL_MFMA, p.nblocks = (int)need, p.per_cu = pc;
-            p.mfma_floats = nnf_hals_mfma_gram_floats(p.RP);
-            return p;
-        }
-    }
-    if (lane_pc < 1) return refuse(p, NNF_ERR_LAUNCH);
-    if (lane_fits) {
-        p.layout = HL_LANE_RES, p.nblocks = (int)need, p.per_cu = lane_pc;
-        return p;
-    }
-    // more columns than stay resident: the streaming form strides over column sets (no snapshots)
-    if (q.snapshots != nullptr) return refuse(p, NNF_ERR_UNSUPPORTED);
-    p.layout = HL_LANE_STREAM, p.per_cu = nnf_hals_fast_per_cu(p.RP, false);
-    if (p.per_cu < 1) return refuse(p, NNF_ERR_LAUNCH);
-    p.nblocks = (int)hals_cap(ctx, p.per_cu);
-    return p;
-}
-
-// Checks the arguments, makes the plan, takes the workspace, runs the launches in front of the sweep, launches the layout's
-// kernel and, in mode 1, sums the per-workgroup partials of every sweep.
+// Checks the arguments, reads NNF_HALS_FORCE, makes the plan, reports it, takes the workspace, runs the launches in front of the
+// sweep, launches the layout's kernel and, in mode 1, sums the per-workgroup partials of every sweep.
 static int hals_entry(nnf_ctx* ctx, hals_request q, hipStream_t st) {
     if (!ctx || !q.UtM || !q.UtU || !q.V || q.r < 1 || q.ncols < 1 || q.ldm < q.ncols || q.ldv < q.ncols || q.ldg < q.r || q.nsweeps < 0)
         return NNF_ERR_ARG;
@@ -452,12 +299,9 @@ static int hals_entry(nnf_ctx* ctx, hals_request q, hipStream_t st) {
     if (q.nsweeps > NNF_HALS_MAX_SWEEPS) return NNF_ERR_UNSUPPORTED;   // (longer solves: chained by the caller)
     if (q.flags & ~(NNF_HALS_SPARSITY | NNF_HALS_NORMALIZE | NNF_HALS_NONZERO)) return NNF_ERR_ARG;
     if (q.Vsrc == nullptr || q.Vsrc == q.V) { q.Vsrc = q.V; q.ldvs = q.ldv; }
-    const hals_plan p = make_plan(ctx, q);
-    if (getenv("NNF_HALS_DEBUG"))
-        fprintf(stderr, "[nnf hals] r=%d ncols=%lld mode=%d sweeps=%d sweep0=%d flags=%u -> %s grid=%d per_cu=%d cpw=%d nw=%d ch=%d "
-                "RP=%d gs=%d lds=%zu hadamard=%d copy=%d prep=%d err=%d\n", q.r, (long long)q.ncols, q.mode, q.nsweeps, q.sweep0,
-                q.flags, hals_layout_name[p.layout], p.nblocks, p.per_cu, p.cpw, p.nw, p.ch, p.RP, p.gs, p.lds, p.hadamard, p.copy,
-                p.prep, p.err);
+    const hals_shape shape = q.shape(hals_force());
+    const hals_plan p = hals_make_plan(ctx->num_cus, hals_device_occupancy, shape);
+    if (getenv("NNF_HALS_DEBUG")) hals_report(stderr, shape, p);
     if (p.err != NNF_OK) return p.err;
 
     const bool sweeps = q.nsweeps > 0;
@@ -577,8 +421,9 @@ extern "C" int nnf_hals_sweeps_ex_f32(nnf_ctx* ctx, const float* UtM, int64_t ld
 // floats of residual state per buffer for nnf_hals_sweeps_ex_f32 on an r x ncols factor (0: the layout that runs carries none)
 extern "C" int nnf_hals_resid_floats(nnf_ctx* ctx, int r, int64_t ncols, int64_t* floats_out) {
     if (!ctx || r < 1 || ncols < 1 || !floats_out) return NNF_ERR_ARG;
-    // the blind launch of a chunk: it carries state when its plan is the matrix-core kernel
-    const hals_plan p = make_plan(ctx, {1, nullptr, ncols, nullptr, nullptr, r, nullptr, ncols, nullptr, ncols, r, ncols, 1});
+    // the blind launch of a chunk (one sweep, contiguous operands): it carries state when its plan is the matrix-core kernel
+    const hals_shape blind = {1, r, ncols, ncols, ncols, ncols, 1, 0, 0u, false, false, false, hals_force()};
+    const hals_plan p = hals_make_plan(ctx->num_cus, hals_device_occupancy, blind);
     *floats_out = (p.err == NNF_OK && p.layout == HL_MFMA) ? (int64_t)nnf_hals_mfma_resid_floats(p.RP, ncols) : 0;
     return NNF_OK;
 }
@@ -648,15 +493,9 @@ __global__ __launch_bounds__(256) void nnf_hals_stop_restore_kernel(const double
 // (the row-sharded protocol, the solve of a 10^6-column factor on one device) split the columns into blocks of this size.
 extern "C" int nnf_hals_resident_columns(nnf_ctx* ctx, int r, int64_t* columns_out) {
     if (!ctx || r < 1 || !columns_out) return NNF_ERR_ARG;
-    if (r > NNF_MAX_RANK) {   // the generic kernel with the column per thread in global memory (GCOL), 128 per workgroup
-        const int pc = generic_per_cu(0, HL_GENERIC_GCOL, r, HALS_GENERIC_SHM_FIXED, 4);
-        if (pc < 1) return NNF_ERR_LAUNCH;
-        *columns_out = hals_cap(ctx, pc) * 128;
-        return NNF_OK;
-    }
-    const int pc = nnf_hals_fast_per_cu(pick_rp(r), true);   // the resident lane kernel, 256 columns per workgroup
-    if (pc < 1) return NNF_ERR_LAUNCH;
-    *columns_out = hals_cap(ctx, pc) * 256;
+    const int64_t columns = hals_resident_columns(ctx->num_cus, hals_device_occupancy, r);
+    if (columns < 1) return NNF_ERR_LAUNCH;
+    *columns_out = columns;
     return NNF_OK;
 }
 

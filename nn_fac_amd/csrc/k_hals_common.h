@@ -1,6 +1,7 @@
 // Shared by k_hals.hip (entry points, generic path) and k_hals_fast.hip (register-resident fast path).
 #pragma once
 #include "nnf_internal.h"
+#include "k_hals_plan.h"   // the sweep plan, the layouts' size arithmetic and constants: no HIP
 
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -377,8 +378,9 @@ static inline int hals_per_cu(hipError_t e, int nb, int cap) {
     return cap > 0 && b > cap ? cap : b;
 }
 
-// Each layout exports a cached "workgroups per CU" query for one instantiation and a launcher that only launches; which
-// layout runs, and with which grid, is decided by the plan in k_hals.hip.
+// Each layout exports a cached "workgroups per CU" query for one instantiation (k_hals.hip hands them to the plan as its
+// hals_occupancy) and a launcher that only launches; which layout runs, and with which grid, is decided by the plan in
+// k_hals_plan.h, where the layouts' workspace sizes are too.
 
 // k_hals_fast.hip: one lane per column, padded rank RP <= 128; `resident`: the columns stay in registers (all workgroups
 // co-resident), else the streaming form strides over column sets.  Lane cap: 3 workgroups per CU.
@@ -386,24 +388,17 @@ int nnf_hals_fast_per_cu(int RP, bool resident);
 int nnf_hals_fast_launch(int RP, bool resident, const hals_args& a, int nblocks, hipStream_t);
 
 // k_hals_wave.hip: one wave per column (lane = row), push form of the sweep; solve mode from the first sweep, r <= 128
-int nnf_hals_wave_grid(int64_t ncols, int cpw, int* nw_out);   // workgroups for cpw columns per compute wave (0: too many)
 int nnf_hals_wave_per_cu(int r, int cpw, int nw);
-size_t nnf_hals_wave_gram_floats(int r);
-size_t nnf_hals_wave_snap_floats(int r, int64_t ncols);
 int nnf_hals_wave_prep(const float* UtU, const float* UtU2, int64_t ldg, int r, float* Gw, unsigned* counter, double* status,
                        hipStream_t);   // status defaults and barrier word of a solve that runs no sweep
 int nnf_hals_wave_launch(int cpw, int nw, const hals_args& a, int64_t ldg, float* snap, int nblocks, hipStream_t);
 
 // k_hals_mfma.hip: push form on the matrix cores, many columns, ranks 48..100 (resident columns only)
-bool nnf_hals_mfma_supported(int RP);
 int nnf_hals_mfma_per_cu(int RP);
-size_t nnf_hals_mfma_gram_floats(int RP);
-size_t nnf_hals_mfma_resid_floats(int RP, int64_t ncols);
 int nnf_hals_mfma_launch(int RP, const float* UtU, int64_t ldg, float* gram, hals_args a, int nblocks, hipStream_t);   // prep + sweep
 
 // k_hals_quad.hip: four lanes per column, for solves with few columns (16 per workgroup), CH = ceil(r / 4) rows per lane
 int nnf_hals_quad_per_cu(int ch);
-size_t nnf_hals_quad_gram_floats(int r);
 int nnf_hals_quad_prep(const float* UtU, const float* UtU2, int64_t ldg, int r, float* Gq, unsigned* counter, double* status,
                        hipStream_t);
 int nnf_hals_quad_launch(int ch, hals_args a, float* Gq, int nblocks, hipStream_t);

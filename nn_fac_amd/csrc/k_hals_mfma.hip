@@ -556,33 +556,6 @@ __global__ __launch_bounds__(256) void nnf_hals_mfma_prep_kernel(const float* __
     }
 }
 
-struct mfma_shape { int rt, rem, nkb; };
-static bool mfma_shape_of(int RP, mfma_shape& s) {
-    switch (RP) {
-        case 48: s = {3, 0, 12}; return true;
-        case 50: s = {3, 2, 13}; return true;
-        case 52: s = {3, 4, 13}; return true;
-        case 64: s = {4, 0, 16}; return true;
-        case 80: s = {5, 0, 20}; return true;
-        case 96: s = {6, 0, 24}; return true;
-        case 100: s = {6, 4, 25}; return true;
-        default: return false;
-    }
-}
-bool nnf_hals_mfma_supported(int RP) { mfma_shape s; return mfma_shape_of(RP, s); }
-size_t nnf_hals_mfma_gram_floats(int RP) {
-    mfma_shape s;
-    if (!mfma_shape_of(RP, s)) return 0;
-    return (size_t)s.nkb * ((s.rt + 3) / 4) * 256 + (size_t)s.nkb * 32 + 64;
-}
-
-// floats of residual state a chunked solve of `ncols` columns carries from launch to launch (0: rank not covered)
-size_t nnf_hals_mfma_resid_floats(int RP, int64_t ncols) {
-    mfma_shape s;
-    if (!mfma_shape_of(RP, s) || ncols < 1) return 0;
-    return (size_t)nnf_cdiv(ncols, 256) * 4 * (s.rt * 4 + 1) * 256;
-}
-
 template <int RT, int REM, int NKB>
 static int mfma_per_cu() {
     static int cached = -1;

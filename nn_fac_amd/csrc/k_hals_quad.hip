@@ -350,11 +350,6 @@ int nnf_hals_quad_per_cu(int ch) {
          : ch <= 27 ? nnf_hals_quad_per_cu_part2(ch) : nnf_hals_quad_per_cu_part3(ch);
 }
 
-size_t nnf_hals_quad_gram_floats(int r) {
-    const int ch = (r + 3) / 4, rq = 4 * ch, rs = 4 * ((ch + 3) & ~3);
-    return (size_t)rq * rs + rq;
-}
-
 // Gq: workspace of nnf_hals_quad_gram_floats(r) floats (the row-scaled Gram image, then 1/diag per row)
 int nnf_hals_quad_prep(const float* UtU, const float* UtU2, int64_t ldg, int r, float* Gq, unsigned* counter, double* status,
                        hipStream_t st) {

@@ -42,10 +42,7 @@
 // Rows with a zero Gram diagonal (nnls.py:160) and the padding rows hold residual 0 and "-v" = -inf: their step is 0.
 #include "k_hals_common.h"
 
-constexpr int WAVE_COMM = 4;         // communication waves per workgroup
-constexpr int WAVE_MAX_NW = 16 - WAVE_COMM;   // compute waves (= columns) per workgroup (1024 threads in all)
-constexpr int WAVE_SNAP = 16;        // snapshot / slot / verdict rings (sweeps a compute wave may run ahead of the verdicts, + 1)
-constexpr int WAVE_NP = 6;           // granule pairs per lane of a communication wave: nblocks <= 384
+// (WAVE_COMM, WAVE_MAX_NW, WAVE_SNAP, WAVE_NP and the sizes the plan counts with them: k_hals_plan.h)
 #ifndef WAVE_REFRESH_V
 #define WAVE_REFRESH_V 8             // (A/B builds: 4, 2 -- tools/probes/wave_refresh_probe.sh; accuracy / time table in DESIGN.md section 4)
 #endif
@@ -486,22 +483,7 @@ __global__ __launch_bounds__(1024) void nnf_hals_wave_kernel(hals_args a, int64_
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-static int wave_ru(int r) { return (r + 7) & ~7; }
-static int wave_rl(int r) { return r <= 64 ? 1 : 2; }
 static size_t wave_lds(int r) { return (size_t)wave_ru(r) * 64 * wave_rl(r) * 4 + sizeof(wave_ctl) + 16; }
-size_t nnf_hals_wave_gram_floats(int r) { return (size_t)wave_ru(r) * 64 * wave_rl(r) + 128; }
-size_t nnf_hals_wave_snap_floats(int r, int64_t ncols) { return (size_t)ncols * WAVE_SNAP * 64 * wave_rl(r); }
-
-// nw compute waves per workgroup (about one workgroup per CU), workgroups for cpw columns per compute wave; 0: more
-// workgroups than the communication waves collect
-int nnf_hals_wave_grid(int64_t ncols, int cpw, int* nw_out) {
-    int nw = (int)nnf_cdiv(ncols, 256);
-    if (nw < 1) nw = 1;
-    if (nw > WAVE_MAX_NW) nw = WAVE_MAX_NW;
-    *nw_out = nw;
-    const int64_t need = nnf_cdiv(ncols, (int64_t)nw * cpw);
-    return need > 64 * WAVE_NP ? 0 : (int)need;
-}
 
 template <int RL, int RU, int CPW>
 static int wave_per_cu(int nw) {

@@ -1,5 +1,6 @@
 // Context management and small deterministic helpers of libnnfac_hip.so.
 #include "nnf_internal.h"
+#include "k_hals_plan.h"   // NNF_HALS_MAX_SWEEPS, NNF_HALS_MAX_BLOCKS: the size of the exchange region
 #include <new>
 
 #include <map>

@@ -40,9 +40,6 @@ void nnf_register_build_flags(const char* unit, const char* flags);
     }
 #define NNF_BUILD_FLAGS(unit, str) NNF_BUILD_FLAGS_I(unit, str)   /* (arguments are macro-expanded first: NNF_CAT(base, PART)) */
 
-#define NNF_HALS_MAX_SWEEPS 1000   // per launch: the exchange tag holds the sweep index in 10 bits (k_hals_common.h)
-#define NNF_HALS_MAX_BLOCKS 2048   // workgroups of one persistent solve (3 * 256 CUs fits)
-
 // measurement hook: record the caller's event `which` (0 begin, 1 end) if the probe is armed for kernel `id`
 static inline void nnf_probe(nnf_ctx* c, int id, int which, hipStream_t st) {
     if (c->probe_id != id) return;

@@ -1,7 +1,7 @@
-"""Every HALS sweep plan (k_hals.hip: make_plan) and kernel instance against fp64.  Needs a MI355X, except
-test_hals_cases_reach_required.
+"""Every HALS sweep plan (k_hals_plan.h: hals_make_plan) and kernel instance against fp64.  Needs a MI355X, except
+test_hals_cases_reach_required; test_hals_plan_table.py checks the same table against the plan header without one.
 
-make_plan picks one of eight layouts from the shape of a call and the CU count: wave (k_hals_wave.hip, one wave per column,
+hals_make_plan picks one of eight layouts from the shape of a call and the CU count: wave (k_hals_wave.hip, one wave per column,
 CPW columns per compute wave), quad (k_hals_quad.hip, CH rows per lane), mfma (k_hals_mfma.hip, padded rank RP), the lane
 kernel resident or streaming (k_hals_fast.hip, RP), and the generic kernel with the column in LDS, in LDS four lanes per column
 (LDS-big, ranks above 128) or in global memory (GCOL).  hals_cases(C) names the plan every case must take, with shapes written
@@ -196,13 +196,14 @@ def hals_cases(C):
     add("lane_r101", "sweeps", 101, 40000, lane(101, 40000), budget=3)
     # features: resident lane reads V_in itself, streaming copies; Hadamard launch; sparsity; zero diagonal; ncols; snapshots
     add("lane_res_cross_gram2", "cross", 20, 40000, lane(20, 40000, hadamard=1, copy=0), gram2=True, ld=dict(ldvs=3, ldv=1, ldg=2))
-    add("lane_stream_cross_gram2", "cross", 20, 131073, lane(20, 131073, res=False, hadamard=1, copy=1), gram2=True, ld=dict(ldvs=3))
+    ns = 256 * PER_CU[("lane-resident", 24)] * C + 1            # RP 24: one column more than stays resident
+    add("lane_stream_cross_gram2", "cross", 20, ns, lane(20, ns, res=False, hadamard=1, copy=1), gram2=True, ld=dict(ldvs=3))
     add("lane_res_sp_zero_diag", "solve", 45, 40000, lane(45, 40000), flags="sp", zero_diag=(0, 44))
     add("lane_stream_sp_zero_diag", "sweeps", 30, 200000, lane(30, 200000, res=False), flags="sp", zero_diag=(29,), budget=3)
     for n in (1, 255, 257):
         add(f"lane_n{n}", "sweeps", 57, n, lane(57, n), force="lane", ld=dict(ldv=1))
     add("lane_snap", "snap", 24, 40000, lane(24, 40000), budget=4)
-    add("lane_stream_snap_refused", "snap", 24, 131073, dict(err=UNSUP), budget=3)
+    add("lane_stream_snap_refused", "snap", 24, ns, dict(err=UNSUP), budget=3)
     add("lane_cont", "cont", 20, 40000, lane(20, 40000), budget=3)
     # the 32-bit buffer offsets of the lane (and mfma) kernel, whose loads and stores cover all RP padded rows of a column:
     # ((RP - 1) ld + n) 4 < 0x7fff0000.  The rest of these buffers holds NaN (sentinels in V): a padded row whose offset wrapped
@@ -221,7 +222,10 @@ def hals_cases(C):
         r = rp if rp in (50, 52, 100) else rp - 1
         force = "mfma" if rp < 64 else None
         add(f"mfma_rp{rp}", "sweeps", r, 40000, mfma(r, 40000), force=force, ld=dict(ldm=1, ldv=3, ldg=1) if rp % 16 else {}, budget=3)
-    add("mfma_r64_n32768_lane", "sweeps", 64, 32768, lane(64, 32768), budget=3)      # (quad CH 16 holds 7 x 16 columns per CU)
+    # 32768 columns, not one more: not mfma, and lane where quad does not hold them -- the first mfma rank whose quad instance
+    # keeps fewer than 32768 columns resident (rank 64 at 256 CUs: CH 16 holds 7 x 16 columns per CU)
+    rq = next(rp for rp in MFMA_RPS if rp >= 64 and 16 * PER_CU[("quad", rp // 4)] * C < 32768)
+    add("mfma_r64_n32768_lane", "sweeps", rq, 32768, lane(rq, 32768), budget=3)
     add("mfma_r64_n32769", "sweeps", 64, 32769, mfma(64, 32769), budget=3)
     nm = 256 * PER_CU[("mfma", 64)] * C
     add("mfma_r64_cap", "sweeps", 64, nm, mfma(64, nm), budget=3)
@@ -530,6 +534,15 @@ print("done")
 """
 
 
+def parse_report(line):
+    """{key: value} of one "[nnf hals] ..." report line (values as strings; "layout": the name after the arrow)."""
+    head, tail = line[11:].split(" -> ")
+    f = tail.split()
+    kv = dict(kv.split("=", 1) for kv in head.split() + f[1:])
+    kv["layout"] = f[0]
+    return kv
+
+
 def parse_plans(stderr):
     """{case name: [{key: value}]} (one dict per report line) from the child's stderr."""
     plans, cur = {}, None
@@ -538,12 +551,62 @@ def parse_plans(stderr):
             cur = line[7:].strip()
             plans[cur] = []
         elif line.startswith("[nnf hals] ") and cur is not None:
-            head, tail = line[11:].split(" -> ")
-            f = tail.split()
-            kv = dict(kv.split("=", 1) for kv in head.split() + f[1:])
-            kv["layout"] = f[0]
-            plans[cur].append(kv)
+            plans[cur].append(parse_report(line))
     return plans
+
+
+# ---- the same table without a device: the library's plan header through tools/nnf_plan.cpp ----
+FLAG_BITS = {"": 0, "sp": 1, "norm": 2, "nz": 4}      # NNF_HALS_SPARSITY, NNF_HALS_NORMALIZE, NNF_HALS_NONZERO
+
+
+def hals_line(C, case, wave_pc=None):
+    """The `hals` line of tools/nnf_plan.cpp for the call of run_call() that writes the case's LAST report line, with every
+    per-CU figure PER_CU pins for the kernel instances of its shape (the tool fails when the plan asks for one that is not
+    there).  wave_pc: the figure of a wave instance with 3 .. 11 compute waves, which PER_CU does not pin; default: the
+    pinned figure of 12 compute waves -- more waves per workgroup cannot raise it, so the case has to hold with it."""
+    e, r, n, b, ld = case.entry, case.r, case.n, case.budget, case.ld
+    mode = 1 if e in ("sweeps", "snap", "chunks") else 0
+    nsweeps, sweep0 = (b - 2, 2) if e in ("cont", "chunks") else (b, 0)       # the second call of the two
+    flags = 2 if e == "csolve" else FLAG_BITS[case.flags]
+    kv = dict(mode=mode, r=r, ncols=n, nsweeps=nsweeps, sweep0=sweep0, flags=flags,
+              ldm=ld.get("ldm_abs", n + ld.get("ldm", 0)), ldv=ld.get("ldv_abs", n + ld.get("ldv", 0)))
+    if e == "cross":
+        kv.update(own_start=1, gram2=int(case.gram2), ldvs=ld.get("ldvs_abs", n + ld.get("ldvs", 0)))
+    if e == "snap":
+        kv["snapshots"] = 1
+    if case.force:
+        kv["force"] = case.force[0]
+    rp = pick_rp(r)
+    if r <= 128:
+        ru, nw = (r + 7) & ~7, wave_nw(n)
+        kv["pc_wave1"] = PER_CU.get(("wave", ru, 1, nw), wave_pc or PER_CU[("wave", ru, 1, 12)])
+        if ("wave", ru, 2, nw) in PER_CU:
+            kv["pc_wave2"] = PER_CU[("wave", ru, 2, nw)]
+        kv["pc_quad"] = PER_CU[("quad", (r + 3) // 4)]
+        kv["pc_lane_res"], kv["pc_lane_stream"] = PER_CU[("lane-resident", rp)], PER_CU[("lane-streaming", rp)]
+    else:
+        kv["pc_generic_gcol"] = PER_CU[("generic-gcol", 0)]
+    for key, form in (("pc_mfma", "mfma"), ("pc_generic_lds", "generic-lds"), ("pc_generic_big", "generic-lds-big")):
+        if (form, rp if form == "mfma" else r) in PER_CU:
+            kv[key] = PER_CU[(form, rp if form == "mfma" else r)]
+    return "hals %d " % C + " ".join("%s=%s" % item for item in kv.items())
+
+
+def ask_plan_tool(lines):
+    """The answer of tools/nnf_plan.cpp to each line (built by test_mu_plan_table.plan_tool)."""
+    from test_mu_plan_table import plan_tool
+    p = subprocess.run([plan_tool()], input="".join(l + "\n" for l in lines), capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    answers = p.stdout.splitlines()
+    assert len(answers) == len(lines), p.stdout[-2000:]
+    return answers
+
+
+def hals_tool_plans(C, cases, wave_pc=None):
+    """{case name: {key: value}}: the report line the library's plan header gives for each case on C compute units."""
+    names = list(cases)
+    answers = ask_plan_tool([hals_line(C, cases[nm], (wave_pc or {}).get(nm)) for nm in names])
+    return {nm: parse_report(text) for nm, text in zip(names, answers)}
 
 
 @pytest.fixture(scope="module")
@@ -557,7 +620,9 @@ def reported(built_lib):
 
 @pytest.mark.gpu
 def test_hals_plan_table(reported):
-    """Every case takes the plan it is listed with (its last report line), and the reported per-CU figures are PER_CU's."""
+    """Every case takes the plan it is listed with (its last report line), and the reported per-CU figures are PER_CU's.  The
+    plan header, asked through tools/nnf_plan.cpp for the request hals_line() makes of the case, answers that same line field by
+    field: the CPU table test (test_hals_plan_table.py) asks about the calls the library was really given."""
     cases = hals_cases(_cus())
     assert sorted(reported) == sorted(cases)
     bad = []
@@ -571,6 +636,13 @@ def test_hals_plan_table(reported):
         for key, want in case.expect.items():
             if kv.get(key) != str(want):
                 bad.append((name, key, kv.get(key), want))
+    assert not bad, "\n".join(map(str, bad))
+    # (a wave instance PER_CU does not pin: the figure the library reported)
+    wave_pc = {name: int(lines[-1]["per_cu"]) for name, lines in reported.items() if lines[-1]["layout"] == "wave"}
+    for name, kv in hals_tool_plans(_cus(), cases, wave_pc).items():
+        for key, got in reported[name][-1].items():
+            if kv[key] != got:
+                bad.append((name, "tool", key, kv[key], got))
     assert not bad, "\n".join(map(str, bad))
 
 

@@ -1,5 +1,5 @@
 // The launch plans of libnnfac_hip.so without a device: the library's own plan functions (nn_fac_amd/csrc/k_stream_plan.h,
-// k_mu_plan.h) for any CU count, printed as the library reports them under NNF_PLAN_DEBUG.
+// k_mu_plan.h, k_hals_plan.h) for any CU count, printed as the library reports them under NNF_PLAN_DEBUG / NNF_HALS_DEBUG.
 //
 //   nnf_plan < cases     one case per line:  <launcher> <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [key=value ...]
 //                        launcher: xht | xty | mu_left | mu_right | mu_mode | mttkrp_rows | mttkrp_seg | partial_last |
@@ -27,6 +27,19 @@
 //                                     rank pass of a rank above 128 (the model buffer aligned, as the library's own is; the CP
 //                                     cost of rank R is asked for its last pass: pin=1, r = R - 128 ((R - 1) / 128)); csplit:
 //                                     NNF_COST_CSPLIT; adds KS= shm= partial_bytes= vf_bytes=
+//                        The HALS sweep plan (k_hals_plan.h) reads key=value fields only:
+//                          hals <CUs> mode= r= ncols= nsweeps= [sweep0=] [flags=] [ldm=] [ldv=] [ldvs=] [gram2=] [own_start=]
+//                               [snapshots=] [force=] [pc_...=]     the fields of hals_shape: mode 0 a solve, 1 blind sweeps; flags
+//                                     the NNF_HALS_* bits; the pitches default to ncols (ldvs: to ldv); gram2 / own_start /
+//                                     snapshots = 1: a second Gram, separate start values, snapshots asked for; force: the
+//                                     first letter of NNF_HALS_FORCE.  pc_...: the workgroups per CU the device would report
+//                                     for the kernel instances of this shape -- pc_wave1= pc_wave2= (1, 2 columns per compute
+//                                     wave) pc_quad= pc_lane_res= pc_lane_stream= pc_mfma= pc_generic_lds= pc_generic_big=
+//                                     pc_generic_gcol= (the generic kernel's three forms, after their cap).  A figure the plan
+//                                     asks for and the line does not give is an error: the tool names it and exits with 3.
+//                                     Answer: the "[nnf hals] ..." line of that call (NNF_HALS_DEBUG; a refusal is its err=),
+//                                     followed by gram_floats= mfma_floats= snap_floats= (what the launcher carves).
+//                          hals_resident <CUs> r= [pc_lane_res=] [pc_generic_gcol=]     nnf_hals_resident_columns: "columns=<n>"
 //   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
 //                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
 //
@@ -36,6 +49,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "k_mu_plan.h"
+#include "k_hals_plan.h"
 
 static long long key_of(const char* rest, const char* key, long long dflt) {
     char pat[32];
@@ -61,6 +75,59 @@ static int print_shm() {
     return 0;
 }
 
+// ---- hals lines: the occupancy answers of the plan are the pc_ fields of the line being answered ----
+static const char* hals_line;
+static int hals_figure(const char* key) {
+    char pat[32];
+    snprintf(pat, sizeof pat, " %s=", key);
+    const char* at = strstr(hals_line, pat);
+    if (!at) {
+        fprintf(stderr, "nnf_plan: the plan asks for %s, which this line does not give: %s", key, hals_line);
+        exit(3);
+    }
+    return atoi(at + strlen(pat));
+}
+static int pc_wave(int, int cpw, int) { return hals_figure(cpw == 1 ? "pc_wave1" : "pc_wave2"); }
+static int pc_quad(int) { return hals_figure("pc_quad"); }
+static int pc_lane(int, bool resident) { return hals_figure(resident ? "pc_lane_res" : "pc_lane_stream"); }
+static int pc_mfma(int) { return hals_figure("pc_mfma"); }
+static int pc_generic(int, hals_layout l, int, size_t, int) {
+    return hals_figure(l == HL_GENERIC_LDS ? "pc_generic_lds" : l == HL_GENERIC_BIG ? "pc_generic_big" : "pc_generic_gcol");
+}
+static const hals_occupancy hals_line_occupancy = {pc_wave, pc_quad, pc_lane, pc_mfma, pc_generic};
+
+static int answer_hals(const char* name, const char* line) {
+    int C = 0, used = 0;
+    if (sscanf(line, "%*s %d%n", &C, &used) != 1 || C < 1) return 2;
+    const char* rest = hals_line = line + used;
+    const long long r = key_of(rest, "r", 0);
+    if (strcmp(name, "hals_resident") == 0) {
+        const long long columns = r < 1 ? 0 : hals_resident_columns(C, hals_line_occupancy, (int)r);
+        if (columns > 0) printf("columns=%lld\n", columns);
+        else printf("status=%d\n", r < 1 ? NNF_ERR_ARG : NNF_ERR_LAUNCH);
+        return 0;
+    }
+    const long long n = key_of(rest, "ncols", 0), ldm = key_of(rest, "ldm", n), ldv = key_of(rest, "ldv", n);
+    const char* fat = strstr(rest, " force=");
+    const hals_shape q = {(int)key_of(rest, "mode", -1), (int)r, n, ldm, ldv, key_of(rest, "ldvs", ldv), (int)key_of(rest, "nsweeps", -1),
+                          (int)key_of(rest, "sweep0", 0), (unsigned)key_of(rest, "flags", 0), key_of(rest, "gram2", 0) != 0,
+                          key_of(rest, "own_start", 0) != 0, key_of(rest, "snapshots", 0) != 0,
+                          fat && !strchr(" \t\r\n", fat[7]) ? fat[7] : (char)0};
+    // (the argument checks of hals_entry, k_hals.hip)
+    if ((q.mode != 0 && q.mode != 1) || r < 1 || n < 1 || ldm < n || ldv < n || q.nsweeps < 0 || q.sweep0 < 0 ||
+        (q.flags & ~(NNF_HALS_SPARSITY | NNF_HALS_NORMALIZE | NNF_HALS_NONZERO))) {
+        printf("status=%d\n", NNF_ERR_ARG);
+    } else if (q.nsweeps > NNF_HALS_MAX_SWEEPS) {
+        printf("status=%d\n", NNF_ERR_UNSUPPORTED);
+    } else {
+        const hals_plan p = hals_make_plan(C, hals_line_occupancy, q);
+        char more[96];
+        snprintf(more, sizeof more, " gram_floats=%zu mfma_floats=%zu snap_floats=%zu", p.gram_floats, p.mfma_floats, p.snap_floats);
+        hals_report(stdout, q, p, more);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "shm") == 0) return print_shm();
     char line[512], name[32], more[192];
@@ -68,6 +135,13 @@ int main(int argc, char** argv) {
         long long C, m, n, r, ld, ws;
         double beta;
         int used = 0;
+        if (sscanf(line, "%31s", name) == 1 && strncmp(name, "hals", 4) == 0) {
+            if (answer_hals(name, line) != 0) {
+                fprintf(stderr, "nnf_plan: bad case line: %s", line);
+                return 2;
+            }
+            continue;
+        }
         if (sscanf(line, "%31s %lld %lld %lld %lld %lld %lf %lld%n", name, &C, &m, &n, &r, &ld, &beta, &ws, &used) != 8) {
             if (line[strspn(line, " \t\r\n")] == 0) continue;
             fprintf(stderr, "nnf_plan: bad case line: %s", line);
