@@ -4,19 +4,17 @@ Every driver enqueues one iteration after the other; each leaves a status block 
 reaches the host through an asynchronous copy and an event.  What the host does with such a block -- when it looks, what a
 "redo" word in it leads to, what it prints, when it stops -- is written here once:
 
-    StatusRing          the ring of status blocks with their host mirrors
+    StatusRing          the ring of status blocks with their host mirrors (the words of a block: _status.py)
     check_status        status words -> nothing / a redo exception / the user-facing exception
     Retired             the host side of a finished iteration (costs, times, printing, stopping test: the reference's)
     Pipeline            pending queue, in-order retirement, flush, stop, rewind to a failed iteration
     IdentityGuard       when a cost taken from the Gram identity cannot be trusted
-    note_sweep_count    row-sharded runs: when the device-side stopping decision is engaged, where its next guess sits
+    AsyncStop           row-sharded runs: when the device-side stopping decision is engaged, where its next guess sits
 
 The drivers supply what is theirs: how a step is enqueued, where cost and sweep counts sit in a block, and what each redo
 exception changes in their own switches.  Nothing here asks which driver it serves.
 """
 import dataclasses
-import math
-import os
 import time
 
 import torch
@@ -24,18 +22,6 @@ import torch
 from .utils import errors as err
 from . import engine as _engine
 from . import dist as _dist
-
-
-def mode_view(T, mode):
-    """The contiguous tensor as (prod of the extents before `mode`, I_mode, prod of those behind): a view."""
-    shape = [int(d) for d in T.shape]
-    return T.view(math.prod(shape[:mode]), shape[mode], math.prod(shape[mode + 1:]))
-
-
-def mu_on_layout(eng, r):
-    """Whether the MU update of a mode other than the last (whose unfolding is a view) runs on the tensor's own layout
-    (Engine.mu_mode) instead of a materialised unfolding: up to the kernel's rank, unless NNF_MU_UNFOLD=1 (read at call time)."""
-    return r <= eng.MU_MODE_MAX_RANK and os.environ.get("NNF_MU_UNFOLD") != "1"
 
 
 class StatusRing:
@@ -52,6 +38,10 @@ class StatusRing:
     def select(self, slot):
         self.slot = slot
         self.block = self.blocks[slot]
+
+    def solve_words(self, i):
+        """The 8 status words of solve `i` of the selected block (a view)."""
+        return self.block[_engine.ST_WORDS * i:_engine.ST_WORDS * (i + 1)]
 
 
 class _SolveTimedOut(Exception):
@@ -84,7 +74,7 @@ def check_status(host, nstat, nranks=0, can_fall_back=False):
     is a rank-local event (the replicated V-side solve of ONE rank found the chip shared), and a rank that fell back to
     chunked solves alone would issue a different sequence of collectives than its peers (a hang over RCCL)."""
     for i in range(nstat):
-        code = _dist.agreed_code(host, i, nranks) if nranks else int(host[8 * i + _engine.ST_ERR])
+        code = _dist.agreed_code(host, i, nranks) if nranks else int(host[_engine.ST_WORDS * i + _engine.ST_ERR])
         if code == 2:
             raise err.ZeroColumnWhenUnautorized("A column of U is zero with nonzero condition")
         if code in (_dist.ERR_BEFORE_WINDOW, _dist.ERR_NOT_STOPPED):
@@ -97,7 +87,7 @@ def check_status(host, nstat, nranks=0, can_fall_back=False):
 
 def sweep_counts(host, nstat):
     """Inner sweeps of each of the `nstat` solves of a status block (the kernels count like the reference: sweeps + 1)."""
-    return [int(host[8 * i + _engine.ST_CNT]) - 1 for i in range(nstat)]
+    return [int(host[_engine.ST_WORDS * i + _engine.ST_CNT]) - 1 for i in range(nstat)]
 
 
 class Retired:
@@ -250,14 +240,27 @@ class IdentityGuard:
         self.last = None
 
 
-def note_sweep_count(state, guess, count, hit):
-    """Row-sharded solve with the device-side stopping decision (dist.sharded_hals_solve_async), after a retired iteration
-    whose sharded solve took `count` sweeps.  A missed guess costs a pipeline drain + a redone iteration, and the sweep counts
-    of the first outer iterations jump by tens (33, 52, 67, 38, ... at NMF config B), so the decision is engaged only once
-    two consecutive solves differ by <= 4 sweeps (`state.async_ready`).  `hit`: this solve took it, and its guess held -- the
-    next blind chunk is centred on this count."""
-    state.async_ready = state.last_count is not None and abs(count - state.last_count) <= 4
-    state.last_count = count
-    if hit:
-        state.async_hits += 1
-        guess.value = max(8, min(count + 4, guess.max_chunk))
+class AsyncStop:
+    """Row-sharded runs: the state of the device-side stopping decision of the sharded solve (dist.sharded_hals_solve_async).
+    `async_sharded`: the run may take it (dist.opt_in; None = not decided yet); `async_ready`: it is engaged (below);
+    `sync_next`: the next step uses the host-synchronous protocol (after a redo); `last_step_async`: the last step took it."""
+
+    def __init__(self, async_sharded=None):
+        self.async_sharded = async_sharded
+        self.async_ready = self.sync_next = self.last_step_async = False
+        self.last_count = None
+        self.async_hits = self.async_misses = 0
+
+    def note_sweep_count(self, guess, count, hit):
+        """After a retired iteration whose sharded solve took `count` sweeps.  A missed guess costs a pipeline drain + a redone
+        iteration, and the sweep counts of the first outer iterations jump by tens (33, 52, 67, 38, ... at NMF config B), so the
+        decision is engaged only once two consecutive solves differ by <= 4 sweeps (`async_ready`).  `hit`: this solve took it,
+        and its guess held -- the next blind chunk is centred on this count."""
+        self.async_ready = self.last_count is not None and abs(count - self.last_count) <= 4
+        self.last_count = count
+        if hit:
+            self.async_hits += 1
+            guess.value = max(8, min(count + 4, guess.max_chunk))
+
+
+note_sweep_count = AsyncStop.note_sweep_count      # (state, guess, count, hit): on any object with those fields

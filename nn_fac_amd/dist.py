@@ -21,11 +21,13 @@ launch, with one copy of the factor taken at the start of the chunk.  A stop bef
 more than the window since the previous outer iteration) restores that copy and re-runs exactly the right number of
 sweeps -- the kernels are deterministic, so the result is bitwise what a straight run would hold.
 """
+import os
+
 import torch
 import torch.distributed as dist
 
-
-import os
+from ._status import NMF_COST, NMF_ERRS
+from .engine import ST_ERR, ST_WORDS
 
 # NNF_FORCE_SHARDED=1: a ONE-rank group runs the row-sharded protocol too (its chunked solves, collectives and host decisions,
 # with nobody to exchange with) -- rehearsal and measurement of what the protocol costs a rank on a one-GPU box
@@ -64,14 +66,15 @@ def allreduce_max_(t, group):
 
 
 def allreduce_cost_(block, group):
-    """The cost word of an iteration's 24-double status block ([16]) summed over the row blocks -- and, in the same
-    collective, copies of the error words of the iteration's two solves ([3], [11] -> [17], [18]).  A solve's error word is
-    identical on every rank except for one code: 1, "the persistent kernel gave up waiting for its workgroups", which is a
-    rank-local event.  The sums let every rank decode the same code (`agreed_code`) and take the same branch of
-    nmf.run_steps -- a rank falling back to chunked solves alone would stop matching its peers' collectives."""
+    """The cost word of an iteration's 24-double status block (NMF_COST) summed over the row blocks -- and, in the same
+    collective, copies of the error words of the iteration's two solves (ST_ERR of each -> NMF_ERRS, the two words behind the
+    cost).  A solve's error word is identical on every rank except for one code: 1, "the persistent kernel gave up waiting
+    for its workgroups", which is a rank-local event.  The sums let every rank decode the same code (`agreed_code`) and take
+    the same branch of nmf.run_steps -- a rank falling back to chunked solves alone would stop matching its peers'
+    collectives."""
     if is_sharded(group):
-        block[17:19].copy_(block[3:12:8])
-        dist.all_reduce(block[16:19], op=dist.ReduceOp.SUM, group=group)
+        block[NMF_ERRS:NMF_ERRS + 2].copy_(block[ST_ERR:2 * ST_WORDS:ST_WORDS])
+        dist.all_reduce(block[NMF_COST:NMF_ERRS + 2], op=dist.ReduceOp.SUM, group=group)
     return block
 
 
@@ -79,8 +82,8 @@ def allreduce_errs_(block, group):
     """The error words alone (HALS cost through the Gram identity: every operand of the cost is replicated, nothing else of
     the block has to cross ranks)."""
     if is_sharded(group):
-        block[17:19].copy_(block[3:12:8])
-        dist.all_reduce(block[17:19], op=dist.ReduceOp.SUM, group=group)
+        block[NMF_ERRS:NMF_ERRS + 2].copy_(block[ST_ERR:2 * ST_WORDS:ST_WORDS])
+        dist.all_reduce(block[NMF_ERRS:NMF_ERRS + 2], op=dist.ReduceOp.SUM, group=group)
     return block
 
 
@@ -88,7 +91,7 @@ def agreed_code(host, i, nranks):
     """Error code of solve i from the summed copies made by allreduce_cost_: 0 if no rank reported anything; the common code
     when every rank reported the same one (3 / 4: the device-side stopping decision missed -- a function of all-reduced sums;
     2: a zero row of the replicated factor); otherwise some ranks timed out and others did not: 1 for everybody."""
-    total = int(round(float(host[17 + i])))
+    total = int(round(float(host[NMF_ERRS + i])))
     if total == 0:
         return 0
     return total // nranks if total % nranks == 0 else 1

@@ -10,6 +10,7 @@ import threading
 import torch
 
 from . import _lib
+from ._status import write_status
 from .utils import errors as err
 from .utils.errors import EngineError
 
@@ -263,7 +264,7 @@ class Engine:
         from . import dist as _dist
         eps, cnt, eps0 = _dist.sharded_hals_solve_rownorm(self, UtM, UtU, V, None, budget=int(max_sweeps), delta=float(delta),
                                                           sparsity=sparsity, normalize=normalize, nonzero=nonzero)
-        st[:4] = torch.tensor([eps, float(cnt), eps0, 0.0], dtype=torch.float64)
+        write_status(st, eps, float(cnt), eps0)
         return st
 
     HALS_MAX_SWEEPS_PER_LAUNCH = 1000     # NNF_HALS_MAX_SWEEPS (exchange tags hold the sweep index in 10 bits)

@@ -17,7 +17,6 @@ Inputs may be NumPy arrays or torch tensors; results come back in kind.  Arithme
 """
 import math
 import os
-import time
 import warnings
 
 import numpy as np
@@ -29,6 +28,8 @@ from . import engine as _engine
 from ._convert import device_of, to_dev, to_dev_t, like_input
 from . import dist as _dist
 from . import _outer_loop as _loop
+from ._status import NMF_COST, NMF_IDENT_COST, NMF_IDENT_VERDICT, NMF_IDENT_ESTIMATE, NMF_WORDS, write_status
+from .update_rules.nnls import tic, toc, timed_budget
 from ._outer_loop import _SolveTimedOut, _IdentityUnreliable, _IdentityNearStop, _GuessMissed  # noqa: F401
 
 
@@ -103,7 +104,7 @@ def one_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta,
     Ut2, V2, nstat = _one_nmf_step_dev(eng, ws, X, rank, Ut, V, update_rule, beta, sparsity_coefficients,
                                        fixed_modes, normalize, deterministic)
     host = ws.block.cpu()
-    cost = float(host[16])
+    cost = float(host[NMF_COST])
     _loop.check_status(host, nstat)
     return like_input(Ut2.t(), U_in), like_input(V2, V_in), cost
 
@@ -112,12 +113,12 @@ def one_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta,
 PIPELINE_DEPTH = 1   # outer iterations enqueued ahead of the one whose cost the host is looking at
 
 
-class _StepBuffers(_loop.StatusRing):
+class _StepBuffers(_loop.StatusRing, _loop.AsyncStop):
     """Device scratch reused across iterations (cross terms, Grams, status words)."""
 
     def select(self, slot):
         super().select(slot)
-        self.cost = self.block[16:17]
+        self.cost = _cost_word(self.block)
 
     def __init__(self, X, r, dtype=torch.float32):
         m, n = X.shape
@@ -132,23 +133,19 @@ class _StepBuffers(_loop.StatusRing):
         # a collective of its own, r x r doubles)
         self.G64 = torch.empty((r, r), dtype=torch.float64, device=X.device) if X.is_cuda else None
         self.g64_ok = False
-        # one block read back per iteration: HALS status of the first / second solve at [0:8] / [8:16], cost at [16].
+        # one block read back per iteration: HALS status of the first / second solve at [0:8] / [8:16], then the cost words
+        # (_status.py).
         # A ring of PIPELINE_DEPTH + 1 blocks with pinned host mirrors: run_steps enqueues iteration i+1 before it reads
         # the block of iteration i, so the device never waits for the host between iterations.
-        self.init_ring(PIPELINE_DEPTH + 2, 24, X.device)
+        self.init_ring(PIPELINE_DEPTH + 2, NMF_WORDS, X.device)
         self.guess_u = _dist.SweepGuess()
         self.guess_v = _dist.SweepGuess()
         # Row-sharded U-side solve with the device-side stopping decision (dist.sharded_hals_solve_async): on by default over
         # RCCL, NNF_SHARDED_ASYNC=0/1 forces it (dist.opt_in).  It is engaged only once two consecutive solves differ by <= 4
-        # sweeps (`async_ready`, _outer_loop.note_sweep_count).  Validated for correctness (gloo world-size-2 tests, one-GPU kernel test);
+        # sweeps (`async_ready`, _outer_loop.AsyncStop).  Validated for correctness (gloo world-size-2 tests, one-GPU kernel test);
         # its gain needs one process per GPU to show -- with two ranks time-slicing ONE GPU (the only rehearsal available
         # here) the unsynchronised ranks starve each other's persistent V-side solves -- hence off over gloo.
-        self.async_sharded = None         # decided by run_steps from the group (dist.opt_in)
-        self.async_ready = False
-        self.last_count = None
-        self.sync_next = False            # row-sharded: the next step uses the host-synchronous U-side protocol (after a redo)
-        self.last_step_async = False
-        self.async_hits = self.async_misses = 0
+        _loop.AsyncStop.__init__(self)    # (whether the run may take it: decided by run_steps from the group, dist.opt_in)
         self.safe_solve = False           # set by run_steps after a persistent solve timed out (chunked launches from then on)
         self.direct_cost = False          # set by run_steps when the Gram-identity cost said it cannot carry the residual
         self.normx2 = None                # ||X||^2 (float64 device scalar; row-sharded: summed over the ranks), on first use
@@ -159,6 +156,9 @@ class _StepBuffers(_loop.StatusRing):
         # a third context + stream: the cost of one iteration runs under the V-side solve of the next (run_steps)
         self.cost_eng, self.cost_stream = _engine.get_side_engine(X.device, "cost") if X.is_cuda else (None, None)
 
+
+def _cost_word(block):
+    return block[NMF_COST:NMF_COST + 1]
 
 
 def _gram_on_side(ws, eng, A, out):
@@ -178,11 +178,6 @@ def _gram_on_side(ws, eng, A, out):
         side.wait_event(ready)
         ws.side_eng.gram(A, out=out)
         return side.record_event()
-
-
-def _sync(dev):
-    if torch.device(dev).type == "cuda":
-        torch.cuda.synchronize(dev)
 
 
 def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coefficients, fixed_modes, normalize,
@@ -264,7 +259,7 @@ def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coeff
             if fused_mu:
                 # the last step's cost from the SAME kernel as every other cost of the run (an update whose output is
                 # dropped): a run stopped early and a run of exactly that many iterations give bitwise equal costs
-                eng.mu_left(X, Ut_s, V_s, beta, cost_out=block[16:17])
+                eng.mu_left(X, Ut_s, V_s, beta, cost_out=_cost_word(block))
                 _dist.allreduce_cost_(block, group)
             else:
                 _step_cost(ws.cost_eng if stream is not main else eng, X, Ut_s, V_s, update_rule, beta,
@@ -278,7 +273,7 @@ def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coeff
         ws.select(iteration % ws.blocks.shape[0])
         hooks = {}
         if fused_mu and owed is not None:
-            hooks["mu_cost_out"] = ws.blocks[owed.slot][16:17]        # cost of the previous step, by-product of this left update
+            hooks["mu_cost_out"] = _cost_word(ws.blocks[owed.slot])   # cost of the previous step, by-product of this left update
         if overlap and owed is not None:
             hooks["before_v_solve"] = lambda prev=owed: cost_of(prev, ws.cost_stream)
         if overlap and costed is not None:
@@ -290,10 +285,10 @@ def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coeff
         step = _loop.Step(iteration, ws.slot, (Ut, V), nstat, async_solve=ws.last_step_async, ident=ident)
         ws.sync_next = False
         if ident:
-            # words 19..21 of the block: {cost, 1 = not reliable, error estimate}; the V update's operands are still in place
-            eng.gram_cost(V, ws.UtM, ws.G2, ws.normx2, ws.block[19:22], rounding=ws.cross_rounding,
-                          UtU64=ws.G64 if ws.g64_ok else None)
-            _add_sparsity_terms(Ut, V, sparsity_coefficients, ws.block[19:20], group)
+            # the identity words of the block: {cost, 1 = not reliable, error estimate}; the V update's operands are still in place
+            eng.gram_cost(V, ws.UtM, ws.G2, ws.normx2, ws.block[NMF_IDENT_COST:NMF_IDENT_ESTIMATE + 1],
+                          rounding=ws.cross_rounding, UtU64=ws.G64 if ws.g64_ok else None)
+            _add_sparsity_terms(Ut, V, sparsity_coefficients, ws.block[NMF_IDENT_COST:NMF_IDENT_COST + 1], group)
             _dist.allreduce_errs_(ws.block, group)
             ws.host[ws.slot].copy_(ws.block, non_blocking=True)
             step.event = main.record_event()
@@ -321,10 +316,10 @@ def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coeff
         host = ws.host[step.slot]
         _loop.check_status(host, step.nstat, nranks=nranks, can_fall_back=not ws.safe_solve)
         if step.ident:
-            guard.check(float(host[20]), float(host[19]), float(host[21]))
+            guard.check(float(host[NMF_IDENT_VERDICT]), float(host[NMF_IDENT_COST]), float(host[NMF_IDENT_ESTIMATE]))
         if group is not None and update_rule == "hals" and step.nstat >= 1 and 0 not in fixed_modes:
-            _loop.note_sweep_count(ws, ws.guess_u, int(host[_engine.ST_CNT]) - 1, step.async_solve)
-        return float(host[19 if step.ident else 16]), _loop.sweep_counts(host, step.nstat)
+            ws.note_sweep_count(ws.guess_u, int(host[_engine.ST_CNT]) - 1, step.async_solve)
+        return float(host[NMF_IDENT_COST if step.ident else NMF_COST]), _loop.sweep_counts(host, step.nstat)
 
     def overlap_again():
         """Everything in flight was dropped: no cost is owed, and the depth follows the overlap."""
@@ -352,7 +347,7 @@ def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coeff
         def direct_cost():
             scratch = torch.zeros_like(ws.block)
             _step_cost(eng, X, factors[0], factors[1], update_rule, beta, sparsity_coefficients, scratch, group)
-            return float(scratch[16])
+            return float(scratch[NMF_COST])
         guard.switch(retired, direct_cost)
         ws.direct_cost = True
         ident = False
@@ -377,18 +372,12 @@ def run_steps(eng, ws, X, rank, Ut, V, n_iter, update_rule, beta, sparsity_coeff
 HALS_INNER = {"maxiter": 100, "delta": 0.01}
 
 
-def _timed_budget(eng, cross, gram, F, sparsity, normalize, timer, group=None):
-    """Sweep budget of the wall-clock rule: rho = atime / btime with btime = the time of one sweep, measured on a scratch copy
-    (nnls.py:155,190-194), cnt <= 1 + 0.5 rho (nnls.py:156).  Row-sharded runs take rank 0's figure on every rank."""
-    from .update_rules.nnls import sweep_budget
+def _agreed_budget(eng, cross, gram, F, sparsity, normalize, timer, group=None):
+    """Sweep budget of the wall-clock rule (nnls.timed_budget, alpha = 0.5: nmf.py:415-419).  Row-sharded runs take rank 0's
+    figure on every rank."""
     probe = F.clone()
-    _sync(F.device)
-    t0 = time.time()
-    eng.hals_sweeps(cross, gram, probe, 1, sparsity=sparsity, normalize=normalize)
-    _sync(F.device)
-    btime = max(time.time() - t0, 10e-7)
-    rho = timer / btime if timer else 100000
-    budget = max(1, sweep_budget(HALS_INNER["maxiter"], 0.5, rho))
+    budget, _ = timed_budget(HALS_INNER["maxiter"], 0.5, timer, lambda: eng.hals_sweeps(
+        cross, gram, probe, 1, sparsity=sparsity, normalize=normalize), F.device)
     return _dist.agree_int(budget, group, F.device)
 
 
@@ -402,7 +391,6 @@ def _hals_call(eng, cross, gram, F_in, sparsity, normalize, deterministic, timer
     `guess` (a dist.SweepGuess): the same chunked form is ALSO the fast one for a factor with more columns than the resident
     sweep kernel holds (config E on one device: 10^6 columns, rank 100) -- blind chunks over register-resident column blocks
     instead of a kernel that streams the whole factor through HBM every sweep (935 -> ~350 us per sweep there)."""
-    from .update_rules.nnls import sweep_budget
     budget = HALS_INNER["maxiter"]
     if safe is None and guess is not None and deterministic and not normalize:
         cap = getattr(eng, "hals_resident_columns", None)
@@ -412,10 +400,10 @@ def _hals_call(eng, cross, gram, F_in, sparsity, normalize, deterministic, timer
         F = F_in.clone()
         eps, cnt, eps0 = _dist.sharded_hals_solve(eng, cross, gram, F, None, safe, budget=budget, delta=HALS_INNER["delta"],
                                                   sparsity=sparsity)
-        status[:4] = torch.tensor([eps, cnt, eps0, 0.0], dtype=torch.float64)
+        write_status(status, eps, cnt, eps0)
         return F
     if not deterministic:
-        budget = _timed_budget(eng, cross, gram, F_in, sparsity, normalize, timer, group)
+        budget = _agreed_budget(eng, cross, gram, F_in, sparsity, normalize, timer, group)
     if hasattr(eng, "hals_solve_cross"):
         F = torch.empty_like(F_in)
         eng.hals_solve_cross(cross, gram, None, F_in, F, budget, delta=HALS_INNER["delta"], sparsity=sparsity, normalize=normalize,
@@ -437,9 +425,9 @@ def _step_cost_local(eng, X, Ut, V, update_rule, beta, out):
 
 def _step_cost_finish(Ut, V, update_rule, sparsity_coefficients, block, group=None):
     """Sum over the row blocks (the error words of the iteration's solves ride along: dist.allreduce_cost_) and the sparsity
-    terms of nmf.py:452.  `block`: the iteration's 24-double status block, cost at [16]."""
+    terms of nmf.py:452.  `block`: the iteration's 24-double status block."""
     sharded = _dist.is_sharded(group)
-    out = block[16:17]
+    out = _cost_word(block)
     if sharded:
         _dist.allreduce_cost_(block, group)
     if update_rule == "hals":
@@ -460,8 +448,8 @@ def _add_sparsity_terms(Ut, V, sparsity_coefficients, out, group=None):
 
 
 def _step_cost(eng, X, Ut, V, update_rule, beta, sparsity_coefficients, block, group=None):
-    """The cost line of one_nmf_step (nmf.py:449-455) into word 16 of the float64 status block `block`, on the current stream."""
-    _step_cost_local(eng, X, Ut, V, update_rule, beta, block[16:17])
+    """The cost line of one_nmf_step (nmf.py:449-455) into the cost word of the float64 status block `block`, current stream."""
+    _step_cost_local(eng, X, Ut, V, update_rule, beta, _cost_word(block))
     _step_cost_finish(Ut, V, update_rule, sparsity_coefficients, block, group)
 
 
@@ -482,39 +470,35 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
 
     Ut, V = Ut_in, V_in
     nstat = 0
+    alpha = math.inf if deterministic else 0.5     # (nmf.py:415-419,440-444)
     dev = X.device
 
     if 0 not in fixed_modes:
         if update_rule == "hals":
-            timer = None
-            if not deterministic:
-                _sync(dev)
-                t0 = time.time()
+            t0 = tic(dev, alpha)
             done = _gram_on_side(ws, eng, V, ws.G)      # VVt (nmf.py:407)
             eng.xht(X, V, out=ws.VMt)                   # VMt  (nmf.py:408)
             if done is not None:
                 torch.cuda.current_stream(dev).wait_event(done)
-            if not deterministic:
-                _sync(dev)
-                timer = time.time() - t0
+            timer = toc(dev, t0)
             if before_u_solve is not None:
                 before_u_solve()
             ws.last_step_async = False
             budget_u = HALS_INNER["maxiter"]
             if sharded and not deterministic:    # wall-clock rule (nnls.py:190-194): rank 0's budget on every rank
-                budget_u = _timed_budget(eng, ws.VMt, ws.G, Ut, sparsity_coefficients[0], False, timer, group)
+                budget_u = _agreed_budget(eng, ws.VMt, ws.G, Ut, sparsity_coefficients[0], False, timer, group)
             if sharded:
                 Ut = Ut_in.clone()                  # the chunked sharded protocols work in place (nmf.py:415: from U_in^T)
             if sharded and normalize[0]:
                 # the row norm runs over the columns of all ranks, once per row update: rows walked from the host (dist.py)
                 eps, cnt, eps0 = _dist.sharded_hals_solve_rownorm(eng, ws.VMt, ws.G, Ut, group, budget=budget_u,
                                                                   delta=HALS_INNER["delta"], sparsity=sparsity_coefficients[0])
-                ws.block[8 * nstat:8 * nstat + 4] = torch.tensor([eps, cnt, eps0, 0.0], dtype=torch.float64)
+                write_status(ws.solve_words(nstat), eps, cnt, eps0)
             elif sharded and deterministic and hasattr(eng, "hals_stop_restore") and not ws.sync_next and ws.async_sharded \
                     and ws.async_ready:
                 # no host round trip: blind chunk + all-reduce + device-side replay of the stopping rule; a missed guess
                 # shows in the status block and run_steps redoes the iteration through the branch below
-                _dist.sharded_hals_solve_async(eng, ws.VMt, ws.G, Ut, group, ws.guess_u, ws.block[8 * nstat:8 * nstat + 8],
+                _dist.sharded_hals_solve_async(eng, ws.VMt, ws.G, Ut, group, ws.guess_u, ws.solve_words(nstat),
                                                budget=HALS_INNER["maxiter"], delta=HALS_INNER["delta"],
                                                sparsity=sparsity_coefficients[0])
                 ws.last_step_async = True
@@ -522,11 +506,10 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
                 eps, cnt, eps0 = _dist.sharded_hals_solve(eng, ws.VMt, ws.G, Ut, group, ws.guess_u,
                                                           budget=budget_u, delta=HALS_INNER["delta"],
                                                           sparsity=sparsity_coefficients[0])
-                ws.block[8 * nstat:8 * nstat + 4] = torch.tensor([eps, cnt, eps0, 0.0], dtype=torch.float64)
+                write_status(ws.solve_words(nstat), eps, cnt, eps0)
             else:
                 Ut = _hals_call(eng, ws.VMt, ws.G, Ut_in, sparsity_coefficients[0], normalize[0], deterministic, timer,
-                                ws.block[8 * nstat:8 * nstat + 8],
-                                safe=ws.guess_u if ws.safe_solve else None, guess=ws.guess_u)
+                                ws.solve_words(nstat), safe=ws.guess_u if ws.safe_solve else None, guess=ws.guess_u)
             nstat += 1
         else:
             if mu_cost_out is not None:                 # + beta_divergence(X, U_in V_in, 1): the previous iteration's cost
@@ -536,10 +519,7 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
 
     if 1 not in fixed_modes:
         if update_rule == "hals":
-            timer = None
-            if not deterministic:
-                _sync(dev)
-                t0 = time.time()
+            t0 = tic(dev, alpha)
             ws.g64_ok = ws.G64 is not None and isinstance(eng, _engine.Engine)
             if ws.g64_ok:
                 eng.gram(Ut, out=ws.G2, out64=ws.G64)   # UtU  (nmf.py:432) -- in line: see _gram_on_side; + its fp64 sums
@@ -550,13 +530,11 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
                 _dist.allreduce_(ws.v_terms, group)
                 if ws.g64_ok:                           # the fp64 sums of the Gram for the identity cost: r x r doubles
                     _dist.allreduce_(ws.G64, group)
-            if not deterministic:
-                _sync(dev)
-                timer = time.time() - t0
+            timer = toc(dev, t0)
             if before_v_solve is not None:
                 before_v_solve()
             V = _hals_call(eng, ws.UtM, ws.G2, V_in, sparsity_coefficients[1], normalize[1], deterministic, timer,
-                           ws.block[8 * nstat:8 * nstat + 8], safe=ws.guess_v if ws.safe_solve else None,
+                           ws.solve_words(nstat), safe=ws.guess_v if ws.safe_solve else None,
                            group=group if sharded else None, guess=ws.guess_v)
             nstat += 1
         else:

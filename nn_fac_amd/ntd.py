@@ -25,7 +25,6 @@ Tensor-sized work goes through the C ABI; what stays in torch is core-sized (pro
 """
 import math
 import os
-import time
 import warnings
 
 import numpy as np
@@ -35,8 +34,9 @@ from .utils import errors as err
 from .utils import initialize_factors as init_factors
 from . import engine as _engine
 from ._convert import device_of, to_dev, to_dev_t, like_input
-from .update_rules.nnls import sweep_budget
+from .update_rules.nnls import tic, toc, timed_budget
 from . import _outer_loop as _loop
+from ._tensor_state import TensorState, mu_mode_update
 
 
 def ntd(tensor, ranks, init="random", core_0=None, factors_0=[], n_iter_max=100, tol=1e-6,
@@ -80,31 +80,19 @@ def ntd(tensor, ranks, init="random", core_0=None, factors_0=[], n_iter_max=100,
                        verbose=verbose, return_costs=return_costs, deterministic=deterministic, seed=seed)
 
 
-class _NtdState(_loop.StatusRing):
+class _NtdState(TensorState):
     """Device-resident tensor, its squared norm, (MU only) the materialised unfoldings, and the per-step status block."""
 
     def __init__(self, eng, T):
         if T.dim() < 3:
             raise NotImplementedError("NTD needs a tensor of order >= 3")
-        self.eng = eng
-        self.T = T.contiguous()
-        self.nway = self.T.dim()
-        self.t0 = self.T.view(self.T.shape[0], -1)
-        self.norm2 = eng.dot(self.t0, self.t0)          # float64 device scalar, ||T||^2 (read once by the driver)
-        self.norm2_host = None
-        self._unf_t = {}
+        super().__init__(eng, T)
+        self.norm2_host = None                          # ||T||^2 is read once by the driver (norm_sq)
         # one HALS status block (8 doubles) per mode, then 6 doubles of the core update, then the cost; two of them with
         # pinned host mirrors: compute_ntd enqueues iteration i+1 before it looks at the block of iteration i
         self.pg_at = 8 * self.nway
         self.cost_at = self.pg_at + 6
         self.init_ring(2, self.cost_at + 2, T.device)
-
-    def unfolded_t(self, mode):
-        """tl.unfold(T, mode)^T as a contiguous (prod(other dims)) x I_mode matrix (MU path).  The last mode is a view of T;
-        the others are materialised once per run -- only above rank 64 or under NNF_MU_UNFOLD=1 (_outer_loop.mu_on_layout)."""
-        if mode not in self._unf_t:
-            self._unf_t[mode] = torch.movedim(self.T, mode, -1).reshape(-1, self.T.shape[mode]).contiguous()
-        return self._unf_t[mode]
 
     def norm_sq(self):
         if self.norm2_host is None:
@@ -189,9 +177,7 @@ def _one_ntd_step_dev(st, core_in, Ft_in, sparsity_coefficients, fixed_modes, no
     grams = [None] * N
     deterministic = math.isinf(alpha)
     for mode in modes_list:
-        if not deterministic:
-            torch.cuda.synchronize(dev)
-            t0 = time.time()
+        t0 = tic(dev, alpha)
         for i in range(N):
             if i != mode:
                 grams[i] = eng.gram(Ft[i])                                    # elemprod (ntd.py:534-537)
@@ -223,16 +209,12 @@ def _one_ntd_step_dev(st, core_in, Ft_in, sparsity_coefficients, fixed_modes, no
         new = Ft[mode].clone()
         budget = 100
         if not deterministic:
-            torch.cuda.synchronize(dev)
-            timer = time.time() - t0
+            timer = toc(dev, t0)
             probe = new.clone()
-            t0 = time.time()
-            eng.hals_sweeps(UtM, UtU, probe, 1, sparsity=sparsity_coefficients[mode], normalize=normalize[mode])
-            torch.cuda.synchronize(dev)
-            rho = timer / max(time.time() - t0, 10e-7) if timer else 100000
-            budget = max(1, sweep_budget(100, alpha, rho))
+            budget, _ = timed_budget(budget, alpha, timer, lambda: eng.hals_sweeps(
+                UtM, UtU, probe, 1, sparsity=sparsity_coefficients[mode], normalize=normalize[mode]), dev)
         eng.hals_solve(UtM, UtU, new, budget, delta=delta, sparsity=sparsity_coefficients[mode],
-                       normalize=normalize[mode], status=st.block[8 * nstat:8 * nstat + 8])
+                       normalize=normalize[mode], status=st.solve_words(nstat))
         nstat += 1
         Ft[mode] = new
         if mode == 0:
@@ -362,16 +344,7 @@ def _one_ntd_step_mu_dev(st, core_in, Ft_in, beta, fixed_modes, normalize, mode_
             mats = [Ft[i].t() if i != mode else None for i in range(N)]
             V = torch.movedim(_core_mode_dots(eng, core, mats, skip=mode), mode, 0)
             V = V.reshape(V.shape[0], -1).contiguous()
-        # mu_betadivmin(F, V, unfold(T, mode)) (ntd.py:672) on the TRANSPOSED problem unfold^T ~ V^T F^T: the unfolding is
-        # short and fat (I_mode rows), its transpose gives the streaming kernel prod(other dims) rows to split over
-        # (the last mode's is a view of T).  Every other mode is updated on the tensor's own layout against the same V
-        # (nnf_mu_mode_f32, r_mode <= 64): no transposed copy of T; NNF_MU_UNFOLD=1 restores the unfolding.
-        if mode == N - 1:
-            Ft[mode] = eng.mu_right(st.T.view(-1, st.T.shape[mode]), V, Ft[mode], beta)
-        elif _loop.mu_on_layout(eng, Ft[mode].shape[0]):
-            Ft[mode] = eng.mu_mode(_loop.mode_view(st.T, mode), Ft[mode], V, beta)
-        else:
-            Ft[mode] = eng.mu_right(st.unfolded_t(mode), V, Ft[mode], beta)
+        Ft[mode] = mu_mode_update(st, mode, Ft[mode], V, beta)
     core = _mu_tensorial_dev(st, core, Ft, beta)
     if normalize[-1]:
         core = _normalize_core(core, mode_core_norm)

@@ -23,18 +23,18 @@ tree and the fused cost pass are 3-way only.
 """
 import math
 import os
-import time
 
-import numpy as np
 import torch
 
 from .utils import errors as err
 from .utils import initialize_factors as init_factors
 from . import engine as _engine
 from ._convert import device_of, to_dev, to_dev_t, like_input
-from .update_rules.nnls import sweep_budget
+from .update_rules.nnls import tic, toc, timed_budget
 from . import dist as _dist
 from . import _outer_loop as _loop
+from ._status import write_status
+from ._tensor_state import TensorState, mu_mode_update
 from ._outer_loop import _IdentityUnreliable, _IdentityNearStop, _GuessMissed  # noqa: F401
 
 
@@ -62,7 +62,7 @@ def ntf(tensor, rank, init="random", factors_0=[], n_iter_max=100, tol=1e-8,
                        verbose=verbose, return_costs=return_costs)
 
 
-class _NtfState(_loop.StatusRing):
+class _NtfState(TensorState, _loop.AsyncStop):
     """Device-resident tensor, its squared norm and (MU only) the materialised unfoldings.
 
     With `group` (torch.distributed process group) T is this rank's block of the LEADING mode and the mode-0
@@ -75,23 +75,12 @@ class _NtfState(_loop.StatusRing):
             raise NotImplementedError("NTF needs a tensor of order >= 3 (a matrix is nmf's business)")
         if T.dim() > 3 and _dist.world(group) > 1:
             raise NotImplementedError("leading-mode-sharded NTF is built for 3-way tensors")
-        self.eng = eng
-        self.group = group
-        self.T = T.contiguous()
-        self.nway = self.T.dim()
-        t2 = self.T.view(self.T.shape[0], -1)
-        self.norm2 = eng.dot(t2, t2)          # float64 device scalar, ||T||^2
-        if _dist.is_sharded(group):
-            _dist.allreduce_(self.norm2, group)
+        super().__init__(eng, T, group)
         self.guess0 = _dist.SweepGuess()
         # leading-mode-sharded runs: the mode-0 solve with the device-side stopping decision (dist.sharded_hals_solve_async),
         # as in the NMF step -- engaged once two consecutive solves differ by <= 4 sweeps, a missed guess redoes the
-        # iteration with the host-synchronous protocol (run_ntf_steps, _outer_loop.note_sweep_count)
-        self.async_sharded = _dist.is_sharded(group) and _dist.opt_in("NNF_SHARDED_ASYNC", group)
-        self.async_ready = self.sync_next = self.last_step_async = False
-        self.last_count = None
-        self.async_hits = self.async_misses = 0
-        self._unf = {}
+        # iteration with the host-synchronous protocol (run_ntf_steps, _outer_loop.AsyncStop)
+        _loop.AsyncStop.__init__(self, _dist.is_sharded(group) and _dist.opt_in("NNF_SHARDED_ASYNC", group))
         self.direct_cost = False           # set for the rest of a run once the Gram-identity cost was found unreliable
         self._Y, self._Y_of, self._grams = None, None, {}
         # per-iteration status: one HALS status block per mode, then {cost, 1 = identity cost not reliable, its error
@@ -147,13 +136,6 @@ class _NtfState(_loop.StatusRing):
         G = self.eng.gram(F)
         self._grams[i] = (F, G)
         return G
-
-    def unfolded_t(self, mode):
-        """tl.unfold(T, mode)^T = moveaxis(mode -> last).reshape(-1, dim), contiguous (MU path; the last mode is a view).
-        The other modes are only materialised above rank 64 or under NNF_MU_UNFOLD=1 (_outer_loop.mu_on_layout)."""
-        if mode not in self._unf:
-            self._unf[mode] = torch.movedim(self.T, mode, -1).reshape(-1, self.T.shape[mode]).contiguous()
-        return self._unf[mode]
 
 
 def _kr_group_t(Fts):
@@ -252,9 +234,7 @@ def _one_ntf_step_dev(st, rank, Ft_in, update_rule, beta, sparsity_coefficients,
     for mode in [m for m in range(N) if m not in fixed_modes]:
         if update_rule == "hals":
             deterministic = math.isinf(alpha)
-            if not deterministic:
-                torch.cuda.synchronize(dev)
-                t0 = time.time()
+            t0 = tic(dev, alpha)
             Ga = Gb = None              # the two Grams whose Hadamard product is `cross` (ntf.py:442-445)
             if sharded and mode != 0:
                 # MTTKRP output (R x I_mode) and the Gram of the sharded mode-0 factor (R x R) are sums over the blocks of
@@ -280,7 +260,7 @@ def _one_ntf_step_dev(st, rank, Ft_in, update_rule, beta, sparsity_coefficients,
                 # result written to a NEW tensor: no Hadamard launch, no copy in front of the solve
                 new = torch.empty_like(Ft[mode])
                 eng.hals_solve_cross(rhs_t, Ga, Gb, Ft[mode], new, budget, delta=delta, sparsity=sparsity_coefficients[mode],
-                                     normalize=normalize[mode], status=st.block[8 * nstat:8 * nstat + 8])
+                                     normalize=normalize[mode], status=st.solve_words(nstat))
                 nstat += 1
                 Ft[mode] = new
                 last = (mode, rhs_t, Ga, Gb)
@@ -291,41 +271,27 @@ def _one_ntf_step_dev(st, rank, Ft_in, update_rule, beta, sparsity_coefficients,
             if sharded and mode == 0:
                 if st.async_sharded and st.async_ready and not st.sync_next and hasattr(eng, "hals_stop_restore"):
                     _dist.sharded_hals_solve_async(eng, rhs_t, cross, new, st.group, st.guess0,
-                                                   st.block[8 * nstat:8 * nstat + 8], budget=budget, delta=delta,
+                                                   st.solve_words(nstat), budget=budget, delta=delta,
                                                    sparsity=sparsity_coefficients[mode])
                     st.last_step_async = True
                 else:
                     eps, cnt, eps0 = _dist.sharded_hals_solve(eng, rhs_t, cross, new, st.group, st.guess0, budget=budget,
                                                               delta=delta, sparsity=sparsity_coefficients[mode])
-                    st.block[8 * nstat:8 * nstat + 4] = torch.tensor([eps, cnt, eps0, 0.0], dtype=torch.float64)
+                    write_status(st.solve_words(nstat), eps, cnt, eps0)
                 nstat += 1
                 Ft[mode] = new
                 continue
             if not deterministic:
-                torch.cuda.synchronize(dev)
-                timer = time.time() - t0
+                timer = toc(dev, t0)
                 probe = new.clone()
-                t0 = time.time()
-                eng.hals_sweeps(rhs_t, cross, probe, 1, sparsity=sparsity_coefficients[mode], normalize=normalize[mode])
-                torch.cuda.synchronize(dev)
-                rho = timer / max(time.time() - t0, 10e-7) if timer else 100000
-                budget = max(1, sweep_budget(100, alpha, rho))
+                budget, _ = timed_budget(budget, alpha, timer, lambda: eng.hals_sweeps(
+                    rhs_t, cross, probe, 1, sparsity=sparsity_coefficients[mode], normalize=normalize[mode]), dev)
             eng.hals_solve(rhs_t, cross, new, budget, delta=delta, sparsity=sparsity_coefficients[mode],
-                           normalize=normalize[mode], status=st.block[8 * nstat:8 * nstat + 8])
+                           normalize=normalize[mode], status=st.solve_words(nstat))
             nstat += 1
             Ft[mode] = new
         else:
-            # mu_betadivmin(F, krao^T, unfold) (ntf.py:459-460) on the transposed problem unfold^T ~ krao F^T: the unfolding
-            # has only I_mode rows, its transpose gives the streaming kernel prod(other dims) rows to split over
-            # (the last mode's unfolding is a view of T).  Every other mode is updated on the tensor's own layout, seen as
-            # (extents before) x I_mode x (extents behind), against the same operand (nnf_mu_mode_f32, r <= 64): no transposed
-            # copy of T.  NNF_MU_UNFOLD=1 (read at call time) takes the unfolding for every mode, for A/B runs.
-            if mode == st.T.dim() - 1:
-                Ft[mode] = eng.mu_right(st.T.view(-1, st.T.shape[mode]), _krao_t(Ft, mode), Ft[mode], beta)
-            elif _loop.mu_on_layout(eng, Ft[mode].shape[0]):
-                Ft[mode] = eng.mu_mode(_loop.mode_view(st.T, mode), Ft[mode], _krao_t(Ft, mode), beta)
-            else:
-                Ft[mode] = eng.mu_right(st.unfolded_t(mode), _krao_t(Ft, mode), Ft[mode], beta)
+            Ft[mode] = mu_mode_update(st, mode, Ft[mode], _krao_t(Ft, mode), beta)
 
     if not skip_cost:
         _ntf_cost(eng, st, Ft, update_rule, beta, sparsity_coefficients, st.block[st.cost_at:st.cost_at + 3],
@@ -382,7 +348,7 @@ def run_ntf_steps(st, rank, Ft, n_iter, update_rule, beta, sparsity_coefficients
             guard.check(float(host[st.cost_at + 1]), cost, float(host[st.cost_at + 2]) / norm2_host)
         if _dist.is_sharded(st.group) and update_rule == "hals" and 0 not in fixed_modes and step.nstat >= 1:
             # (the sharded mode-0 solve is the first status block)
-            _loop.note_sweep_count(st, st.guess0, int(host[_engine.ST_CNT]) - 1, step.async_solve)
+            st.note_sweep_count(st.guess0, int(host[_engine.ST_CNT]) - 1, step.async_solve)
         return cost, _loop.sweep_counts(host, step.nstat)
 
     def guess_missed(Ft):

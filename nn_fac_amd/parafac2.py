@@ -33,7 +33,8 @@ import numpy as np
 import torch
 
 from . import engine as _engine
-from .update_rules.nnls import sweep_budget
+from ._convert import device_of
+from .update_rules import nnls as _nnls
 from .utils import errors as err
 from .utils import initialize_factors as init_factors
 
@@ -94,16 +95,8 @@ class _State:
     """The stacked problem on the device."""
 
     def __init__(self, slices, rank, W_list, H, D_list, W_star, P_list, rows, n):
-        dev = None
-        for x in list(slices) + [H]:
-            if _is_t(x) and x.is_cuda:
-                dev = x.device
-                break
-        if dev is None:
-            if not torch.cuda.is_available():
-                raise err.EngineError("no ROCm device available: the nn_fac_amd engine is GPU-only (no CPU fallback)")
-            dev = torch.device(f"cuda:{torch.cuda.current_device()}")
-        self.dev, self.eng = dev, _engine.get_engine(dev)
+        self.dev = dev = device_of(*slices, H)
+        self.eng = _engine.get_engine(dev)
         self.r, self.K, self.n, self.rows = int(rank), len(slices), n, rows
         self.total = sum(rows)
         self.off_host = [0]
@@ -230,30 +223,9 @@ def _runs(st, lens_ok):
     return runs
 
 
-def _budget(st, alpha, atime, probe):
+def _timed(st, alpha, atime, probe):
     """Sweeps allowed by cnt <= 1 + alpha*rho (nnls.py:156): rho = wall time of the products / wall time of one probe sweep."""
-    if math.isinf(alpha) or not atime:
-        return sweep_budget(100, alpha, 100000)
-    torch.cuda.synchronize(st.dev)
-    t0 = time.time()
-    probe()
-    torch.cuda.synchronize(st.dev)
-    rho = atime / max(time.time() - t0, 10e-7)
-    return max(1, sweep_budget(100, alpha, rho))
-
-
-def _tic(st, alpha):
-    if math.isinf(alpha):
-        return None
-    torch.cuda.synchronize(st.dev)
-    return time.time()
-
-
-def _toc(st, t0):
-    if t0 is None:
-        return None
-    torch.cuda.synchronize(st.dev)
-    return time.time() - t0
+    return _nnls.timed_budget(100, alpha, atime, probe, st.dev)[0]
 
 
 def _update_W(st, mu, P, Tt, HH64, normalize0, alpha, t0):
@@ -268,7 +240,7 @@ def _update_W(st, mu, P, Tt, HH64, normalize0, alpha, t0):
     diag += torch.as_tensor(np.asarray(mu, dtype=np.float64), device=st.dev)[:, None]
     diag[frozen] = 0.0                                                             # rows the reference skips (nnls.py:316)
     Gs = G64.float().contiguous()
-    atime = _toc(st, t0)
+    atime = _nnls.toc(st.dev, t0)
     status = torch.zeros((K, _engine.ST_WORDS), dtype=torch.float64, device=st.dev)
     grouped = [(not _per_slice()) and (not normalize0) and st.rows[k] <= st.cap for k in range(K)]
     runs = _runs(st, grouped)
@@ -278,14 +250,14 @@ def _update_W(st, mu, P, Tt, HH64, normalize0, alpha, t0):
             eng.hals_solve_group(Ms, Gs[g0:g1], V, st.off[g0:g1 + 1], min(st.maxlen, st.cap), sweeps, delta=0.01,
                                  status=stt[g0:g1])
     if runs:
-        budget = _budget(st, alpha, atime, lambda: launch(st.Wt.clone(), 1, torch.empty_like(status)))
+        budget = _timed(st, alpha, atime, lambda: launch(st.Wt.clone(), 1, torch.empty_like(status)))
         launch(st.Wt, budget, status)
     for k in range(K):
         if grouped[k]:
             continue
         sg = st.seg(k)
         Mk, Vk = Ms[:, sg], st.Wt[:, sg]
-        budget = _budget(st, alpha, atime, lambda: eng.hals_sweeps(Mk, Gs[k], Vk.clone(), 1, normalize=normalize0))
+        budget = _timed(st, alpha, atime, lambda: eng.hals_sweeps(Mk, Gs[k], Vk.clone(), 1, normalize=normalize0))
         eng.hals_solve(Mk, Gs[k], Vk, budget, delta=0.01, normalize=normalize0, status=status[k])
     return status
 
@@ -313,15 +285,15 @@ def _update_D(st, G64, c, HH64, alpha, t0):
     eng, K = st.eng, st.K
     UtU = (G64 * HH64[None]).float().contiguous()
     UtM = c.t().float().contiguous()                                               # r x K
-    atime = _toc(st, t0)
+    atime = _nnls.toc(st.dev, t0)
     status = torch.zeros((K, _engine.ST_WORDS), dtype=torch.float64, device=st.dev)
     if not _per_slice():
-        budget = _budget(st, alpha, atime, lambda: eng.hals_solve_group(UtM, UtU, st.Dt.clone(), st.offK, 1, 1))
+        budget = _timed(st, alpha, atime, lambda: eng.hals_solve_group(UtM, UtU, st.Dt.clone(), st.offK, 1, 1))
         eng.hals_solve_group(UtM, UtU, st.Dt, st.offK, 1, budget, delta=0.01, status=status)
         return status
     for k in range(K):
         Mk, Vk = UtM[:, k:k + 1], st.Dt[:, k:k + 1]
-        budget = _budget(st, alpha, atime, lambda: eng.hals_sweeps(Mk, UtU[k], Vk.clone(), 1))
+        budget = _timed(st, alpha, atime, lambda: eng.hals_sweeps(Mk, UtU[k], Vk.clone(), 1))
         eng.hals_solve(Mk, UtU[k], Vk, budget, delta=0.01, status=status[k])
     return status
 
@@ -365,13 +337,13 @@ def _step(st, mu_in, norm_slices, prev_cost, increasing_mu, tol_mu, step_mu, ini
     Tt = eng.small_gemm(st.Ws.t().contiguous(), st.Pt)                             # targets (P_k W*)^T : r x total
     HH64 = torch.empty((r, r), dtype=torch.float64, device=st.dev)
     need_P = (0 not in fixed_modes) or (2 not in fixed_modes)
-    t0 = _tic(st, alpha)
+    t0 = _nnls.tic(st.dev, alpha)
     P = eng.xht(st.Xs, st.H) if need_P else None                                   # H Xs^T : r x total
     eng.gram(st.H, out64=HH64)
     stW = stD = stH = None
     if 0 not in fixed_modes:
         stW = _update_W(st, mu, P, Tt, HH64, normalize[0], alpha, t0)
-    t0 = _tic(st, alpha)
+    t0 = _nnls.tic(st.dev, alpha)
     G64, c, e = _grams(st, P if 2 not in fixed_modes else None, Tt)
     if 2 not in fixed_modes:
         stD = _update_D(st, G64, c, HH64, alpha, t0)
@@ -380,13 +352,13 @@ def _step(st, mu_in, norm_slices, prev_cost, increasing_mu, tol_mu, step_mu, ini
         st.Dt = torch.where(nrm[:, None] == 0, torch.full_like(st.Dt, 1.0 / K ** 2),
                             (st.Dt.double() / torch.where(nrm == 0, torch.ones_like(nrm), nrm)[:, None]).float()).contiguous()
     if 1 not in fixed_modes:                                                       # p2:566-582
-        t0 = _tic(st, alpha)
+        t0 = _nnls.tic(st.dev, alpha)
         Us = _scaled_W(st)
         UtM = eng.xty(st.Xs, Us)
         d64 = st.Dt.t().double()
         UtU = (d64[:, :, None] * d64[:, None, :] * G64).sum(dim=0).float().contiguous()
-        atime = _toc(st, t0)
-        budget = _budget(st, alpha, atime,
+        atime = _nnls.toc(st.dev, t0)
+        budget = _timed(st, alpha, atime,
                          lambda: eng.hals_sweeps(UtM, UtU, st.H.clone(), 1, sparsity=sparsity, normalize=normalize[1]))
         stH = eng.hals_solve(UtM, UtU, st.H, budget, delta=0.01, sparsity=sparsity, normalize=normalize[1])
     else:

@@ -42,6 +42,37 @@ def sweep_budget(maxiter, alpha, rho):
     return int(max(0, math.floor(lim)))
 
 
+clock = time.time      # every reading of the wall-clock rule goes through this name (tests script it)
+
+
+def tic(dev, alpha=0.5):
+    """Start of a timed bracket: the device is synchronised (a CUDA device only: the CPU engine double has nothing to wait
+    for) and the clock read.  Infinite `alpha`: the rule is off -- nothing is synchronised, nothing read, None."""
+    if math.isinf(alpha):
+        return None
+    if torch.device(dev).type == "cuda":
+        torch.cuda.synchronize(dev)
+    return clock()
+
+
+def toc(dev, t0):
+    """Wall time since `t0 = tic(...)`, after a synchronisation (None stays None)."""
+    return None if t0 is None else tic(dev) - t0
+
+
+def timed_budget(maxiter, alpha, atime, probe, dev):
+    """The wall-clock rule ``cnt <= 1 + alpha*rho`` (nnls.py:155-156,190-194) -> (sweep budget, rho).  rho = atime / btime;
+    `atime`: the time the products took (a tic / toc bracket), btime: the time of `probe()`, which launches one sweep on a
+    scratch copy.  Infinite `alpha` or a falsy `atime`: the reference's rho = 100000 -- no probe, no synchronisation.  (The
+    drivers used to launch the probe for an `atime` of exactly 0 too and drop its timing; it writes a scratch copy only.)"""
+    if math.isinf(alpha) or not atime:
+        return sweep_budget(maxiter, alpha, 100000), 100000
+    t0 = tic(dev)
+    probe()
+    rho = atime / max(toc(dev, t0), 10e-7)
+    return (max(1, sweep_budget(maxiter, alpha, rho)) if maxiter >= 1 else 0), rho
+
+
 def hals_nnls_acc(UtM, UtU, in_V, maxiter=500, atime=None, alpha=0.5, delta=0.01,
                   sparsity_coefficient=None, normalize=False, nonzero=False):
     """Accelerated HALS NNLS (Gillis & Glineur 2012).  See the reference docstring, nnls.py:28-129."""
@@ -80,18 +111,10 @@ def hals_nnls_acc(UtM, UtU, in_V, maxiter=500, atime=None, alpha=0.5, delta=0.01
         if nonzero:
             raise err.ArgumentException("nonzero=True needs UtM, UtU and V of consistent rank.")
 
-    rho = 100000
-    budget = sweep_budget(maxiter, alpha, rho)
-    if atime and not math.isinf(alpha):
-        # probe: wall time of the first sweep (nnls.py:155,190), measured on a scratch copy
-        probe = V.clone()
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        eng.hals_sweeps(M, G, probe, 1, sparsity=sparsity_coefficient, normalize=normalize, nonzero=nonzero)
-        torch.cuda.synchronize(dev)
-        btime = max(time.time() - t0, 10e-7)
-        rho = atime / btime
-        budget = max(1, sweep_budget(maxiter, alpha, rho)) if maxiter >= 1 else 0
+    # probe: wall time of the first sweep (nnls.py:155,190), measured on a scratch copy made before the clock starts
+    scratch = V.clone() if atime and not math.isinf(alpha) else None
+    budget, rho = timed_budget(maxiter, alpha, atime, lambda: eng.hals_sweeps(
+        M, G, scratch, 1, sparsity=sparsity_coefficient, normalize=normalize, nonzero=nonzero), dev)
 
     st = eng.hals_solve(M, G, V, budget, delta=delta, sparsity=sparsity_coefficient, normalize=normalize,
                         nonzero=nonzero)
@@ -150,17 +173,9 @@ def hals_coupling_nnls_acc(UtM, UtU, in_V, Vtarget, mu, maxiter=500, atime=None,
     d.add_(mu)
     d[frozen] = 0.0                                      # rows the reference skips stay skipped (nnls.py:316)
 
-    rho = 100000
-    budget = sweep_budget(maxiter, alpha, rho)
-    if atime and not math.isinf(alpha):
-        probe = V.clone()
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        eng.hals_sweeps(Ms, Gs, probe, 1, normalize=normalize, nonzero=nonzero)
-        torch.cuda.synchronize(dev)
-        btime = max(time.time() - t0, 10e-7)
-        rho = atime / btime
-        budget = max(1, sweep_budget(maxiter, alpha, rho)) if maxiter >= 1 else 0
+    scratch = V.clone() if atime and not math.isinf(alpha) else None
+    budget, rho = timed_budget(maxiter, alpha, atime, lambda: eng.hals_sweeps(
+        Ms, Gs, scratch, 1, normalize=normalize, nonzero=nonzero), dev)
 
     st = eng.hals_solve(Ms, Gs, V, budget, delta=delta, normalize=normalize, nonzero=nonzero).cpu()
     code = int(st[_engine.ST_ERR])
