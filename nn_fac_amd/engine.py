@@ -170,8 +170,15 @@ class Engine:
             raise EngineError("gram_cost: shape / dtype mismatch")
         if UtU_b is not None and (UtU_b.shape != UtU.shape or _ld(UtU_b) != _ld(UtU)):
             raise EngineError("gram_cost: the two Grams of a Hadamard pair must share shape and leading dimension")
+        if UtU64 is not None:
+            # (the kernel reads r x r doubles with row stride r, whatever UtU's leading dimension is)
+            if UtU_b is not None:
+                raise EngineError("gram_cost: UtU64 cannot be combined with a Hadamard pair (UtU_b)")
+            if not torch.is_tensor(UtU64) or UtU64.dtype != torch.float64 or not UtU64.is_contiguous() or UtU64.numel() != r * r \
+                    or UtU64.device != V.device:
+                raise EngineError("gram_cost: UtU64 must be a contiguous float64 device tensor of exactly r*r elements")
         sa, ba = (6e-8, 0.0) if rounding is None else (float(rounding[0]), float(rounding[1]))
-        if UtU64 is not None and UtU_b is None:
+        if UtU64 is not None:
             # the quadratic form on the Gram before its rounding to fp32; rounding[2] = relative rms error of a UtU64 entry
             sg = float(rounding[2]) if rounding is not None and len(rounding) > 2 else 1e-8
             _lib.check(self.lib.nnf_nmf_gram_cost_g64_f32(self.ctx, _ptr(V), _ld(V), _ptr(UtM), _ld(UtM), _ptr(UtU), _ptr(UtU64),
