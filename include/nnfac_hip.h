@@ -65,7 +65,7 @@ typedef struct nnf_ctx nnf_ctx;
 
 int nnf_version(void);
 /* The values the timing-only ablation / A-B switches of the kernel sources were COMPILED with, one "unit: NAME=value ..."
- * entry per translation unit, sorted by unit, separated by "; " (e.g. "k_stream: XHT_ABL=0; ...").  Every switch has a
+ * entry per translation unit, sorted by unit, separated by "; " (e.g. "k_xht: XHT_ABL=0; ...").  Every switch has a
  * product default; a stray -D in a build would silently ship a kernel that skips work, so tests/test_abi_and_host.py
  * compares this string with the defaults.  Writes at most `cap` bytes (NUL-terminated), returns the full length. */
 size_t nnf_build_flags(char* buf, size_t cap);

@@ -1,11 +1,13 @@
 // Fast HALS sweep kernels: one lane = one column of V, column resident in VGPRs, Gram through the scalar cache.
-// Compiled once per -DHALS_PART=0..3 (each part instantiates a subset of padded ranks) so the parts build in parallel.
-// See k_hals.hip for the algorithm, the grid-exchange protocol and the entry points.
+// Compiled once per part, -DHALS_PART=p (k_parts.h; each part instantiates the padded ranks HALS_TABLE gives it), so the parts build
+// in parallel.  See k_hals.hip for the algorithm, the grid-exchange protocol and the entry points.
 #include "k_hals_common.h"
+#include "k_parts.h"
 
 #ifndef HALS_PART
-#error "compile with -DHALS_PART=0..3"
+#error "compile with -DHALS_PART=<part>"
 #endif
+#define NNF_PART HALS_PART
 
 NNF_BUILD_FLAGS(NNF_CAT(k_hals_fast, HALS_PART), "HALS_LATE_ISSUE=" NNF_STR(HALS_LATE_ISSUE) " HALS_MID_AT(R)=" NNF_STR(HALS_MID_AT(R)) " HALS_DBG=" NNF_STR(HALS_DBG))
 
@@ -423,42 +425,36 @@ static int fast_launch(bool res, const hals_args& a, int nblocks, hipStream_t st
     return NNF_OK;
 }
 
-// The instantiations are compiled as four translation units (-DHALS_PART=0..3); part 0 also holds the dispatchers.
-#define HALS_CASE(N, FN, ...) \
-    case N:                   \
-        return FN<N>(__VA_ARGS__);
-#if HALS_PART == 0
-#define HALS_CASES(FN, ...) HALS_CASE(8, FN, __VA_ARGS__) HALS_CASE(16, FN, __VA_ARGS__) HALS_CASE(24, FN, __VA_ARGS__) \
-    HALS_CASE(32, FN, __VA_ARGS__) HALS_CASE(40, FN, __VA_ARGS__) HALS_CASE(48, FN, __VA_ARGS__)
-#elif HALS_PART == 1
-#define HALS_CASES(FN, ...) HALS_CASE(50, FN, __VA_ARGS__) HALS_CASE(52, FN, __VA_ARGS__) HALS_CASE(56, FN, __VA_ARGS__) \
-    HALS_CASE(64, FN, __VA_ARGS__)
-#elif HALS_PART == 2
-#define HALS_CASES(FN, ...) HALS_CASE(80, FN, __VA_ARGS__) HALS_CASE(96, FN, __VA_ARGS__) HALS_CASE(100, FN, __VA_ARGS__) \
-    HALS_CASE(104, FN, __VA_ARGS__)
-#else
-#define HALS_CASES(FN, ...) HALS_CASE(112, FN, __VA_ARGS__) HALS_CASE(128, FN, __VA_ARGS__)
-#endif
+// X(part, padded rank): every instantiation, once (k_parts.h), cut by measured compile time (ranks 100 and 104: 50 CPU-seconds
+// each).  Part 0 also holds the dispatchers.  A kernel's code can depend on what else its unit instantiates (ranks 8 .. 64 in ONE
+// unit: other register allocation in all ten resident-column kernels): compare the kept ISA kernel by kernel after moving an entry.
+#define HALS_TABLE(X)                                                                                            \
+    X(0, 8) X(0, 16) X(0, 24) X(0, 32) X(0, 40) X(0, 48)                                                         \
+    X(1, 50) X(1, 52) X(1, 56) X(1, 64)                                                                          \
+    X(2, 80) X(2, 96)                                                                                            \
+    X(3, 100)                                                                                                    \
+    X(4, 104)                                                                                                    \
+    X(5, 112) X(5, 128)
+NNF_PART_DISPATCHER(fast_mine, HALS_TABLE)
+
 int NNF_CAT(nnf_hals_fast_per_cu_part, HALS_PART)(int RP, bool res) {
-    switch (RP) { HALS_CASES(fast_per_cu, res) default: return 0; }
+    return fast_mine(RP, 0, [&](auto rp) { return fast_per_cu<decltype(rp)::value>(res); });
 }
 int NNF_CAT(nnf_hals_fast_launch_part, HALS_PART)(int RP, bool res, const hals_args& a, int nblocks, hipStream_t st) {
-    switch (RP) { HALS_CASES(fast_launch, res, a, nblocks, st) default: return NNF_ERR_UNSUPPORTED; }
+    return fast_mine(RP, NNF_ERR_UNSUPPORTED, [&](auto rp) { return fast_launch<decltype(rp)::value>(res, a, nblocks, st); });
 }
 
 #if HALS_PART == 0
-int nnf_hals_fast_per_cu_part1(int, bool);
-int nnf_hals_fast_per_cu_part2(int, bool);
-int nnf_hals_fast_per_cu_part3(int, bool);
-int nnf_hals_fast_launch_part1(int, bool, const hals_args&, int, hipStream_t);
-int nnf_hals_fast_launch_part2(int, bool, const hals_args&, int, hipStream_t);
-int nnf_hals_fast_launch_part3(int, bool, const hals_args&, int, hipStream_t);
+#define HALS_DECLARE(p, v)                                      \
+    int NNF_PART_FN(nnf_hals_fast_per_cu_part, p)(int, bool);   \
+    int NNF_PART_FN(nnf_hals_fast_launch_part, p)(int, bool, const hals_args&, int, hipStream_t);
+#define HALS_PER_CU(p, v) case v: return NNF_PART_FN(nnf_hals_fast_per_cu_part, p)(RP, res);
+#define HALS_LAUNCH(p, v) case v: return NNF_PART_FN(nnf_hals_fast_launch_part, p)(RP, res, a, nblocks, st);
+HALS_TABLE(HALS_DECLARE)
 int nnf_hals_fast_per_cu(int RP, bool res) {
-    return RP <= 48 ? nnf_hals_fast_per_cu_part0(RP, res) : RP <= 64 ? nnf_hals_fast_per_cu_part1(RP, res)
-         : RP <= 104 ? nnf_hals_fast_per_cu_part2(RP, res) : nnf_hals_fast_per_cu_part3(RP, res);
+    switch (RP) { HALS_TABLE(HALS_PER_CU) default: return 0; }
 }
 int nnf_hals_fast_launch(int RP, bool res, const hals_args& a, int nblocks, hipStream_t st) {
-    return RP <= 48 ? nnf_hals_fast_launch_part0(RP, res, a, nblocks, st) : RP <= 64 ? nnf_hals_fast_launch_part1(RP, res, a, nblocks, st)
-         : RP <= 104 ? nnf_hals_fast_launch_part2(RP, res, a, nblocks, st) : nnf_hals_fast_launch_part3(RP, res, a, nblocks, st);
+    switch (RP) { HALS_TABLE(HALS_LAUNCH) default: return NNF_ERR_UNSUPPORTED; }
 }
 #endif

@@ -18,6 +18,12 @@
 //     (nnls.py:160), so no per-row guard arithmetic.
 // Stopping rule, lag-one speculation, tagged exchange, fixed-sweep mode and snapshots are those of k_hals_fast.hip.
 #include "k_hals_common.h"
+#include "k_parts.h"
+
+#ifndef QUAD_PART
+#error "compile with -DQUAD_PART=<part>"
+#endif
+#define NNF_PART QUAD_PART
 
 typedef float f32x4q __attribute__((ext_vector_type(4)));
 
@@ -26,7 +32,7 @@ __device__ __forceinline__ float dpp_quad(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
 }
 
-#if !defined(QUAD_PART) || QUAD_PART == 0
+#if QUAD_PART == 0
 // prep: LDS image of the row-scaled Gram.  Row k (k < RQ = 4*CH) is four chunks of CHP = roundup(CH, 4) floats; chunk q holds
 // G'[k][q*CH + jj] = UtU[k][q*CH + jj] / UtU[k][k], jj < CH (0 in the padding, outside r x r and in rows with a zero
 // diagonal).  Then 1/diag per row (0 = skip row), zeroed barrier word and status.
@@ -292,38 +298,19 @@ static int quad_per_cu() {   // workgroups per CU that can be co-resident (all o
     return cached;
 }
 
-// The 32 instantiations are compiled as four translation units (-DQUAD_PART=0..3, like k_hals_fast.hip); each part exports
-// one residency query and one launcher for its range of CH, part 0 also holds the prep kernel's launcher and the dispatchers.
-#define QUAD_CASE(N, FN, ...) \
-    case N:                   \
-        return FN<N>(__VA_ARGS__);
-#ifndef QUAD_PART
-#define QUAD_PART 0
-#endif
+// X(part, CH): every instantiation, once (k_parts.h).  The fully unrolled sweep makes the compile time of an instantiation grow
+// faster than CH^2, so the table is cut by measured compile time, not by count (40 .. 100 CPU-seconds a part): the five largest
+// CH sit alone.  Each part exports one residency query and one launcher; part 0 also holds the prep launcher and the dispatchers.
+#define QUAD_TABLE(X)                                                                                             \
+    X(0, 1) X(0, 2) X(0, 3) X(0, 4) X(0, 5) X(0, 6) X(0, 7) X(0, 8) X(0, 9) X(0, 10) X(0, 11) X(0, 12) X(0, 13)   \
+    X(0, 14) X(0, 15) X(0, 16) X(0, 17) X(0, 18)                                                                  \
+    X(1, 19) X(1, 20) X(1, 21)                                                                                    \
+    X(2, 22) X(2, 23)                                                                                             \
+    X(3, 24) X(3, 25)                                                                                             \
+    X(4, 26) X(4, 27)                                                                                             \
+    X(5, 28) X(6, 29) X(7, 30) X(8, 31) X(9, 32)
+NNF_PART_DISPATCHER(quad_mine, QUAD_TABLE)
 NNF_BUILD_FLAGS(NNF_CAT(k_hals_quad, QUAD_PART), "QUAD_MID_SEL=" NNF_STR(QUAD_MID_SEL) " HALS_LATE_ISSUE=" NNF_STR(HALS_LATE_ISSUE))
-#if QUAD_PART == 0
-#define QUAD_CASES(FN, ...)                                                                                             \
-    QUAD_CASE(1, FN, __VA_ARGS__) QUAD_CASE(2, FN, __VA_ARGS__) QUAD_CASE(3, FN, __VA_ARGS__) QUAD_CASE(4, FN, __VA_ARGS__)     \
-    QUAD_CASE(5, FN, __VA_ARGS__) QUAD_CASE(6, FN, __VA_ARGS__) QUAD_CASE(7, FN, __VA_ARGS__) QUAD_CASE(8, FN, __VA_ARGS__)     \
-    QUAD_CASE(9, FN, __VA_ARGS__) QUAD_CASE(10, FN, __VA_ARGS__) QUAD_CASE(11, FN, __VA_ARGS__) QUAD_CASE(12, FN, __VA_ARGS__)  \
-    QUAD_CASE(13, FN, __VA_ARGS__) QUAD_CASE(14, FN, __VA_ARGS__)
-#define QUAD_PART_FN(name) name##0
-#elif QUAD_PART == 1
-#define QUAD_CASES(FN, ...)                                                                                             \
-    QUAD_CASE(15, FN, __VA_ARGS__) QUAD_CASE(16, FN, __VA_ARGS__) QUAD_CASE(17, FN, __VA_ARGS__) QUAD_CASE(18, FN, __VA_ARGS__) \
-    QUAD_CASE(19, FN, __VA_ARGS__) QUAD_CASE(20, FN, __VA_ARGS__) QUAD_CASE(21, FN, __VA_ARGS__)
-#define QUAD_PART_FN(name) name##1
-#elif QUAD_PART == 2
-#define QUAD_CASES(FN, ...)                                                                                             \
-    QUAD_CASE(22, FN, __VA_ARGS__) QUAD_CASE(23, FN, __VA_ARGS__) QUAD_CASE(24, FN, __VA_ARGS__) QUAD_CASE(25, FN, __VA_ARGS__) \
-    QUAD_CASE(26, FN, __VA_ARGS__) QUAD_CASE(27, FN, __VA_ARGS__)
-#define QUAD_PART_FN(name) name##2
-#else
-#define QUAD_CASES(FN, ...)                                                                                             \
-    QUAD_CASE(28, FN, __VA_ARGS__) QUAD_CASE(29, FN, __VA_ARGS__) QUAD_CASE(30, FN, __VA_ARGS__) QUAD_CASE(31, FN, __VA_ARGS__) \
-    QUAD_CASE(32, FN, __VA_ARGS__)
-#define QUAD_PART_FN(name) name##3
-#endif
 
 template <int CH>
 static int quad_launch(const hals_args& a, int nblocks, hipStream_t st) {
@@ -331,23 +318,22 @@ static int quad_launch(const hals_args& a, int nblocks, hipStream_t st) {
     NNF_CHECK_LAUNCH();
     return NNF_OK;
 }
-int QUAD_PART_FN(nnf_hals_quad_per_cu_part)(int ch) {
-    switch (ch) { QUAD_CASES(quad_per_cu) default: return 0; }
+int NNF_CAT(nnf_hals_quad_per_cu_part, QUAD_PART)(int ch) {
+    return quad_mine(ch, 0, [](auto c) { return quad_per_cu<decltype(c)::value>(); });
 }
-int QUAD_PART_FN(nnf_hals_quad_launch_part)(int ch, const hals_args& a, int nblocks, hipStream_t st) {
-    switch (ch) { QUAD_CASES(quad_launch, a, nblocks, st) default: return NNF_ERR_UNSUPPORTED; }
+int NNF_CAT(nnf_hals_quad_launch_part, QUAD_PART)(int ch, const hals_args& a, int nblocks, hipStream_t st) {
+    return quad_mine(ch, NNF_ERR_UNSUPPORTED, [&](auto c) { return quad_launch<decltype(c)::value>(a, nblocks, st); });
 }
 
 #if QUAD_PART == 0
-int nnf_hals_quad_per_cu_part1(int);
-int nnf_hals_quad_per_cu_part2(int);
-int nnf_hals_quad_per_cu_part3(int);
-int nnf_hals_quad_launch_part1(int, const hals_args&, int, hipStream_t);
-int nnf_hals_quad_launch_part2(int, const hals_args&, int, hipStream_t);
-int nnf_hals_quad_launch_part3(int, const hals_args&, int, hipStream_t);
+#define QUAD_DECLARE(p, v)                                \
+    int NNF_PART_FN(nnf_hals_quad_per_cu_part, p)(int);   \
+    int NNF_PART_FN(nnf_hals_quad_launch_part, p)(int, const hals_args&, int, hipStream_t);
+#define QUAD_PER_CU(p, v) case v: return NNF_PART_FN(nnf_hals_quad_per_cu_part, p)(ch);
+#define QUAD_LAUNCH(p, v) case v: return NNF_PART_FN(nnf_hals_quad_launch_part, p)(ch, a, nblocks, st);
+QUAD_TABLE(QUAD_DECLARE)
 int nnf_hals_quad_per_cu(int ch) {
-    return ch <= 14 ? nnf_hals_quad_per_cu_part0(ch) : ch <= 21 ? nnf_hals_quad_per_cu_part1(ch)
-         : ch <= 27 ? nnf_hals_quad_per_cu_part2(ch) : nnf_hals_quad_per_cu_part3(ch);
+    switch (ch) { QUAD_TABLE(QUAD_PER_CU) default: return 0; }
 }
 
 // Gq: workspace of nnf_hals_quad_gram_floats(r) floats (the row-scaled Gram image, then 1/diag per row)
@@ -363,7 +349,6 @@ int nnf_hals_quad_prep(const float* UtU, const float* UtU2, int64_t ldg, int r, 
 int nnf_hals_quad_launch(int ch, hals_args a, float* Gq, int nblocks, hipStream_t st) {
     a.Gp = Gq;
     a.dinv = Gq + (size_t)(4 * ch) * (4 * ((ch + 3) & ~3));
-    return ch <= 14 ? nnf_hals_quad_launch_part0(ch, a, nblocks, st) : ch <= 21 ? nnf_hals_quad_launch_part1(ch, a, nblocks, st)
-         : ch <= 27 ? nnf_hals_quad_launch_part2(ch, a, nblocks, st) : nnf_hals_quad_launch_part3(ch, a, nblocks, st);
+    switch (ch) { QUAD_TABLE(QUAD_LAUNCH) default: return NNF_ERR_UNSUPPORTED; }
 }
 #endif   // QUAD_PART == 0

@@ -9,7 +9,7 @@
 //            -> both are "V X^T"-shaped (reduction along the contiguous axis): one segmented kernel, split over segments
 //   mode 2:  out[r][k] = sum_{i,j} T[i][j][k] F0t[r][i] F1t[r][j]     T seen as an (I*J) x K matrix, reduction over rows
 //            -> "W^T X"-shaped, split over rows
-// Same MFMA / buffer-load / fragment-order machinery as k_stream.hip; partial slabs are summed in fp64 in a fixed order.
+// Same MFMA / buffer-load / fragment-order machinery as k_xty.hip (k_stream_common.h); partial slabs are summed in fp64 in a fixed order.
 // unfold/khatri_rao index conventions follow tensorly 0.6.0 (first remaining mode slowest), see SURVEY.md appendix B.
 #include "k_stream_common.h"
 #ifndef SEG_ABL
@@ -415,32 +415,25 @@ static int launch_rows(nnf_ctx* ctx, const float* M, int64_t m, int64_t n, const
     return nnf_launch_reduce_slabs(slabs, nsplit, slab_elems, r, n, ldp, out, ldo, st);
 }
 
-#define MTTKRP_MT(FN, VEC, ...)                       \
-    switch (MT) {                                     \
-        case 1: return FN<1, VEC>(__VA_ARGS__);       \
-        case 2: return FN<2, VEC>(__VA_ARGS__);       \
-        case 3: return FN<3, VEC>(__VA_ARGS__);       \
-        case 4: return FN<4, VEC>(__VA_ARGS__);       \
-        case 5: return FN<5, VEC>(__VA_ARGS__);       \
-        case 6: return FN<6, VEC>(__VA_ARGS__);       \
-        case 7: return FN<7, VEC>(__VA_ARGS__);       \
-        default: return FN<8, VEC>(__VA_ARGS__);      \
-    }
-
 static int seg_dispatch(nnf_ctx* ctx, const float* T, int64_t nrows, int64_t ldrow, int64_t nseg, int64_t segstride,
                         int64_t klen, const float* Fs, int64_t lds_, const float* Fk, int64_t ldk, int R, float* out,
                         int64_t ldo, hipStream_t st) {
-    const int MT = (R + 15) / 16;
     const bool vec = x_vec_ok(T, ldrow) && segstride % 4 == 0;
-    if (vec) { MTTKRP_MT(launch_seg, true, ctx, T, nrows, ldrow, nseg, segstride, klen, Fs, lds_, Fk, ldk, R, out, ldo, st) }
-    else { MTTKRP_MT(launch_seg, false, ctx, T, nrows, ldrow, nseg, segstride, klen, Fs, lds_, Fk, ldk, R, out, ldo, st) }
+    return nnf_dispatch<8>((R + 15) / 16, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        return vec ? launch_seg<MT, true>(ctx, T, nrows, ldrow, nseg, segstride, klen, Fs, lds_, Fk, ldk, R, out, ldo, st)
+                   : launch_seg<MT, false>(ctx, T, nrows, ldrow, nseg, segstride, klen, Fs, lds_, Fk, ldk, R, out, ldo, st);
+    });
 }
 
 static int rows_dispatch(nnf_ctx* ctx, const float* M, int64_t m, int64_t n, const float* Fa, int64_t lda,
                          const float* Fb, int64_t ldb, int64_t nb, int R, float* out, int64_t ldo, hipStream_t st) {
-    const int MT = (R + 15) / 16;
-    if (x_vec_ok(M, n)) { MTTKRP_MT(launch_rows, true, ctx, M, m, n, Fa, lda, Fb, ldb, nb, R, out, ldo, st) }
-    else { MTTKRP_MT(launch_rows, false, ctx, M, m, n, Fa, lda, Fb, ldb, nb, R, out, ldo, st) }
+    const bool vec = x_vec_ok(M, n);
+    return nnf_dispatch<8>((R + 15) / 16, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        return vec ? launch_rows<MT, true>(ctx, M, m, n, Fa, lda, Fb, ldb, nb, R, out, ldo, st)
+                   : launch_rows<MT, false>(ctx, M, m, n, Fa, lda, Fb, ldb, nb, R, out, ldo, st);
+    });
 }
 
 extern "C" int nnf_mttkrp3_f32(nnf_ctx* ctx, const float* T, int64_t I, int64_t J, int64_t K, const float* Ft0,
@@ -452,13 +445,11 @@ extern "C" int nnf_mttkrp3_f32(nnf_ctx* ctx, const float* T, int64_t I, int64_t 
     if (R > NNF_MAX_RANK) {
         // ranks above 128: the rank rows of the result are independent of each other -- passes of <= 128 rows of the three
         // transposed factors (the tensor is read once per pass)
-        for (int k0 = 0; k0 < R; k0 += NNF_MAX_RANK) {
-            const int rc = nnf_mttkrp3_f32(ctx, T, I, J, K, Ft0 + (int64_t)k0 * ld0, ld0, Ft1 + (int64_t)k0 * ld1, ld1,
-                                           Ft2 + (int64_t)k0 * ld2, ld2, R - k0 < NNF_MAX_RANK ? R - k0 : NNF_MAX_RANK, mode,
-                                           out + (int64_t)k0 * ldo, ldo, stream);
-            if (rc != NNF_OK) return rc;
-        }
-        return NNF_OK;
+        nnf_ws_cursor cur(ctx);
+        return nnf_rank_passes(R, cur, [&](int k0, int rc) {
+            return nnf_mttkrp3_f32(ctx, T, I, J, K, Ft0 + (int64_t)k0 * ld0, ld0, Ft1 + (int64_t)k0 * ld1, ld1, Ft2 + (int64_t)k0 * ld2, ld2,
+                                   rc, mode, out + (int64_t)k0 * ldo, ldo, stream);
+        });
     }
     hipStream_t st = (hipStream_t)stream;
     if (mode == 0) {
@@ -547,13 +538,11 @@ extern "C" int nnf_mttkrp3_from_partial_f32(nnf_ctx* ctx, const float* Y, int64_
     if (!ctx || !Y || !Ft || !out || A < 1 || B < 1 || R < 1 || (axis != 1 && axis != 2)) return NNF_ERR_ARG;
     if (ldf < (axis == 1 ? A : B) || ldo < (axis == 1 ? B : A)) return NNF_ERR_ARG;
     if (R > NNF_MAX_RANK) {   // R independent matrix-vector products: passes of <= 128 of them
-        for (int k0 = 0; k0 < R; k0 += NNF_MAX_RANK) {
-            const int rc = nnf_mttkrp3_from_partial_f32(ctx, Y + (int64_t)k0 * A * B, A, B, Ft + (int64_t)k0 * ldf, ldf,
-                                                        R - k0 < NNF_MAX_RANK ? R - k0 : NNF_MAX_RANK, axis, out + (int64_t)k0 * ldo,
-                                                        ldo, stream);
-            if (rc != NNF_OK) return rc;
-        }
-        return NNF_OK;
+        nnf_ws_cursor cur(ctx);
+        return nnf_rank_passes(R, cur, [&](int k0, int rc) {
+            return nnf_mttkrp3_from_partial_f32(ctx, Y + (int64_t)k0 * A * B, A, B, Ft + (int64_t)k0 * ldf, ldf, rc, axis,
+                                                out + (int64_t)k0 * ldo, ldo, stream);
+        });
     }
     hipStream_t st = (hipStream_t)stream;
     if (axis == 2) {

@@ -2,7 +2,7 @@
 // gradient update of the (small) core tensor as ONE single-workgroup launch.
 //
 //   nnf_ttm3_f32    out = T x_mode F^T   (tl.tenalg.mode_dot(T, F.T, mode), the building block of ntd.py:550,581)
-//       mode 0: T viewed as I x (J*K), first axis contracted   -> the W^T X kernel (k_stream.hip), out[r][J][K]
+//       mode 0: T viewed as I x (J*K), first axis contracted   -> the W^T X kernel (k_xty.hip), out[r][J][K]
 //       mode 2: T viewed as (I*J) x K, last axis contracted     -> the X H^T kernel,                out[r][I][J]
 //       mode 1: middle axis, per slab i: out[i][r][K] = F^T T_i -> nnf_ttm_mid_kernel below (VALU, factor row in SGPRs)
 //     The two big cases stream T once with the MFMA kernels; the new axis comes out FIRST (row-major [r][rest]) so the

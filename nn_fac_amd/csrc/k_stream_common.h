@@ -1,4 +1,26 @@
-// Device helpers shared by the streaming MFMA kernels (k_stream.hip, k_mu.hip, k_mttkrp.hip).
+// Streaming fp32-MFMA contractions over the data matrix X (gfx950 / CDNA4, wave64), and the device helpers they share with
+// k_mu.hip and k_mttkrp.hip.
+//
+//   xty : out[r x n] = Ut[r x m] * X[m x n]          ("W^T X",  nmf.py:433)   split over m, slab reduce     k_xty.hip
+//   xht : out[r x m] = V [r x n] * X[m x n]^T        ("X H^T",  nmf.py:408)                                 k_xht.hip, k_xht_lds.hip
+//   gram: G  [r x r] = A [r x K] * A^T               (nmf.py:407,432; ntf.py:442-445)                       k_gram.hip
+//   cost: sum f(X, Ut^T V)                           (nmf.py:452,455; beta_divergence.py:45-52) product never materialised   k_cost.hip
+//   (the slab and partial sums behind them: k_reduce.hip)
+//
+// Common design
+//   * v_mfma_f32_16x16x4_f32 (exact fp32, 32 cycles/issue/SIMD; MI355X_MICROARCH "Matrix cores").  The 16-granular M tile
+//     keeps rank padding small (r=50 -> 64).  Operand lane maps (cdna_hip_programming.md s.3):
+//       A[row = l&15][k = l>>4],  B[k = l>>4][col = l&15],  D[row = 4*(l>>4)+reg][col = l&15].
+//   * X is read ONCE per kernel, straight from HBM into VGPRs with 16-byte buffer loads whose four components feed
+//     four different MFMAs, so no LDS round trip for the streamed operand: for xty/frob a wave instruction covers
+//     4 rows x 256 contiguous bytes; the column a lane holds in component c is 4*(l&15)+c, i.e. the four N tiles of a
+//     wave are column-interleaved (a pure relabelling, undone in the epilogue's float4 stores).
+//   * The small operand (Ut / V tile) is staged once per workgroup into LDS in *fragment order*
+//     ([tile][k-group][lane] float4) so every fragment read is one conflict-free linear ds_read_b128.
+//   * Hardware bounds checking of the buffer descriptor (num_records) zero-fills rows past the end of a workgroup's
+//     row range; ragged k tails are masked with selects (never 0*garbage).
+//   * Register double buffering: the loads of the next 64-deep chunk are issued right after the MFMAs that free the
+//     registers, so ~16 KB per wave stay in flight (hipcc's in-order vmcnt bookkeeping keeps them counted).
 #pragma once
 #include "nnf_internal.h"
 #include <type_traits>
@@ -163,8 +185,6 @@ __device__ __forceinline__ void stageK_bload(const mu_stage& s, int64_t K, int64
         regs[s4] = v;
     }
 }
-
-
 
 static inline bool x_vec_ok(const float* X, int64_t ldx) { return (((uintptr_t)X) & 15) == 0 && (ldx & 3) == 0; }
 

@@ -1,4 +1,4 @@
-// Launch plans of the streaming and MTTKRP launchers (k_stream.hip: W^T X, X H^T, the Gram, the cost pass; k_xht_lds.hip;
+// Launch plans of the streaming and MTTKRP launchers (k_xty.hip, k_xht.hip, k_gram.hip, k_cost.hip: W^T X, X H^T, the Gram, the cost pass; k_xht_lds.hip;
 // k_mttkrp.hip: the segment and rows kernels, the two dimension-tree contractions; k_mu_plan.h builds on them):
 // what a call will launch, decided from sizes alone before anything is carved from the workspace or launched, and the
 // NNF_PLAN_DEBUG line that reports it (every "[nnf plan]" line of the library is formatted in these two headers).  No HIP in here: tools/nnf_plan.cpp is a plain host program that prints the same plans

@@ -1,0 +1,233 @@
+// X H^T: out[r x m] = V[r x n] * X[m x n]^T  (nmf.py:408) with the fragments of X loaded straight into registers; ranks up to
+// 32 go to the LDS-staged form of k_xht_lds.hip.  The design shared with W^T X, the Gram and the cost pass is described at the
+// head of k_stream_common.h.
+#include "k_stream_common.h"
+#ifndef XHT_ABL
+#define XHT_ABL 0   // timing-only ablations of nnf_xht_kernel (tools/xht_ablate.sh); 0 = the product
+#endif
+NNF_BUILD_FLAGS(k_xht, "XHT_ABL=" NNF_STR(XHT_ABL))
+
+// =========================================================================================================
+// xht: out[rk][i] = sum_j V[rk][j] * X[i][j]
+//   workgroup = 256 rows of X (wave w: rows 64w..64w+63 as four 16-row N tiles), k runs over the n columns.
+//   B operand lane (ii = l&15, g = l>>4) of tile nt, k-group t: float4 X[i0w+16nt+ii][64q+16t+4g .. +3].
+// =========================================================================================================
+// NT = 16-row tiles per wave (a workgroup covers 64*NT rows starting at row0).
+template <int MT, int REM, bool VEC, int NT>
+__device__ __forceinline__ void nnf_xht_body(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+                                             const float* __restrict__ V, int64_t ldv, int r, float* __restrict__ out,
+                                             int64_t ldo, int a_vec_ok, int64_t row0, f32x4 (*ldsA)[(MT + (REM > 0 ? 1 : 0)) * 256],
+                                             int q0 = 0, int q1 = -1, int64_t oshift = 0) {
+    // [q0, q1): the 64-column chunks this call contracts (default: all of them; a sub-range = a k-split share, see the kernel);
+    // row i of the result goes to column i - oshift of `out` (a share's slab starts at the first k-split row)
+    constexpr int MTA = MT + (REM > 0 ? 1 : 0);
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ii = lane & 15, g = lane >> 4;
+    const int64_t i0w = row0 + 16 * NT * w;
+    int64_t rows = m - i0w;
+    if (rows > 16 * NT) rows = 16 * NT;
+    const uint32_t bytes = rows > 0 ? (uint32_t)(((rows - 1) * ldx + n) * 4) : 0u;
+    const rsrc_t rs = nnf_make_rsrc(X + (rows > 0 ? i0w : 0) * ldx, bytes);
+    const int voff = (int)(((int64_t)ii * ldx + 4 * g) * 4);
+    const int ldx4 = (int)(ldx * 4);
+    const int nchunk = q1 >= 0 ? q1 : (int)((n + 63) >> 6);
+
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 xb[4][NT];  // [k-group t][row tile nt]
+    f32x4 areg[MTA];
+    float ev[REM > 0 ? REM : 1][NT];   // leftover rank rows x the 16-row tiles: partial over this lane's k
+#pragma unroll
+    for (int rr = 0; rr < (REM > 0 ? REM : 1); ++rr)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) ev[rr][nt] = 0.f;
+
+    stageA_load<MTA>(V, ldv, r, n, 64 * (int64_t)q0, a_vec_ok, areg);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) xb[t][nt] = nnf_bload4<VEC>(rs, voff, nt * 16 * ldx4 + 256 * q0 + 64 * t);
+    stageA_store<MTA>(ldsA[q0 & 1], areg);
+    __syncthreads();
+
+    for (int q = q0; q < nchunk; ++q) {
+        const f32x4* img = ldsA[q & 1];
+        stageA_load<MTA>(V, ldv, r, n, 64 * (int64_t)(q + 1), a_vec_ok, areg);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            f32x4 af[MT];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) af[mt] = img[(mt * 4 + t) * 64 + lane];
+            // ragged k tail: never multiply a staged zero by out-of-row data
+#if XHT_ABL != 5
+            const int64_t nrem = n - (64 * (int64_t)q + 16 * t + 4 * g);
+            if (nrem < 4) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (c >= nrem) xb[t][nt][c] = 0.f;
+            }
+#endif
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+#if XHT_ABL == 2
+                        if (mt == 0) acc[0][nt][c] += af[0][c] * xb[t][nt][c];
+#else
+                        acc[mt][nt] = MFMA16(af[mt][c], xb[t][nt][c], acc[mt][nt]);
+#endif
+                    }
+            if constexpr (REM > 0 && XHT_ABL != 3) {
+#pragma unroll
+                for (int rr = 0; rr < REM; ++rr) {
+                    const f32x4 uv = img[(MT * 4 + t) * 64 + 16 * g + rr];   // V[16MT+rr][64q+16t+4g+c], c = 0..3
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        float e = ev[rr][nt];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) e = fmaf(uv[c], xb[t][nt][c], e);
+                        ev[rr][nt] = e;
+                    }
+                }
+            }
+#if XHT_ABL != 1
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+                xb[t][nt] = nnf_bload4<VEC>(rs, voff, nt * 16 * ldx4 + 256 * (q + 1) + 64 * t);
+#endif
+        }
+#if XHT_ABL != 4
+        stageA_store<MTA>(const_cast<f32x4*>(ldsA[(q + 1) & 1]), areg);
+        __syncthreads();
+#endif
+    }
+
+    // epilogue: tile (mt, nt): out[16mt + 4g + reg][i0w + 16nt + ii]
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int64_t i = i0w + 16 * nt + ii;
+        if (i < m) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int rk = 16 * mt + 4 * g + reg;
+                    if (rk < r) out[(int64_t)rk * ldo + (i - oshift)] = acc[mt][nt][reg];
+                }
+        }
+    }
+    if constexpr (REM > 0) {
+#pragma unroll
+        for (int rr = 0; rr < REM; ++rr)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                float x = ev[rr][nt];
+                x += __shfl_xor(x, 16, 64);
+                x += __shfl_xor(x, 32, 64);
+                const int64_t i = i0w + 16 * nt + ii;
+                const int rk = 16 * MT + rr;
+                if (g == 0 && rk < r && i < m) out[(int64_t)rk * ldo + (i - oshift)] = x;
+            }
+    }
+}
+
+// A resident wave is the unit the MFMA pipe is shared in, and one round of workgroups covers B's 100000 rows: with
+// 64 rows per wave everywhere that is 1563 waves on 1024 SIMDs -- the SIMDs holding two of them decide the time
+// (8 row tiles against 6.1 on average).  The first n_hi workgroups take NTH tiles per wave, the others NTH-1, chosen
+// on the host so that one full round of resident workgroups covers the matrix (7 tiles on the busiest SIMD).
+template <int MT, int REM, bool VEC, int NTH>
+__global__ __launch_bounds__(256, (MT + (REM > 0) <= 4 || NTH <= 2 ? 2 : 1)) void nnf_xht_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+                                                         const float* __restrict__ V, int64_t ldv, int r,
+                                                         float* __restrict__ out, int64_t ldo, int a_vec_ok, int n_hi,
+                                                         float* __restrict__ tail_slabs, int64_t tail_row0, int64_t tail_ld,
+                                                         int tail_tiles, int tail_parts, int tail_cpp) {
+    constexpr int MTA = MT + (REM > 0 ? 1 : 0);
+    __shared__ f32x4 ldsA[2][MTA * 256];
+    const int b = (int)blockIdx.x;
+    if (b < n_hi)
+        nnf_xht_body<MT, REM, VEC, NTH>(X, m, n, ldx, V, ldv, r, out, ldo, a_vec_ok, (int64_t)b * (64 * NTH), ldsA);
+    else
+        nnf_xht_body<MT, REM, VEC, NTH - 1>(X, m, n, ldx, V, ldv, r, out, ldo, a_vec_ok,
+                                            (int64_t)n_hi * (64 * NTH) + (int64_t)(b - n_hi) * (64 * (NTH - 1)), ldsA);
+    // k-split tail (launch_xht): the row tiles that do not fill another whole round -- 106 of config B's 6250 -- are shared by ALL
+    // workgroups instead of making 27 of them a third longer: workgroup b takes chunk share p = b % parts of the four tiles
+    // 4 (b / parts) + wave, into slab p; the shares are added in share order by the usual slab reduction.
+    if (tail_parts > 0) {
+        const int p = b % tail_parts, tg = b / tail_parts;
+        if (4 * tg < tail_tiles) {
+            __syncthreads();
+            const int nchunk_all = (int)((n + 63) >> 6);
+            const int q0 = p * tail_cpp, q1 = (q0 + tail_cpp < nchunk_all) ? q0 + tail_cpp : nchunk_all;
+            nnf_xht_body<MT, REM, VEC, 1>(X, m, n, ldx, V, ldv, r, tail_slabs + (int64_t)p * r * tail_ld, tail_ld, a_vec_ok,
+                                          tail_row0 + 64 * (int64_t)tg, ldsA, q0 < q1 ? q0 : q1, q1, tail_row0);
+        }
+    }
+}
+
+template <int MT, int REM, bool VEC>
+static int launch_xht(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r, int64_t ldv,
+                      float* out, int64_t ldo, hipStream_t st) {
+    if (!nnf_xht_offsets_ok(n, ldx)) return NNF_ERR_UNSUPPORTED;
+    static const int nt2 = [] { const char* e = getenv("NNF_XHT_NT2"); return e ? atoi(e) : -1; }();
+    static const int tail_on = [] { const char* e = getenv("NNF_XHT_TAIL"); return e ? atoi(e) : 1; }();
+    const nnf_xht_plan pl = nnf_plan_xht_direct(ctx->num_cus, m, n, r, nnf_rank_tiles{MT, REM}, nt2, tail_on, cur.remaining());
+    if (!pl.covers(m)) return NNF_ERR_UNSUPPORTED;   // (cannot happen: the split covers m by construction)
+    if (nnf_plan_debug()) nnf_report_xht(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, false, pl);
+    float* tail_slabs = pl.tail_parts > 0 ? (float*)cur.take((size_t)pl.tail_parts * r * pl.tail_ld * 4) : nullptr;
+    if (pl.tail_parts > 0 && !tail_slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
+    const int a_vec_ok = x_vec_ok(V, ldv) ? 1 : 0;
+    nnf_probe(ctx, NNF_PROBE_XHT, 0, st);
+#define NNF_XHT_GO(NTH)                                                                                                          \
+    hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, NTH>), dim3((int)pl.grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo, \
+                       a_vec_ok, (int)pl.n_hi, tail_slabs, pl.tail_row0, pl.tail_ld, pl.tail_tiles, pl.tail_parts, pl.tail_cpp)
+    if (pl.nth == 4) NNF_XHT_GO(4);
+    else if (pl.nth == 2) {
+        if constexpr (MT + (REM > 0) > 4) NNF_XHT_GO(2);
+    } else NNF_XHT_GO(3);
+#undef NNF_XHT_GO
+    NNF_CHECK_LAUNCH();
+    nnf_probe(ctx, NNF_PROBE_XHT, 1, st);
+    if (pl.tail_parts > 0)    // the k-split shares of the last rows, added in share order
+        return nnf_launch_reduce_slabs(tail_slabs, pl.tail_parts, (int64_t)r * pl.tail_ld, r, m - pl.tail_row0, pl.tail_ld,
+                                       out + pl.tail_row0, ldo, st);
+    return NNF_OK;
+}
+
+int nnf_xht_lds_launch(nnf_ctx* ctx, int MT, int REM, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r,
+                       int64_t ldv, float* out, int64_t ldo, hipStream_t st);   // k_xht_lds.hip
+int nnf_xht_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V,
+                 int r, int64_t ldv, float* out, int64_t ldo, hipStream_t st) {
+    if (!ctx || !X || !V || !out || m < 1 || n < 1 || r < 1 || ldx < n || ldv < n || ldo < m) return NNF_ERR_ARG;
+    if (r > NNF_MAX_RANK)   // the rows of the result are independent of each other
+        return nnf_rank_passes(r, cur, [&](int k0, int rc) {
+            return nnf_xht_impl(ctx, cur, X, m, n, ldx, V + (int64_t)k0 * ldv, rc, ldv, out + (int64_t)k0 * ldo, ldo, st);
+        });
+    const bool vec = x_vec_ok(X, ldx);
+    const nnf_rank_tiles t = nnf_xht_tiles(r, vec);
+    const char* pick = getenv("NNF_XHT");       // measurement knob: "direct" keeps the register-fragment kernel
+    if (nnf_xht_use_lds(t, vec) && !(pick && pick[0] == 'd'))
+        return nnf_xht_lds_launch(ctx, t.MT, t.REM, X, m, n, ldx, V, r, ldv, out, ldo, st);
+    return nnf_dispatch<8>(t.MT, [&](auto mt) -> int {
+        constexpr int MT = decltype(mt)::value;
+        const auto go = [&](auto rem, auto v) {
+            return launch_xht<MT, decltype(rem)::value, decltype(v)::value>(ctx, cur, X, m, n, ldx, V, r, ldv, out, ldo, st);
+        };
+        if (!vec) return go(nnf_int<0>{}, std::false_type{});
+        if (t.REM == 2) return go(nnf_int<2>{}, std::true_type{});
+        if (t.REM == 4) return go(nnf_int<4>{}, std::true_type{});
+        return go(nnf_int<0>{}, std::true_type{});
+    });
+}
+extern "C" int nnf_xht_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r,
+                           int64_t ldv, float* out, int64_t ldo, void* stream) {
+    if (!ctx) return NNF_ERR_ARG;
+    nnf_ws_cursor cur(ctx);
+    return nnf_xht_impl(ctx, cur, X, m, n, ldx, V, r, ldv, out, ldo, (hipStream_t)stream);
+}

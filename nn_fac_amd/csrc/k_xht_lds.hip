@@ -1,7 +1,7 @@
 // X H^T with the X tile staged through LDS in whole 256-byte row pieces (nmf.py:408, ntd.py / ntf.py mode products along the
 // contiguous axis):   out[rk][i] = sum_j V[rk][j] * X[i][j]
 //
-// nnf_xht_kernel (k_stream.hip) loads the MFMA B fragments of X straight into registers: a wave instruction then reads 16 rows x
+// nnf_xht_kernel (k_xht.hip) loads the MFMA B fragments of X straight into registers: a wave instruction then reads 16 rows x
 // 64 bytes -- half a cache line per row -- and that access shape itself tops out near 3.5 TB/s (DESIGN_HISTORY.md, segment
 // MTTKRP ablation; the guide's "fragment-shaped loads": the texture path is busy twice as long for the same bytes).  Here a
 // wave instruction reads 4 rows x 256 contiguous bytes, the wave parks the 64-row x 64-column piece in ITS OWN 16 KB of LDS

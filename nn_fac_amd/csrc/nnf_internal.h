@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include "../../include/nnfac_hip.h"
 #include "k_mu_plan.h"   // the host-only launch plans (k_stream_plan.h, k_mu_plan.h): sizes in, plan out, no HIP
+#include "k_dispatch.h"  // run-time count -> template argument, rank passes: no HIP either
 
 struct nnf_ctx {
     int device;

@@ -883,7 +883,7 @@ def get_engine(device=None):
         e = _engines.get(dev.index)
         if e is None:
             # 1 GiB of scratch for the main context (NNF_WORKSPACE_MB overrides): the split-K slabs of W^T X at 10^6 x 4000 rank
-            # 100 are 780 MB when a workgroup sums at most 2048 rows in fp32 (k_stream.hip: launch_xty) -- with the C default of
+            # 100 are 780 MB when a workgroup sums at most 2048 rows in fp32 (k_xty.hip: launch_xty) -- with the C default of
             # 256 MiB the plan falls back to longer chains.  Side contexts keep the default.
             mb = int(os.environ.get("NNF_WORKSPACE_MB", "1024"))
             e = Engine(dev, workspace_bytes=mb << 20)

@@ -10,6 +10,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _tool(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def _declared_symbols():
     txt = open(os.path.join(ROOT, "include", "nnfac_hip.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
@@ -46,9 +54,11 @@ def test_built_library_carries_the_default_build_switches(built_lib):
     hals = "HALS_LATE_ISSUE=1 HALS_MID_AT(R)=((R) - 1) HALS_DBG=0"
     quad = "QUAD_MID_SEL=1 HALS_LATE_ISSUE=1"
     mu = "MU_WG_PER_CU=2 MU_STEP_FENCE()=__builtin_amdgcn_sched_barrier(0)"
-    want = {"k_stream": "XHT_ABL=0 XTY_BIG_WG=2", "k_mttkrp": "SEG_ABL=0 MTTKRP_ABL=0", "k_hals_wave": "WAVE_DBG=0 WAVE_REFRESH_V=8",
+    parts = _tool("check_sweep_spills").parts            # the part lists of the Makefile: the one place that names them
+    assert len(parts("FAST")) >= 4 and len(parts("QUAD")) >= 4
+    want = {"k_xht": "XHT_ABL=0", "k_xty": "XTY_BIG_WG=2", "k_mttkrp": "SEG_ABL=0 MTTKRP_ABL=0", "k_hals_wave": "WAVE_DBG=0 WAVE_REFRESH_V=8",
             "k_hals_mfma": "MFMA_NREF_V=32 MFMA_EARLY=1 MFMA_DBG=0",
-            **{f"k_hals_fast{i}": hals for i in range(4)}, **{f"k_hals_quad{i}": quad for i in range(4)},
+            **{f"k_hals_fast{i}": hals for i in parts("FAST")}, **{f"k_hals_quad{i}": quad for i in parts("QUAD")},
             **{f"k_mu{i}": mu for i in range(3)}}
     for unit, flags in want.items():
         assert got.get(unit) == flags, (unit, got.get(unit))
@@ -139,27 +149,20 @@ def test_sweep_kernels_never_touch_a_load_destination_before_its_wait(built_lib)
     SGPRs; k_hals_quad: hand-issued ds_read_b128 into VGPRs): no instruction of a sweep block may name a register with such a
     load in flight before the wait that covers it -- the abort class of round 1 (a rank instantiation over the SGPR budget
     made the allocator move an in-flight buffer).  Runs in seconds after `make`; compiles to assembly otherwise."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("check_sweep_spills", os.path.join(ROOT, "tools", "check_sweep_spills.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    bad, blocks = mod.check_all()
+    bad, blocks = _tool("check_sweep_spills").check_all()   # (asserts that every CH 1 .. 32 and every padded rank was seen)
     assert blocks >= 60, blocks          # every rank instantiation of both kernels was seen
     assert not bad, bad[:3]
 
 
 def test_streaming_kernels_keep_their_prefetch_ring_in_flight(built_lib):
-    """tools/check_loop_drains.py on the ISA the build kept for k_stream / k_mttkrp: the chunk loops of the streaming MFMA
+    """tools/check_loop_drains.py on the ISA the build kept for k_xty / k_xht / k_mttkrp: the chunk loops of the streaming MFMA
     kernels of the BASELINE configurations hold no `s_waitcnt vmcnt(0)` -- a full drain of the X prefetch ring per trip is
     what hipcc emits when a load sits under a branch and its value is used at once (round 2: 30 of the mode-2 MTTKRP's
     125 us).  A regression shows up here, on the CPU, instead of as a slower bench line."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("check_loop_drains", os.path.join(ROOT, "tools", "check_loop_drains.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = _tool("check_loop_drains")
     build = os.path.join(ROOT, "nn_fac_amd", "csrc", "build")
-    want = {"k_stream.s": ["nnf_xty_kernel<3, 2, true>", "nnf_xht_kernel<3, 2, true, 4>", "nnf_xty_kernel<6, 4, true>",
-                           "nnf_xht_kernel<6, 4, true, 4>", "nnf_xty_kernel<2, 0, true>"],
+    want = {"k_xty.s": ["nnf_xty_kernel<3, 2, true>", "nnf_xty_kernel<6, 4, true>", "nnf_xty_kernel<2, 0, true>"],
+            "k_xht.s": ["nnf_xht_kernel<3, 2, true, 4>", "nnf_xht_kernel<6, 4, true, 4>"],
             "k_mttkrp.s": ["nnf_mttkrp_rows_kernel<2, true, true>", "nnf_mttkrp_seg_kernel<2, true>",
                            "nnf_mttkrp_rows_kernel<4, true, true>", "nnf_mttkrp_seg_kernel<4, true>"]}
     for fname, kernels in want.items():
@@ -179,6 +182,20 @@ def test_streaming_kernels_keep_their_prefetch_ring_in_flight(built_lib):
                 main = [l for l in loops if l["mfma"] >= max(90, 16 * mt + 1)]
                 assert main, (k, loops)
                 assert all(l["vmcnt0"] == 0 for l in main), (k, main)
+
+
+def test_tile_count_dispatcher_and_rank_passes_on_the_cpu(tmp_path):
+    """nn_fac_amd/csrc/k_dispatch.h under the host compiler's address and undefined-behaviour sanitizers, as a stand-alone
+    program (tools/dispatch_check.cpp): each of 1 .. N reaches its own instantiation exactly once, every value outside 1 .. N
+    (0, N + 1, INT_MAX, negatives) takes N, and the rank passes cover a rank above 128 in order, hand the workspace back after
+    each pass and stop at the first error."""
+    import subprocess
+    exe = str(tmp_path / "dispatch_check")
+    subprocess.run([os.environ.get("CXX", "c++"), "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "nn_fac_amd", "csrc"), os.path.join(ROOT, "tools", "dispatch_check.cpp"), "-o", exe],
+                   check=True)
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0 and p.stdout.strip() == "ok", p.stdout[-2000:] + p.stderr[-2000:]
 
 
 # Parameters of Engine methods the double does not take, each with the reason it may lack them.

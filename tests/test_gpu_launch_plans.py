@@ -1,4 +1,4 @@
-"""Every launch plan of the streaming (k_stream.hip, k_xht_lds.hip) and MU (k_mu.hip) launchers, against fp64.  Needs a MI355X.
+"""Every launch plan of the streaming (k_xty.hip, k_xht.hip, k_gram.hip, k_cost.hip, k_xht_lds.hip) and MU (k_mu.hip) launchers, against fp64.  Needs a MI355X.
 
 The launchers pick a plan from m, n, r, the alignment of X, the CU count and the free workspace: the X H^T row tilings and
 their k-split tail, the split counts of W^T X, of the right MU update and of the Gram, the row mixes of the left MU update,

@@ -1,4 +1,4 @@
-"""Every launch plan of the tensor side (k_mttkrp.hip, the CP cost of k_stream.hip), against fp64.  Needs a MI355X, except for
+"""Every launch plan of the tensor side (k_mttkrp.hip, the CP cost of k_cost.hip), against fp64.  Needs a MI355X, except for
 test_tensor_cases_reach_required.
 
 launch_seg (MTTKRP modes 0 and 1), launch_rows (mode 2), nnf_mttkrp3_from_partial_f32 (dimension tree) and the cost pass with

@@ -2,6 +2,7 @@
 # Timing-only build of ONE translation unit with extra -D flags, linked with the product's other objects into
 # tools/abl/libnnfac_<tag>.so (NNF_LIBRARY=<that file> selects it; never shipped, git-ignored).
 #   bash tools/abl_build.sh <tag> <source.hip> <object it replaces, e.g. k_hals_fast1.o> <flags...>
+#   e.g.  bash tools/abl_build.sh xty1 k_xty.hip k_xty.o -DXTY_BIG_WG=1
 set -e
 TAG=$1; SRC=$2; REPL=$3; shift 3
 R=$(cd "$(dirname "$0")/.." && pwd)

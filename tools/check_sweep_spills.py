@@ -11,7 +11,7 @@ load and the wait that covers it.  hipcc cannot see these loads, so nothing but 
       s_waitcnt lgkmcnt(N) retires all but the N youngest reads.  Same walk over the blocks with > 16 ds_read_b128.
 
     python tools/check_sweep_spills.py            (seconds after `make`: the build keeps each unit's ISA listing; without
-                                                   them the eight translation units are compiled to assembly, ~3 minutes)
+                                                   them the parts of both units are compiled to assembly, minutes)
 
 Exit code 1 / a non-empty list from check_all() = a rank instantiation (or a compiler bump) broke the invariant: the
 abort class of round 1 (gpurun_out/t44.log: a row-split sweep over the SGPR budget).
@@ -27,12 +27,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "nn_fac_amd", "csrc")
 
 
+def parts(family):
+    """Part numbers of a range-split unit, from the one place that names them: <family>_PARTS in nn_fac_amd/csrc/Makefile."""
+    m = re.search(r"^%s_PARTS\s*:?=\s*([\d ]+)$" % family, open(os.path.join(CSRC, "Makefile")).read(), re.M)
+    assert m, f"{family}_PARTS not found in the Makefile"
+    return [int(p) for p in m.group(1).split()]
+
+
 def _isa(src, define):
     """ISA of one translation unit: the listing the build left next to its object (same compilation as the shipped code,
     nn_fac_amd/csrc/Makefile) when it is newer than every source, else a fresh compilation to assembly."""
     part = define.split("=")[1]
     kept = os.path.join(CSRC, "build", f"{os.path.splitext(src)[0]}{part}.s")
-    deps = [os.path.join(CSRC, f) for f in (src, "k_hals_common.h", "nnf_internal.h")] + \
+    deps = [os.path.join(CSRC, f) for f in (src, "k_hals_common.h", "k_parts.h", "k_dispatch.h", "nnf_internal.h")] + \
         [os.path.join(ROOT, "include", "nnfac_hip.h")]
     if os.path.exists(kept) and os.path.getmtime(kept) >= max(os.path.getmtime(d) for d in deps):
         return open(kept).read().split("\n")
@@ -68,11 +75,16 @@ def _regs(text, bank):
     return used
 
 
+SEEN_FAST, SEEN_QUAD = set(), set()   # padded ranks / quad counts whose kernels the walks have met
+FAST_RANKS = (8, 16, 24, 32, 40, 48, 50, 52, 56, 64, 80, 96, 100, 104, 112, 128)   # what the plan may ask for (pick_rp, k_hals_plan.h)
+
+
 def check_fast(part):
     """Violations in k_hals_fast.hip, translation unit `part`: list of (kernel, instruction)."""
     lines = _isa("k_hals_fast.hip", f"-DHALS_PART={part}")
     bad, seen = [], 0
     for name, blocks in _kernels(lines, r"^_Z15nnf_hals_kernelILi\d+ELb\dEEv9hals_args:"):
+        SEEN_FAST.add(int(re.match(r"_Z15nnf_hals_kernelILi(\d+)E", name).group(1)))
         for b in blocks:
             if sum("v_pk_fma_f32" in x for x in b) <= 100:
                 continue
@@ -99,6 +111,7 @@ def check_quad(part):
     lines = _isa("k_hals_quad.hip", f"-DQUAD_PART={part}")
     bad, seen = [], 0
     for name, blocks in _kernels(lines, r"^_Z20nnf_hals_quad_kernelILi\d+EEv9hals_args:"):
+        SEEN_QUAD.add(int(re.match(r"_Z20nnf_hals_quad_kernelILi(\d+)E", name).group(1)))
         for b in blocks:
             if sum("ds_read_b128" in x for x in b) <= 16:
                 continue
@@ -126,9 +139,12 @@ def check_quad(part):
 
 
 def check_all(verbose=False):
-    jobs = [(check_fast, p) for p in range(4)] + [(check_quad, p) for p in range(4)]
+    jobs = [(check_fast, p) for p in parts("FAST")] + [(check_quad, p) for p in parts("QUAD")]
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         res = list(ex.map(lambda j: j[0](j[1]), jobs))
+    # the parts together hold every instantiation the plan may ask for, whichever way the tables cut them
+    assert SEEN_FAST >= set(FAST_RANKS), sorted(set(FAST_RANKS) - SEEN_FAST)
+    assert SEEN_QUAD >= set(range(1, 33)), sorted(set(range(1, 33)) - SEEN_QUAD)
     bad, blocks = [], 0
     for (fn, p), (b, seen) in zip(jobs, res):
         blocks += seen

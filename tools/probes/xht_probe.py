@@ -1,4 +1,4 @@
-"""X H^T (nnf_xht_f32) per kernel form -- X fragments straight into registers (k_stream.hip, NNF_XHT=direct) against X staged
+"""X H^T (nnf_xht_f32) per kernel form -- X fragments straight into registers (k_xht.hip, NNF_XHT=direct) against X staged
 through LDS in 256-byte row pieces (k_xht_lds.hip, the default where it applies) -- at config B's shape and at the shape of
 config D's partial product (T x_2 F2^T on the (I J) x K view), each checked against a float64 product on a slice.
     python tools/probes/xht_probe.py [m n r ...]"""

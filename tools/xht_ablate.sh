@@ -1,5 +1,5 @@
 #!/bin/bash
-# Timing-only ablations of nnf_xht_kernel (k_stream.hip, XHT_ABL) at config B's shape: which part of the kernel its time belongs to.
+# Timing-only ablations of nnf_xht_kernel (k_xht.hip, XHT_ABL) at config B's shape: which part of the kernel its time belongs to.
 #   here (no GPU):   bash tools/xht_ablate.sh build     -> tools/abl/libnnfac_xht{1..5}.so
 #   on the GPU box:  bash tools/xht_ablate.sh run       -> gpurun_out/abl_xht.txt   (results of the ablated builds are WRONG by design)
 # 1: no X stream   2: no MFMA   3: no leftover-rank FMAs   4: no LDS restage / barrier   5: no ragged-tail branch
@@ -8,14 +8,14 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/nn_fac_amd/csrc
 mkdir -p $R/tools/abl
 if [ "$1" = "build" ]; then
-  OBJS=$(ls $C/build/*.o | grep -v k_stream.o)
+  OBJS=$(ls $C/build/*.o | grep -v k_xht.o)
   for v in 1 2 3 4 5; do
-    /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-value -Wno-unused-result -DXHT_ABL=$v -c $C/k_stream.hip -o $R/tools/abl/k_stream_abl$v.o &
+    /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-value -Wno-unused-result -DXHT_ABL=$v -c $C/k_xht.hip -o $R/tools/abl/k_xht_abl$v.o &
   done
   wait
   for v in 1 2 3 4 5; do
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/tools/abl/libnnfac_xht$v.so $OBJS $R/tools/abl/k_stream_abl$v.o -ldl
-    rm -f $R/tools/abl/k_stream_abl$v.o
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/tools/abl/libnnfac_xht$v.so $OBJS $R/tools/abl/k_xht_abl$v.o -ldl
+    rm -f $R/tools/abl/k_xht_abl$v.o
   done
   exit 0
 fi

@@ -1,4 +1,4 @@
-// Dev tool: component ablation of the W^T X kernel (generated from k_stream.hip by hand; not part of the library).
+// Dev tool: component ablation of the W^T X kernel (generated from k_xty.hip by hand; not part of the library).
 
 #include "../nn_fac_amd/csrc/k_stream_common.h"
 #include <cstdio>
