@@ -420,7 +420,10 @@ int nnf_hals_group_max_columns(nnf_ctx* ctx, int r, int64_t* columns_out);
  * group g is the dense r x r matrix at UtU + g*gstride (row stride ldg); status_f64: ngroups blocks of NNF_HALS_ST_WORDS
  * doubles in the NNF_HALS_ST_* layout.  One workgroup per group: the stopping rule is a sum over that workgroup.
  * max_group_cols: the caller's bound on the group lengths, <= NNF_HALS_GROUP_MAX_COLUMNS (else NNF_ERR_UNSUPPORTED).  Groups of
- * one column (K diagonal updates in one launch) and empty groups are fine; max_sweeps = 1 on a copy is a probe sweep. */
+ * one column (K diagonal updates in one launch) and empty groups are fine (an empty group changes nothing and reports eps 0,
+ * cnt max_sweeps + 1, eps0 0); max_sweeps = 1 on a copy is a probe sweep, max_sweeps = 0 leaves V alone and reports eps 1,
+ * cnt 1, eps0 0.  A NaN in a group's operands is not projected away: as with np.maximum it stays in that group's V, makes its
+ * sum of squared steps NaN and ends its loop after that sweep (eps NaN); the other groups do not see it. */
 int nnf_hals_solve_group_f32(nnf_ctx* ctx, const float* UtM, int64_t ldm, const float* UtU, int64_t ldg, int64_t gstride,
                              float* V, int64_t ldv, int r, const int64_t* off, int ngroups, int64_t max_group_cols,
                              int64_t total_cols, int max_sweeps, double delta, double* status_f64, void* stream);

@@ -90,7 +90,10 @@ __global__ __launch_bounds__(128) void nnf_hals_group_kernel(const float* __rest
                     dot = fmaf(gq.w, vv[384], dot);
                 }
                 const float vk = vl[k * 128 + tid];
-                float step = fmaxf((UtM[(int64_t)k * ldm + cc] - dot) * di, -vk);
+                // np.maximum(x, -v), NaN included (nnls.py:167): fmaxf would drop a NaN of x, turn the group's V into clean
+                // zeros and go on sweeping; kept, it makes the sum of squared steps NaN and the stopping rule below ends the group
+                const float x = (UtM[(int64_t)k * ldm + cc] - dot) * di;
+                float step = (x < -vk) ? -vk : x;
                 if (!active) step = 0.f;
                 vl[k * 128 + tid] = vk + step;
                 nd += (double)step * (double)step;

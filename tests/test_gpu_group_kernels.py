@@ -14,7 +14,7 @@ import nnfac_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-RANKS = [1, 3, 16, 17, 50, 64, 65, 128]
+RANKS = [1, 3, 16, 17, 32, 33, 50, 64, 65, 128]
 CAP = 8192          # NNF_HALS_GROUP_MAX_COLUMNS (asserted against the query entry below)
 
 
@@ -81,7 +81,7 @@ def group_reference(G, M, V, budget, delta=0.01):
     Vg, e, c, _ = orc.hals_nnls_acc(M.astype(np.float64), G.astype(np.float64), V.astype(np.float64), maxiter=budget,
                                     alpha=math.inf, delta=delta, sweep_log=log)
     for s in log[-2:]:
-        if log[0] > 0 and abs(s / (delta * log[0]) - 1.0) < 1e-3:
+        if delta * log[0] > 0 and abs(s / (delta * log[0]) - 1.0) < 1e-3:       # (delta = 0 never stops: no flip)
             return None
     return Vg, e, c
 
@@ -89,7 +89,7 @@ def group_reference(G, M, V, budget, delta=0.01):
 _REF = {}
 
 
-def solve_case(key, r, lens, seed, budget, **kw):
+def solve_case(key, r, lens, seed, budget, delta=0.01, **kw):
     """Inputs and their fp64 answers, once per key.  Group g is drawn from the first of the seeds 1000 seed + g, + 500000, ...
     whose restatement keeps the margin (decided by the restatement alone, never by the device's result)."""
     if key not in _REF:
@@ -100,7 +100,7 @@ def solve_case(key, r, lens, seed, budget, **kw):
         for g, n in enumerate(lens):
             for s in range(1000 * seed + g, 1000 * seed + g + 20 * 500000, 500000):
                 Gg, Mg, Vg = group_problem(r, n, s, **kw)
-                ref = group_reference(Gg, Mg, Vg, budget)
+                ref = group_reference(Gg, Mg, Vg, budget, delta)
                 if ref is not None:
                     break
             else:
@@ -135,7 +135,7 @@ def check_solve(eng, key, r, lens, seed, budget, frozen_row=None, **kw):
 
 
 def mixed_lens():
-    return [1, 2, 63, 64, 65, 255, 256, 257, CAP - 1, CAP]
+    return [1, 2, 31, 32, 33, 63, 64, 65, 255, 256, 257, CAP - 1, CAP]
 
 
 def test_cap_query(eng):
