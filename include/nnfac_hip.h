@@ -299,6 +299,27 @@ int nnf_mu_apply_f32(nnf_ctx* ctx, const float* F, int64_t ldf, int r, int64_t c
                      const float* den, int64_t ldden, const double* den_vec_f64, double beta, float* out, int64_t ldo,
                      void* stream);
 
+/* simplex_proj_mu at beta = 1 (mu.py:161-175) from already formed operands, with the multiplier solve of
+ * update_lagragian_multipliers_simplex_projection (normalize_wh.py:24-58): H (r x cols) with its columns on the unit simplex.
+ *   num = C = W^T(X ./ (WH)),  den = D = W^T 1  -- the num / den_vec_f64 of nnf_mu_right_accum_f32 at beta = 1; exactly one of
+ *   `den` (r x cols matrix) and `den_vec_f64` (r doubles: den[k,j] = den_vec_f64[k]) is given, as in nnf_mu_apply_f32.
+ *   lambda[j] starts from lambda0_f64[j], or (NULL) from the reference's D[0,j] - C[0,j] H[0,j]; up to max_iter times, all columns
+ *   together:  den = D - lambda[j];  lambda[j] -= (sum_k H C/(den + 1e-8) - 1) / (sum_k H C/den^2 + 1e-8);  stop after the first
+ *   iteration whose max_j |lambda - lambda_prev| is <= tol (ONE test over all columns);  then
+ *   H_out = max(H .* (C ./ ((D - lambda) + 1e-12)), 1e-12).
+ * The operands are fp32, every statement of the solve and of the update runs in fp64 (sums over k included), a NaN is kept:
+ * a NaN operand makes its column NaN and the call run all max_iter iterations, as np.max does in the reference.
+ * Two stream-ordered launches of one kernel and no wait between workgroups (nn_fac_amd/csrc/k_simplex.hip); two calls are
+ * bitwise equal.  status_f64 (device, 2 doubles): {iterations run, max_j |dlambda| of the last one} -- the reference warns
+ * 'Maximum of iterations reached ...' exactly when status[0] == max_iter and not status[1] <= tol.
+ * H_out may be NULL (multipliers only) and may alias H; lambda_out_f64 (cols doubles) may be NULL.
+ * Refused before anything is launched, every output untouched: r > NNF_MAX_RANK or max_iter outside 1 .. 1024
+ * (NNF_ERR_UNSUPPORTED), both or neither of den / den_vec_f64 (NNF_ERR_ARG), a workspace that cannot hold max_iter + 1 64-bit
+ * words (NNF_ERR_WORKSPACE).  beta != 1 has no entry point: the reference's rule does not reach the simplex there. */
+int nnf_simplex_proj_kl_f32(nnf_ctx* ctx, const float* H, int64_t ldh, int r, int64_t cols, const float* num, int64_t ldnum,
+                            const float* den, int64_t ldden, const double* den_vec_f64, const double* lambda0_f64, double tol,
+                            int max_iter, float* H_out, int64_t ldo, double* lambda_out_f64, double* status_f64, void* stream);
+
 /* Ranks beyond the fused kernels (r > NNF_MAX_RANK, every beta): the element-wise operands of mu_betadivmin (mu.py:84-97),
  *   R1 = X .* (UV)^(beta-2)   and, unless beta == 1,   R2 = (UV)^(beta-1)        (both m x n, row stride ldr, caller-owned),
  * written in one pass over X; the two contractions are then plain nnf_xht_f32 / nnf_xty_f32 calls on R1 / R2 and

@@ -66,6 +66,7 @@ SIGNATURES = {
     "nnf_ntd_core_pgn_f32": (_i32, [_p, _p, _p, _p, _i32, _p, _f64, _f64, _i32, _f64, _p, _p]),
     "nnf_mu_ratio_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i32, _f64, _p, _p, _i64, _p]),
     "nnf_mu_apply_f32": (_i32, [_p, _p, _i64, _i32, _i64, _p, _i64, _p, _i64, _p, _f64, _p, _i64, _p]),
+    "nnf_simplex_proj_kl_f32": (_i32, [_p, _p, _i64, _i32, _i64, _p, _i64, _p, _i64, _p, _p, _f64, _i32, _p, _i64, _p, _p, _p]),
     "nnf_mu_left_num_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i32, _p, _i64, _p]),
     "nnf_small_gemm_f32": (_i32, [_p, _p, _i64, _i32, _i32, _p, _i64, _i64, _p, _i64, _p]),
     "nnf_deep_kl_apply_f32": (_i32, [_p, _p, _i64, _i32, _i64, _p, _i64, _p, _p, _i64, _f64, _p, _i64, _p]),

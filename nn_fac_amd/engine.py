@@ -616,6 +616,42 @@ class Engine:
                                              _ld(O), self._stream()), "nnf_mu_apply_f32")
         return O
 
+    SIMPLEX_MAX_ITER = 1024   # Newton iterations one nnf_simplex_proj_kl_f32 call takes (one stopping slot each)
+
+    def simplex_proj(self, H, num, den, den_vec, tol=1e-6, max_iter=100, lambda0=None, out=None, lambda_out=None, status=None,
+                     update=True):
+        """simplex_proj_mu at beta = 1 from reduced operands (mu.py:161-175; normalize_wh.py:24-58): the Newton solve for the
+        per-column multipliers -- from `lambda0` (cols float64) or the reference's start -- and, with `update`, the update of H
+        that puts its columns on the unit simplex.  `num`, and exactly one of `den` (r x cols) and `den_vec` (r float64), are
+        what mu_right_accum(..., 1) returns.  Returns (H_out or None, status): status = 2 float64 on the device, {iterations run,
+        max |dlambda| of the last one}; `lambda_out` (cols float64) receives the multipliers.  `out` may be H itself."""
+        _chk2d(H, "simplex H"), _chk2d(num, "simplex num")
+        r, cols = H.shape
+        if num.shape != (r, cols) or (den is None) == (den_vec is None):
+            raise EngineError("simplex_proj: num must have H's shape, and exactly one of den / den_vec is given")
+        if den is not None and _chk2d(den, "simplex den").shape != (r, cols):
+            raise EngineError("simplex_proj: den must have H's shape")
+        f64 = [("den_vec", den_vec, r), ("lambda0", lambda0, cols), ("lambda_out", lambda_out, cols), ("status", status, 2)]
+        for name, t, count in f64:
+            if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() < count):
+                raise EngineError(f"simplex_proj: {name} must be a contiguous float64 device tensor of {count} elements")
+        if r > MAX_RANK or not 1 <= int(max_iter) <= self.SIMPLEX_MAX_ITER:
+            raise EngineError(f"simplex_proj: built for r <= {MAX_RANK} and 1 <= max_iter <= {self.SIMPLEX_MAX_ITER}")
+        O = None
+        if update:
+            O = out if out is not None else torch.empty_like(H)
+            if _chk2d(O, "simplex out").shape != (r, cols):
+                raise EngineError("simplex_proj: out must have H's shape")
+        st = status if status is not None else torch.empty(2, dtype=torch.float64, device=H.device)
+        _lib.check(self.lib.nnf_simplex_proj_kl_f32(self.ctx, _ptr(H), _ld(H), r, cols, _ptr(num), _ld(num),
+                                                    _ptr(den) if den is not None else None, _ld(den) if den is not None else 0,
+                                                    _ptr(den_vec) if den_vec is not None else None,
+                                                    _ptr(lambda0) if lambda0 is not None else None, float(tol), int(max_iter),
+                                                    _ptr(O) if O is not None else None, _ld(O) if O is not None else 0,
+                                                    _ptr(lambda_out) if lambda_out is not None else None, _ptr(st),
+                                                    self._stream()), "nnf_simplex_proj_kl_f32")
+        return O, st
+
     # ---- deep KL-NMF (deep_mu.py:8-14) -------------------------------------------------------------
     def mu_left_num(self, X, Ut, V, out=None):
         """Raw KL numerator of the left update: num[k,i] = sum_j (X[i,j] / (UV)[i,j]) V[k,j]  (r x m)."""

@@ -4,6 +4,10 @@
 the fused kernels (``nnf_mu_left_f32`` / ``nnf_mu_right_f32``) stream M once and never materialise U@V, for every beta up
 to rank 128 (no data-sized temporary); above 128 the engine composes the update from the ratio pass and plain contractions
 (m x n operands in device memory), beta = 2 runs the Gram form at any rank.
+
+``simplex_proj_mu(data, W, H, beta, tol_update_lagrangian)`` (mu.py:161-175) is the H update of simplex-constrained NMF at
+beta = 1: ``nnf_mu_right_accum_f32`` for C and D, then the Newton solve and the update in ``nnf_simplex_proj_kl_f32``; every
+other beta is refused (nn_fac_amd/simplex_nmf.py says why).
 """
 import torch
 
@@ -57,3 +61,18 @@ def mu_tensorial(G, factors, tensor, beta):
     st = _NtdState(eng, to_dev(tensor, dev))
     core = _mu_tensorial_dev(st, to_dev(G, dev).contiguous(), [to_dev_t(f, dev) for f in factors], beta)
     return like_input(core, G)
+
+
+def simplex_proj_mu(data, W, H, beta, tol_update_lagrangian=1e-6):
+    """H <- max(H * (C / ((D - lambda) + 1e-12)), 1e-12) with the multipliers of normalize_wh.py:24-58 (mu.py:161-175), beta = 1:
+    the columns of the result sum to one.  Warns like the reference when the 100 Newton iterations do not reach the tolerance."""
+    from .. import simplex_nmf as _sx
+    _sx.check_beta(beta, "simplex_proj_mu")
+    _sx.check_rank(H.shape[0], "simplex_proj_mu")
+    dev = device_of(data, W, H)
+    eng = _engine.get_engine(dev)
+    words = torch.zeros(2, dtype=torch.float64, device=dev)
+    out = _sx.simplex_right(eng, to_dev(data, dev), to_dev_t(W, dev), to_dev(H, dev), tol_update_lagrangian, words)
+    count, last = words.cpu().tolist()
+    _sx.newton_warning(count, last, tol_update_lagrangian)
+    return like_input(out, H)

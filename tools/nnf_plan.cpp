@@ -1,5 +1,5 @@
 // The launch plans of libnnfac_hip.so without a device: the library's own plan functions (nn_fac_amd/csrc/k_stream_plan.h,
-// k_mu_plan.h, k_hals_plan.h) for any CU count, printed as the library reports them under NNF_PLAN_DEBUG / NNF_HALS_DEBUG.
+// k_mu_plan.h, k_hals_plan.h, k_simplex_plan.h) for any CU count, printed as the library reports them under NNF_PLAN_DEBUG / NNF_HALS_DEBUG.
 //
 //   nnf_plan < cases     one case per line:  <launcher> <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [key=value ...]
 //                        launcher: xht | xty | mu_left | mu_right | mu_mode | mttkrp_rows | mttkrp_seg | partial_last |
@@ -40,6 +40,13 @@
 //                                     Answer: the "[nnf hals] ..." line of that call (NNF_HALS_DEBUG; a refusal is its err=),
 //                                     followed by gram_floats= mfma_floats= snap_floats= (what the launcher carves).
 //                          hals_resident <CUs> r= [pc_lane_res=] [pc_generic_gcol=]     nnf_hals_resident_columns: "columns=<n>"
+//                        The simplex projection's plan (k_simplex_plan.h) reads key=value fields too:
+//                          simplex <CUs> r= cols= [max_iter=] [ws=] [force=] [matrix=] [pitch=] [both=]     max_iter defaults to
+//                                     100, ws (free workspace bytes) to 1 GiB; force: NNF_SIMPLEX_FORCE; matrix=1: the
+//                                     denominator is the r x cols matrix; pitch: the smallest of the operands' pitches (default
+//                                     cols); both=1 / both=-1: den and den_vec both given / both missing.  Answer: the
+//                                     "[nnf plan] simplex ..." line of that call, or "status=<code>" for a refusal (the argument
+//                                     checks of nnf_simplex_proj_kl_f32 included).
 //   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
 //                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
 //
@@ -50,6 +57,7 @@
 #include <string.h>
 #include "k_mu_plan.h"
 #include "k_hals_plan.h"
+#include "k_simplex_plan.h"
 
 static long long key_of(const char* rest, const char* key, long long dflt) {
     char pat[32];
@@ -128,6 +136,24 @@ static int answer_hals(const char* name, const char* line) {
     return 0;
 }
 
+static int answer_simplex(const char* line) {
+    int C = 0, used = 0;
+    if (sscanf(line, "%*s %d%n", &C, &used) != 1 || C < 1) return 2;
+    const char* rest = line + used;
+    const long long r = key_of(rest, "r", 0), cols = key_of(rest, "cols", 0), force = key_of(rest, "force", 0);
+    const long long max_iter = key_of(rest, "max_iter", 100), ws = key_of(rest, "ws", 1024ll << 20), both = key_of(rest, "both", 0);
+    // (the argument checks of nnf_simplex_proj_kl_f32, k_simplex.hip)
+    if (r < 1 || cols < 1 || key_of(rest, "pitch", cols) < cols || both != 0 ||
+        (force != 0 && force != 1 && force != 4 && force != 16 && force != 64)) {
+        printf("status=%d\n", NNF_ERR_ARG);
+        return 0;
+    }
+    const simplex_plan p = simplex_make_plan(C, (int)(r > 1000000 ? 1000000 : r), cols, (int)max_iter, (int)force, (size_t)ws);
+    if (p.status != NNF_OK) printf("status=%d\n", p.status);
+    else simplex_report(stdout, (int)r, cols, (int)max_iter, key_of(rest, "matrix", 0) != 0, p);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "shm") == 0) return print_shm();
     char line[512], name[32], more[192];
@@ -135,8 +161,8 @@ int main(int argc, char** argv) {
         long long C, m, n, r, ld, ws;
         double beta;
         int used = 0;
-        if (sscanf(line, "%31s", name) == 1 && strncmp(name, "hals", 4) == 0) {
-            if (answer_hals(name, line) != 0) {
+        if (sscanf(line, "%31s", name) == 1 && (strncmp(name, "hals", 4) == 0 || strcmp(name, "simplex") == 0)) {
+            if ((name[0] == 's' ? answer_simplex(line) : answer_hals(name, line)) != 0) {
                 fprintf(stderr, "nnf_plan: bad case line: %s", line);
                 return 2;
             }
