@@ -139,6 +139,20 @@ int nnf_xht_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx,
 int nnf_xty_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int r, int64_t ldu,
                 float* out, int64_t ldo, void* stream);
 
+/* A cross product and the Gram of its small factor in ONE main launch and ONE slab reduction (the two are independent of each
+ * other, nmf.py:407-408 / :432-433): the Gram's split-K workgroups ride behind the cross product's in the same grid, and one
+ * reduction adds the slab sets of both.  Kernel bodies, split plans and slab order are those of the separate entry points, so
+ * every output is bit for bit what nnf_xty_f32 + nnf_gram_f32 (nnf_gram_f64_f32 with G64 != NULL) and nnf_xht_f32 +
+ * nnf_gram_f32 write.  Where the Gram cannot ride (its one-workgroup forms for K <= 1024, ranks above NNF_MAX_RANK, the
+ * LDS-staged X H^T of ranks <= 32, a workspace too small for both carves) the call runs the two one after the other.
+ *   nnf_xty_gram_f32: out[r x n] = Ut X,   G[r x r] = Ut Ut^T (pitch ldg), G64 (may be NULL): its sums before rounding
+ *   nnf_xht_gram_f32: out[r x m] = V X^T,  G[r x r] = V V^T   (pitch ldg)
+ * The NNF_PROBE_XTY / NNF_PROBE_XHT events bracket the main launch with its rider. */
+int nnf_xty_gram_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int r, int64_t ldu,
+                     float* out, int64_t ldo, float* G, int64_t ldg, double* G64, void* stream);
+int nnf_xht_gram_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r, int64_t ldv,
+                     float* out, int64_t ldo, float* G, int64_t ldg, void* stream);
+
 /* *out_f64 = sum_ij (X[i,j] - sum_k Ut[k,i] V[k,j])^2.   Replaces np.linalg.norm(data - U@V, 'fro')**2 (nmf.py:452)
  * without materialising U@V.  Per-lane fp32, then fp64 from the wave level up, fixed order. */
 int nnf_frob_resid_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,

@@ -352,6 +352,39 @@ inline void nnf_report_gram(FILE* f, int r, int64_t K, const nnf_gram_plan& p, c
             (long long)p.nsplit, (long long)p.kps, p.bound, more);
 }
 
+// ---- a cross product with the Gram of its factor riding in the same launch (nnf_xty_gram_f32, nnf_xht_gram_f32) ----
+// The cross product keeps its own plan and its first main_grid workgroups; the Gram keeps the plan a call of its own takes
+// (`g`, made against the same free workspace) and rides as workgroups [rider_offset, rider_offset + rider_grid), one per split.
+// Both carves come from one cursor: the cross product's slabs first (main_bytes, 0: none), the Gram's behind them on the
+// cursor's 256-byte boundary.  Only the slab form rides (small / single write G without slabs, blocks has a grid of its own), and
+// only where both carves fit and the Gram stages `tiles` rank tiles, the LDS image of the cross product: otherwise rides = false
+// and the two run as the launches of their own, which gives the same bits.
+struct nnf_rider_plan {
+    bool rides;
+    int64_t main_grid, rider_grid, rider_offset, grid;
+    size_t main_bytes, rider_bytes, rider_ws_off, ws_bytes;
+};
+inline nnf_rider_plan nnf_plan_rider(int64_t main_grid, size_t main_bytes, const nnf_gram_plan& g, int r, int tiles,
+                                     size_t free_bytes) {
+    nnf_rider_plan p{false, main_grid, 0, main_grid, main_grid, main_bytes, 0, 0, main_bytes};
+    if (g.status != NNF_OK || g.form != NNF_GRAM_SLABS || (r + 15) / 16 != tiles) return p;
+    nnf_ws_cursor cur(nullptr, free_bytes);
+    const size_t rider_bytes = (size_t)g.nsplit * r * r * 4;
+    if ((main_bytes > 0 && !cur.reserve(main_bytes)) || !cur.reserve(rider_bytes)) return p;
+    p.rides = true;
+    p.rider_grid = g.nsplit;
+    p.grid = main_grid + g.nsplit;
+    p.rider_bytes = rider_bytes;
+    p.rider_ws_off = cur.off - rider_bytes;
+    p.ws_bytes = cur.off;
+    return p;
+}
+inline void nnf_report_rider(FILE* f, const char* what, const nnf_rider_plan& p, const char* more = "") {
+    fprintf(f, "[nnf plan] %s rides=%d main_grid=%lld rider_grid=%lld rider_offset=%lld grid=%lld main_bytes=%zu rider_bytes=%zu "
+               "rider_ws_off=%zu ws_bytes=%zu%s\n", what, (int)p.rides, (long long)p.main_grid, (long long)p.rider_grid,
+            (long long)p.rider_offset, (long long)p.grid, p.main_bytes, p.rider_bytes, p.rider_ws_off, p.ws_bytes, more);
+}
+
 // ---- the cost / ratio pass (launch_cost): 128-row workgroups x column splits ----
 // 32 rows of X (or of the model buffer of a rank above 128) at pitch ld and a factor chunk inside 32-bit offsets
 constexpr bool nnf_cost_offsets_ok(int64_t ld, int64_t n) { return 32 * ld * 4 + 4 * (n + 128) < NNF_OFFSET32_END; }

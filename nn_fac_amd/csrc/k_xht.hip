@@ -1,7 +1,7 @@
 // X H^T: out[r x m] = V[r x n] * X[m x n]^T  (nmf.py:408) with the fragments of X loaded straight into registers; ranks up to
 // 32 go to the LDS-staged form of k_xht_lds.hip.  The design shared with W^T X, the Gram and the cost pass is described at the
 // head of k_stream_common.h.
-#include "k_stream_common.h"
+#include "k_gram_body.h"
 #ifndef XHT_ABL
 #define XHT_ABL 0   // timing-only ablations of nnf_xht_kernel (tools/xht_ablate.sh); 0 = the product
 #endif
@@ -142,15 +142,14 @@ __device__ __forceinline__ void nnf_xht_body(const float* __restrict__ X, int64_
 // 64 rows per wave everywhere that is 1563 waves on 1024 SIMDs -- the SIMDs holding two of them decide the time
 // (8 row tiles against 6.1 on average).  The first n_hi workgroups take NTH tiles per wave, the others NTH-1, chosen
 // on the host so that one full round of resident workgroups covers the matrix (7 tiles on the busiest SIMD).
+// b: the workgroup's index in the X H^T grid; ldsA: its two chunk images
 template <int MT, int REM, bool VEC, int NTH>
-__global__ __launch_bounds__(256, (MT + (REM > 0) <= 4 || NTH <= 2 ? 2 : 1)) void nnf_xht_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
-                                                         const float* __restrict__ V, int64_t ldv, int r,
-                                                         float* __restrict__ out, int64_t ldo, int a_vec_ok, int n_hi,
-                                                         float* __restrict__ tail_slabs, int64_t tail_row0, int64_t tail_ld,
-                                                         int tail_tiles, int tail_parts, int tail_cpp) {
-    constexpr int MTA = MT + (REM > 0 ? 1 : 0);
-    __shared__ f32x4 ldsA[2][MTA * 256];
-    const int b = (int)blockIdx.x;
+__device__ __forceinline__ void nnf_xht_wg(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+                                           const float* __restrict__ V, int64_t ldv, int r,
+                                           float* __restrict__ out, int64_t ldo, int a_vec_ok, int n_hi,
+                                           float* __restrict__ tail_slabs, int64_t tail_row0, int64_t tail_ld,
+                                           int tail_tiles, int tail_parts, int tail_cpp, int b,
+                                           f32x4 (*ldsA)[(MT + (REM > 0 ? 1 : 0)) * 256]) {
     if (b < n_hi)
         nnf_xht_body<MT, REM, VEC, NTH>(X, m, n, ldx, V, ldv, r, out, ldo, a_vec_ok, (int64_t)b * (64 * NTH), ldsA);
     else
@@ -171,22 +170,75 @@ __global__ __launch_bounds__(256, (MT + (REM > 0) <= 4 || NTH <= 2 ? 2 : 1)) voi
     }
 }
 
+#define NNF_XHT_BOUNDS __launch_bounds__(256, (MT + (REM > 0) <= 4 || NTH <= 2 ? 2 : 1))
+template <int MT, int REM, bool VEC, int NTH>
+__global__ NNF_XHT_BOUNDS void nnf_xht_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+                                              const float* __restrict__ V, int64_t ldv, int r,
+                                              float* __restrict__ out, int64_t ldo, int a_vec_ok, int n_hi,
+                                              float* __restrict__ tail_slabs, int64_t tail_row0, int64_t tail_ld,
+                                              int tail_tiles, int tail_parts, int tail_cpp) {
+    __shared__ f32x4 ldsA[2][(MT + (REM > 0 ? 1 : 0)) * 256];
+    nnf_xht_wg<MT, REM, VEC, NTH>(X, m, n, ldx, V, ldv, r, out, ldo, a_vec_ok, n_hi, tail_slabs, tail_row0, tail_ld, tail_tiles,
+                                  tail_parts, tail_cpp, (int)blockIdx.x, ldsA);
+}
+
+// X H^T with the Gram of its left factor riding in the same launch (nnf_xht_gram_f32): workgroups [0, main_grid) are the cross
+// product's (tail shares included), workgroup main_grid + s forms split s of V V^T (k_gram_body.h) in the same LDS -- the Gram
+// stages the same MT + (REM > 0) tiles of V.  Same bodies, same plans: the bits of the two launches of their own.
+template <int MT, int REM, bool VEC, int NTH>
+__global__ NNF_XHT_BOUNDS void nnf_xht_gram_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+                                                   const float* __restrict__ V, int64_t ldv, int r,
+                                                   float* __restrict__ out, int64_t ldo, int a_vec_ok, int n_hi,
+                                                   float* __restrict__ tail_slabs, int64_t tail_row0, int64_t tail_ld,
+                                                   int tail_tiles, int tail_parts, int tail_cpp, int main_grid,
+                                                   float* __restrict__ gslabs, int64_t g_kps) {
+    constexpr int MTA = MT + (REM > 0 ? 1 : 0);
+    __shared__ f32x4 ldsA[2][MTA * 256];
+    const int b = (int)blockIdx.x;
+    if (b < main_grid)
+        nnf_xht_wg<MT, REM, VEC, NTH>(X, m, n, ldx, V, ldv, r, out, ldo, a_vec_ok, n_hi, tail_slabs, tail_row0, tail_ld, tail_tiles,
+                                      tail_parts, tail_cpp, b, ldsA);
+    else
+        nnf_gram_body<MTA>(V, r, n, ldv, gslabs, g_kps, a_vec_ok, b - main_grid, ldsA);
+}
+
 template <int MT, int REM, bool VEC>
 static int launch_xht(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r, int64_t ldv,
-                      float* out, int64_t ldo, hipStream_t st) {
+                      float* out, int64_t ldo, hipStream_t st, nnf_gram_ride* ride) {
     if (!nnf_xht_offsets_ok(n, ldx)) return NNF_ERR_UNSUPPORTED;
     static const int nt2 = [] { const char* e = getenv("NNF_XHT_NT2"); return e ? atoi(e) : -1; }();
     static const int tail_on = [] { const char* e = getenv("NNF_XHT_TAIL"); return e ? atoi(e) : 1; }();
-    const nnf_xht_plan pl = nnf_plan_xht_direct(ctx->num_cus, m, n, r, nnf_rank_tiles{MT, REM}, nt2, tail_on, cur.remaining());
+    const size_t free_bytes = cur.remaining();
+    const nnf_xht_plan pl = nnf_plan_xht_direct(ctx->num_cus, m, n, r, nnf_rank_tiles{MT, REM}, nt2, tail_on, free_bytes);
     if (!pl.covers(m)) return NNF_ERR_UNSUPPORTED;   // (cannot happen: the split covers m by construction)
     if (nnf_plan_debug()) nnf_report_xht(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, false, pl);
-    float* tail_slabs = pl.tail_parts > 0 ? (float*)cur.take((size_t)pl.tail_parts * r * pl.tail_ld * 4) : nullptr;
-    if (pl.tail_parts > 0 && !tail_slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
     const int a_vec_ok = x_vec_ok(V, ldv) ? 1 : 0;
-    nnf_probe(ctx, NNF_PROBE_XHT, 0, st);
-#define NNF_XHT_GO(NTH)                                                                                                          \
-    hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, NTH>), dim3((int)pl.grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, ldo, \
-                       a_vec_ok, (int)pl.n_hi, tail_slabs, pl.tail_row0, pl.tail_ld, pl.tail_tiles, pl.tail_parts, pl.tail_cpp)
+    const size_t tail_bytes = pl.tail_parts > 0 ? (size_t)pl.tail_parts * r * pl.tail_ld * 4 : 0;
+    nnf_gram_plan gp{};
+    nnf_rider_plan rp{};
+    if (ride) {   // the Gram's plan as a call of its own makes it: against the whole free workspace
+        gp = nnf_plan_gram(ctx->num_cus, r, n, ride->ldg == r, a_vec_ok, free_bytes);
+        rp = nnf_plan_rider(pl.grid, tail_bytes, gp, r, MT + (REM > 0 ? 1 : 0), free_bytes);
+        if (nnf_plan_debug()) nnf_report_rider(stderr, "xht_gram", rp);
+    }
+    const bool rides = ride && rp.rides;
+    float* tail_slabs = pl.tail_parts > 0 ? (float*)cur.take(tail_bytes) : nullptr;
+    if (pl.tail_parts > 0 && !tail_slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
+    float* gslabs = rides ? (float*)cur.take(rp.rider_bytes) : nullptr;
+    if (rides && !gslabs) return NNF_ERR_WORKSPACE;   // (cannot happen: nnf_plan_rider counted both carves)
+    if (rides && nnf_plan_debug()) nnf_report_gram(stderr, r, n, gp);
+    nnf_probe(ctx, NNF_PROBE_XHT, 0, st);   // (with its rider, where one comes along)
+#define NNF_XHT_GO(NTH)                                                                                                               \
+    do {                                                                                                                              \
+        if (rides)                                                                                                                    \
+            hipLaunchKernelGGL((nnf_xht_gram_kernel<MT, REM, VEC, NTH>), dim3((int)rp.grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, \
+                               out, ldo, a_vec_ok, (int)pl.n_hi, tail_slabs, pl.tail_row0, pl.tail_ld, pl.tail_tiles, pl.tail_parts,  \
+                               pl.tail_cpp, (int)pl.grid, gslabs, gp.kps);                                                           \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((nnf_xht_kernel<MT, REM, VEC, NTH>), dim3((int)pl.grid), dim3(256), 0, st, X, m, n, ldx, V, ldv, r, out, \
+                               ldo, a_vec_ok, (int)pl.n_hi, tail_slabs, pl.tail_row0, pl.tail_ld, pl.tail_tiles, pl.tail_parts,       \
+                               pl.tail_cpp);                                                                                          \
+    } while (0)
     if (pl.nth == 4) NNF_XHT_GO(4);
     else if (pl.nth == 2) {
         if constexpr (MT + (REM > 0) > 4) NNF_XHT_GO(2);
@@ -194,16 +246,23 @@ static int launch_xht(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
 #undef NNF_XHT_GO
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_XHT, 1, st);
-    if (pl.tail_parts > 0)    // the k-split shares of the last rows, added in share order
-        return nnf_launch_reduce_slabs(tail_slabs, pl.tail_parts, (int64_t)r * pl.tail_ld, r, m - pl.tail_row0, pl.tail_ld,
-                                       out + pl.tail_row0, ldo, st);
-    return NNF_OK;
+    // the k-split shares of the last rows, added in share order, and the rider's splits: one launch
+    nnf_reduce_set sets[2];
+    int nsets = 0;
+    if (pl.tail_parts > 0)
+        sets[nsets++] = nnf_plan_reduce_set(tail_slabs, pl.tail_parts, (int64_t)r * pl.tail_ld, r, m - pl.tail_row0, pl.tail_ld,
+                                            out + pl.tail_row0, ldo);
+    if (rides) {
+        sets[nsets++] = nnf_plan_reduce_set(gslabs, (int)gp.nsplit, (int64_t)r * r, r, r, r, ride->G, ride->ldg, ride->G64);
+        ride->rode = true;
+    }
+    return nsets > 0 ? nnf_launch_reduce_sets(sets, nsets, st) : NNF_OK;
 }
 
 int nnf_xht_lds_launch(nnf_ctx* ctx, int MT, int REM, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r,
                        int64_t ldv, float* out, int64_t ldo, hipStream_t st);   // k_xht_lds.hip
 int nnf_xht_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V,
-                 int r, int64_t ldv, float* out, int64_t ldo, hipStream_t st) {
+                 int r, int64_t ldv, float* out, int64_t ldo, hipStream_t st, nnf_gram_ride* ride) {
     if (!ctx || !X || !V || !out || m < 1 || n < 1 || r < 1 || ldx < n || ldv < n || ldo < m) return NNF_ERR_ARG;
     if (r > NNF_MAX_RANK)   // the rows of the result are independent of each other
         return nnf_rank_passes(r, cur, [&](int k0, int rc) {
@@ -217,7 +276,7 @@ int nnf_xht_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, in
     return nnf_dispatch<8>(t.MT, [&](auto mt) -> int {
         constexpr int MT = decltype(mt)::value;
         const auto go = [&](auto rem, auto v) {
-            return launch_xht<MT, decltype(rem)::value, decltype(v)::value>(ctx, cur, X, m, n, ldx, V, r, ldv, out, ldo, st);
+            return launch_xht<MT, decltype(rem)::value, decltype(v)::value>(ctx, cur, X, m, n, ldx, V, r, ldv, out, ldo, st, ride);
         };
         if (!vec) return go(nnf_int<0>{}, std::false_type{});
         if (t.REM == 2) return go(nnf_int<2>{}, std::true_type{});
@@ -230,4 +289,17 @@ extern "C" int nnf_xht_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, i
     if (!ctx) return NNF_ERR_ARG;
     nnf_ws_cursor cur(ctx);
     return nnf_xht_impl(ctx, cur, X, m, n, ldx, V, r, ldv, out, ldo, (hipStream_t)stream);
+}
+// X H^T and the Gram of its left factor, G = V V^T (pitch ldg), in one main launch and one reduction where nnf_plan_rider lets
+// the Gram ride (the register-fragment kernel: ranks above 32), as two calls otherwise: the bits of nnf_xht_f32 + nnf_gram_f32
+// either way.
+extern "C" int nnf_xht_gram_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V, int r,
+                                int64_t ldv, float* out, int64_t ldo, float* G, int64_t ldg, void* stream) {
+    if (!ctx || !V || !G || r < 1 || n < 1 || ldv < n || ldg < r) return NNF_ERR_ARG;
+    nnf_gram_ride ride{G, ldg, nullptr, false};
+    nnf_ws_cursor cur(ctx);
+    const int rc = nnf_xht_impl(ctx, cur, X, m, n, ldx, V, r, ldv, out, ldo, (hipStream_t)stream, &ride);
+    if (rc != NNF_OK || ride.rode) return rc;
+    nnf_ws_cursor gcur(ctx);   // (same stream: the Gram takes the workspace the cross product has finished with)
+    return nnf_gram_impl(ctx, gcur, V, r, n, ldv, G, ldg, (hipStream_t)stream, nullptr);
 }

@@ -1,6 +1,6 @@
 // W^T X: out[r x n] = Ut[r x m] * X[m x n]  (nmf.py:433), split over m, the slabs added by k_reduce.hip.
 // The design shared with X H^T, the Gram and the cost pass is described at the head of k_stream_common.h.
-#include "k_stream_common.h"
+#include "k_gram_body.h"
 #ifndef XTY_BIG_WG
 #define XTY_BIG_WG 2   // resident workgroups per CU the W^T X kernel of five or six rank tiles is compiled for (A/B: tools/abl_build.sh)
 #endif
@@ -14,15 +14,16 @@ NNF_BUILD_FLAGS(k_xty, "XTY_BIG_WG=" NNF_STR(XTY_BIG_WG))
 // REM > 0: rank = 16*MT + (1..REM) -- the MT full 16-row tiles run on MFMA, the REM leftover rows on the VALU pipe, which
 // is otherwise idle here (fp32 MFMA and fp32 VALU have the same peak on gfx950, so padding r=50 to 64 would burn 22 % of
 // the MFMA time on zeros).  The leftover rows' operand is the (MT+1)-th tile of the same LDS image, read as a broadcast.
+// bid: the workgroup's index in the cross-product grid; ldsA: its two chunk images
 template <int MT, int REM, bool VEC>
-__global__ __launch_bounds__(256, (nnf_xty_wg_per_cu(MT, REM, XTY_BIG_WG))) void nnf_xty_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
-                                                         const float* __restrict__ Ut, int64_t ldu, int r,
-                                                         float* __restrict__ slabs, int64_t ldp, int ncb, int nsplit,
-                                                         int64_t rows_per_split, int a_vec_ok) {
+__device__ __forceinline__ void nnf_xty_body(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+                                             const float* __restrict__ Ut, int64_t ldu, int r,
+                                             float* __restrict__ slabs, int64_t ldp, int ncb, int nsplit,
+                                             int64_t rows_per_split, int a_vec_ok, int bid,
+                                             f32x4 (*ldsA)[(MT + (REM > 0 ? 1 : 0)) * 256]) {
     constexpr int MTA = MT + (REM > 0 ? 1 : 0);   // tiles staged in LDS
-    __shared__ f32x4 ldsA[2][MTA * 256];
     int ks, cb;
-    nnf_xcd_map(blockIdx.x, ncb, ks, cb);
+    nnf_xcd_map(bid, ncb, ks, cb);
     if (ks >= nsplit) return;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int jj = lane & 15, g = lane >> 4;
@@ -125,20 +126,72 @@ __global__ __launch_bounds__(256, (nnf_xty_wg_per_cu(MT, REM, XTY_BIG_WG))) void
     }
 }
 
-// plan (k_stream_plan.h; a refusal launches nothing), report, carve, launch, reduce
+template <int MT, int REM, bool VEC>
+__global__ __launch_bounds__(256, (nnf_xty_wg_per_cu(MT, REM, XTY_BIG_WG))) void nnf_xty_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+                                                         const float* __restrict__ Ut, int64_t ldu, int r,
+                                                         float* __restrict__ slabs, int64_t ldp, int ncb, int nsplit,
+                                                         int64_t rows_per_split, int a_vec_ok) {
+    __shared__ f32x4 ldsA[2][(MT + (REM > 0 ? 1 : 0)) * 256];
+    nnf_xty_body<MT, REM, VEC>(X, m, n, ldx, Ut, ldu, r, slabs, ldp, ncb, nsplit, rows_per_split, a_vec_ok, (int)blockIdx.x, ldsA);
+}
+
+// W^T X with the Gram of its left factor riding in the same launch (nnf_xty_gram_f32): workgroups [0, main_grid) are the cross
+// product's, workgroup main_grid + s forms split s of Ut Ut^T (k_gram_body.h) in the same LDS -- the Gram stages the same
+// MT + (REM > 0) tiles of Ut.  Same bodies, same plans: every slab is the bits the two launches of their own write.
+template <int MT, int REM, bool VEC>
+__global__ __launch_bounds__(256, (nnf_xty_wg_per_cu(MT, REM, XTY_BIG_WG))) void nnf_xty_gram_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+                                                         const float* __restrict__ Ut, int64_t ldu, int r,
+                                                         float* __restrict__ slabs, int64_t ldp, int ncb, int nsplit,
+                                                         int64_t rows_per_split, int a_vec_ok, int main_grid,
+                                                         float* __restrict__ gslabs, int64_t g_kps) {
+    constexpr int MTA = MT + (REM > 0 ? 1 : 0);
+    __shared__ f32x4 ldsA[2][MTA * 256];
+    const int b = (int)blockIdx.x;
+    if (b < main_grid)
+        nnf_xty_body<MT, REM, VEC>(X, m, n, ldx, Ut, ldu, r, slabs, ldp, ncb, nsplit, rows_per_split, a_vec_ok, b, ldsA);
+    else
+        nnf_gram_body<MTA>(Ut, r, m, ldu, gslabs, g_kps, a_vec_ok, b - main_grid, ldsA);
+}
+
+// plan (k_stream_plan.h; a refusal launches nothing), report, carve, launch, reduce.  ride: the Gram of Ut asked to come along
+// (nnf_plan_rider decides; where it does not ride, ride->rode stays false and the caller runs the Gram on its own).
 template <int MT, int REM, bool VEC>
 static int launch_xty(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int r,
-                      int64_t ldu, float* out, int64_t ldo, hipStream_t st) {
-    const nnf_split_plan pl = nnf_plan_xty(ctx->num_cus, m, n, ldx, r, nnf_rank_tiles{MT, REM}, XTY_BIG_WG, cur.remaining());
+                      int64_t ldu, float* out, int64_t ldo, hipStream_t st, nnf_gram_ride* ride) {
+    const size_t free_bytes = cur.remaining();
+    const nnf_split_plan pl = nnf_plan_xty(ctx->num_cus, m, n, ldx, r, nnf_rank_tiles{MT, REM}, XTY_BIG_WG, free_bytes);
     if (pl.status != NNF_OK) return pl.status;
     if (nnf_plan_debug()) nnf_report_xty(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, pl);
     const int ncb = (int)nnf_cdiv(n, 256), nsplit = (int)pl.nsplit;
     const int64_t ldp = nnf_rup(n, 4), slab_elems = (int64_t)r * ldp;
+    const int a_vec_ok = x_vec_ok(Ut, ldu) ? 1 : 0;
+    const int main_grid = nnf_split_grid(nsplit, ncb);
+    nnf_gram_plan gp{};
+    nnf_rider_plan rp{};
+    if (ride) {   // the Gram's plan as a call of its own makes it: against the whole free workspace
+        gp = nnf_plan_gram(ctx->num_cus, r, m, ride->ldg == r, a_vec_ok, free_bytes);
+        rp = nnf_plan_rider(main_grid, (size_t)nsplit * slab_elems * 4, gp, r, MT + (REM > 0 ? 1 : 0), free_bytes);
+        if (nnf_plan_debug()) nnf_report_rider(stderr, "xty_gram", rp);
+    }
     float* slabs = (float*)cur.take((size_t)nsplit * slab_elems * 4);
     if (!slabs) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan counted them)
-    const int a_vec_ok = x_vec_ok(Ut, ldu) ? 1 : 0;
+    if (ride && rp.rides) {
+        if (nnf_plan_debug()) nnf_report_gram(stderr, r, m, gp);
+        float* gslabs = (float*)cur.take(rp.rider_bytes);
+        if (!gslabs) return NNF_ERR_WORKSPACE;   // (cannot happen: nnf_plan_rider counted both carves)
+        nnf_probe(ctx, NNF_PROBE_XTY, 0, st);   // measurement hook: the main kernel, now with its rider (bench.py)
+        hipLaunchKernelGGL((nnf_xty_gram_kernel<MT, REM, VEC>), dim3((int)rp.grid), dim3(256), 0, st, X, m, n, ldx, Ut, ldu, r,
+                           slabs, ldp, ncb, nsplit, pl.rows_per_split, a_vec_ok, main_grid, gslabs, gp.kps);
+        NNF_CHECK_LAUNCH();
+        nnf_probe(ctx, NNF_PROBE_XTY, 1, st);
+        const nnf_reduce_set sets[2] = {
+            nnf_plan_reduce_set(slabs, nsplit, slab_elems, r, n, ldp, out, ldo),
+            nnf_plan_reduce_set(gslabs, (int)gp.nsplit, (int64_t)r * r, r, r, r, ride->G, ride->ldg, ride->G64)};
+        ride->rode = true;
+        return nnf_launch_reduce_sets(sets, 2, st);
+    }
     nnf_probe(ctx, NNF_PROBE_XTY, 0, st);   // measurement hook: the main kernel alone (bench.py)
-    hipLaunchKernelGGL((nnf_xty_kernel<MT, REM, VEC>), dim3(nnf_split_grid(nsplit, ncb)), dim3(256), 0, st, X, m, n, ldx, Ut, ldu, r,
+    hipLaunchKernelGGL((nnf_xty_kernel<MT, REM, VEC>), dim3(main_grid), dim3(256), 0, st, X, m, n, ldx, Ut, ldu, r,
                        slabs, ldp, ncb, nsplit, pl.rows_per_split, a_vec_ok);
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_XTY, 1, st);
@@ -146,9 +199,9 @@ static int launch_xty(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t 
 }
 
 int nnf_xty_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut,
-                 int r, int64_t ldu, float* out, int64_t ldo, hipStream_t st) {
+                 int r, int64_t ldu, float* out, int64_t ldo, hipStream_t st, nnf_gram_ride* ride) {
     if (!ctx || !X || !Ut || !out || m < 1 || n < 1 || r < 1 || ldx < n || ldu < m || ldo < n) return NNF_ERR_ARG;
-    if (r > NNF_MAX_RANK)   // the rows of the result are independent of each other
+    if (r > NNF_MAX_RANK)   // the rows of the result are independent of each other (no rider: the Gram runs in blocks there)
         return nnf_rank_passes(r, cur, [&](int k0, int rc) {
             return nnf_xty_impl(ctx, cur, X, m, n, ldx, Ut + (int64_t)k0 * ldu, rc, ldu, out + (int64_t)k0 * ldo, ldo, st);
         });
@@ -157,7 +210,7 @@ int nnf_xty_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, in
     return nnf_dispatch<8>(t.MT, [&](auto mt) -> int {
         constexpr int MT = decltype(mt)::value;
         const auto go = [&](auto rem, auto v) {
-            return launch_xty<MT, decltype(rem)::value, decltype(v)::value>(ctx, cur, X, m, n, ldx, Ut, r, ldu, out, ldo, st);
+            return launch_xty<MT, decltype(rem)::value, decltype(v)::value>(ctx, cur, X, m, n, ldx, Ut, r, ldu, out, ldo, st, ride);
         };
         if (!vec) return go(nnf_int<0>{}, std::false_type{});
         if (t.REM == 2) return go(nnf_int<2>{}, std::true_type{});
@@ -170,4 +223,17 @@ extern "C" int nnf_xty_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, i
     if (!ctx) return NNF_ERR_ARG;
     nnf_ws_cursor cur(ctx);
     return nnf_xty_impl(ctx, cur, X, m, n, ldx, Ut, r, ldu, out, ldo, (hipStream_t)stream);
+}
+// W^T X and the Gram of its left factor, G = Ut Ut^T (pitch ldg; G64: its fp64 sums, may be NULL), in one main launch and one
+// reduction where nnf_plan_rider lets the Gram ride, as two calls otherwise: the bits of nnf_xty_f32 + nnf_gram_f32 /
+// nnf_gram_f64_f32 either way.
+extern "C" int nnf_xty_gram_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int r,
+                                int64_t ldu, float* out, int64_t ldo, float* G, int64_t ldg, double* G64, void* stream) {
+    if (!ctx || !Ut || !G || r < 1 || m < 1 || ldu < m || ldg < r) return NNF_ERR_ARG;
+    nnf_gram_ride ride{G, ldg, G64, false};
+    nnf_ws_cursor cur(ctx);
+    const int rc = nnf_xty_impl(ctx, cur, X, m, n, ldx, Ut, r, ldu, out, ldo, (hipStream_t)stream, &ride);
+    if (rc != NNF_OK || ride.rode) return rc;
+    nnf_ws_cursor gcur(ctx);   // (same stream: the Gram takes the workspace the cross product has finished with)
+    return nnf_gram_impl(ctx, gcur, Ut, r, m, ldu, G, ldg, (hipStream_t)stream, G64);
 }

@@ -122,6 +122,32 @@ __device__ __forceinline__ void nnf_xcd_map(int bid, int members, int& group, in
 int nnf_launch_reduce_slabs(const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols, int64_t lds,
                             float* out, int64_t ldo, hipStream_t st, double* out64 = nullptr);   // out64: the sums before rounding (rows x cols, contiguous)
 
+// One set of slabs, where its sums go and the form the reduction takes for it (nnf_plan_reduce_set, k_reduce.hip): lg > 0: 2^lg
+// threads per element; else vec4: four columns per thread; else one element per thread.  blocks: its workgroups; block0: where
+// they start in a launch shared with other sets (nnf_launch_reduce_sets fills it in).
+#define NNF_REDUCE_MAX_SETS 3
+struct nnf_reduce_set {
+    const float* slabs;
+    float* out;
+    double* out64;
+    int64_t slab_stride, cols, lds, ldo;
+    int nslab, rows;
+    int lg, vec4, blocks, block0;
+};
+nnf_reduce_set nnf_plan_reduce_set(const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols, int64_t lds,
+                                   float* out, int64_t ldo, double* out64 = nullptr);
+// up to NNF_REDUCE_MAX_SETS planned sets in one launch; every set's sums are the bits nnf_launch_reduce_slabs gives it
+int nnf_launch_reduce_sets(const nnf_reduce_set* sets, int nsets, hipStream_t st);
+
+// the Gram that may ride in a cross-product launch (nnf_xty_gram_f32, nnf_xht_gram_f32): G (pitch ldg) and, if not null, its
+// fp64 sums; `rode` is set by the launcher that took it along -- otherwise the caller runs nnf_gram_impl itself
+struct nnf_gram_ride {
+    float* G;
+    int64_t ldg;
+    double* G64;
+    bool rode;
+};
+
 // out[z] = A (p x q) B[z] (q x cols), z < batch: a rank-sized left operand staged in LDS (k_mu.hip)
 int nnf_small_gemm_launch(const float* A, int64_t lda, int p, int q, const float* B, int64_t ldb, int64_t cols, float* out,
                           int64_t ldo, int64_t batch, int64_t bstride, int64_t ostride, hipStream_t st);
@@ -139,8 +165,8 @@ int nnf_launch_mu_finish(const float* F, int64_t ldf, int r, int64_t cols, const
                          hipStream_t st);
 
 int nnf_xty_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut,
-                 int r, int64_t ldu, float* out, int64_t ldo, hipStream_t st);
+                 int r, int64_t ldu, float* out, int64_t ldo, hipStream_t st, nnf_gram_ride* ride = nullptr);
 int nnf_xht_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* V,
-                 int r, int64_t ldv, float* out, int64_t ldo, hipStream_t st);
+                 int r, int64_t ldv, float* out, int64_t ldo, hipStream_t st, nnf_gram_ride* ride = nullptr);
 int nnf_gram_impl(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* A, int r, int64_t K, int64_t lda, float* G, int64_t ldg,
                   hipStream_t st, double* G64 = nullptr);

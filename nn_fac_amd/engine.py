@@ -134,6 +134,41 @@ class Engine:
                                         _ld(O), self._stream()), "nnf_xty_f32")
         return O
 
+    def _chk_g64(self, G64, r, dev, what):
+        if G64 is not None and (G64.dtype != torch.float64 or not G64.is_contiguous() or G64.numel() < r * r or G64.device != dev):
+            raise EngineError(f"{what}: out64 must be a contiguous float64 device tensor of r*r elements")
+
+    def xty_gram(self, X, Ut, out=None, G=None, G64=None):
+        """xty(X, Ut, out) and gram(Ut, G, G64) in one main launch and one slab reduction (nnf_xty_gram_f32): the same bits as
+        the two calls.  Returns (Ut X, Ut Ut^T)."""
+        _chk2d(X, "xty_gram X"), _chk2d(Ut, "xty_gram Ut")
+        m, n = X.shape
+        r = Ut.shape[0]
+        if Ut.shape[1] != m:
+            raise EngineError("xty_gram: shape mismatch")
+        O = out if out is not None else torch.empty((r, n), dtype=torch.float32, device=X.device)
+        G = G if G is not None else torch.empty((r, r), dtype=torch.float32, device=X.device)
+        _chk2d(O, "xty_gram out"), _chk2d(G, "xty_gram G")
+        self._chk_g64(G64, r, X.device, "xty_gram")
+        _lib.check(self.lib.nnf_xty_gram_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), r, _ld(Ut), _ptr(O), _ld(O), _ptr(G), _ld(G),
+                                             _ptr(G64) if G64 is not None else None, self._stream()), "nnf_xty_gram_f32")
+        return O, G
+
+    def xht_gram(self, X, V, out=None, G=None):
+        """xht(X, V, out) and gram(V, G) in one main launch and one slab reduction (nnf_xht_gram_f32): the same bits as the two
+        calls.  Returns (V X^T, V V^T)."""
+        _chk2d(X, "xht_gram X"), _chk2d(V, "xht_gram V")
+        m, n = X.shape
+        r = V.shape[0]
+        if V.shape[1] != n:
+            raise EngineError("xht_gram: shape mismatch")
+        O = out if out is not None else torch.empty((r, m), dtype=torch.float32, device=X.device)
+        G = G if G is not None else torch.empty((r, r), dtype=torch.float32, device=X.device)
+        _chk2d(O, "xht_gram out"), _chk2d(G, "xht_gram G")
+        _lib.check(self.lib.nnf_xht_gram_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(V), r, _ld(V), _ptr(O), _ld(O), _ptr(G), _ld(G),
+                                             self._stream()), "nnf_xht_gram_f32")
+        return O, G
+
     def frob_resid(self, X, Ut, V, out=None):
         """sum (X - Ut^T V)^2 as a 1-element float64 device tensor."""
         _chk2d(X, "frob X"), _chk2d(Ut, "frob Ut"), _chk2d(V, "frob V")

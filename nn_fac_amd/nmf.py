@@ -167,7 +167,8 @@ def _gram_on_side(ws, eng, A, out):
     on before `out` is used -- None: it ran inline (CPU test doubles, buffers without a side stream).  Only the SHORT factor's
     Gram (V V^T: r x n) goes to the side stream: the Gram of the long one (U^T U, 20 MB at config B) took 82 us there next to
     W^T X instead of 5.4 us alone and cost that kernel 5 % (profiles/r02_B_kernel_stats.txt) -- it is launched in line, in
-    front of W^T X (`inline=True`)."""
+    front of W^T X (`inline=True`).  Only engines without the fused entries (Engine.xht_gram / xty_gram, where the Gram rides in
+    the cross product's own launch) come here."""
     side = ws.side_stream
     if side is None or not isinstance(eng, _engine.Engine):
         eng.gram(A, out=out)
@@ -476,10 +477,13 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
     if 0 not in fixed_modes:
         if update_rule == "hals":
             t0 = tic(dev, alpha)
-            done = _gram_on_side(ws, eng, V, ws.G)      # VVt (nmf.py:407)
-            eng.xht(X, V, out=ws.VMt)                   # VMt  (nmf.py:408)
-            if done is not None:
-                torch.cuda.current_stream(dev).wait_event(done)
+            if getattr(eng, "xht_gram", None) is not None:
+                eng.xht_gram(X, V, out=ws.VMt, G=ws.G)      # VMt and VVt (nmf.py:407-408): the Gram rides in the X H^T launch
+            else:                                           # engines without the fused entry (the CPU tests' doubles)
+                done = _gram_on_side(ws, eng, V, ws.G)      # VVt (nmf.py:407)
+                eng.xht(X, V, out=ws.VMt)                   # VMt  (nmf.py:408)
+                if done is not None:
+                    torch.cuda.current_stream(dev).wait_event(done)
             timer = toc(dev, t0)
             if before_u_solve is not None:
                 before_u_solve()
@@ -521,11 +525,14 @@ def _one_nmf_step_dev(eng, ws, X, rank, Ut_in, V_in, update_rule, beta, sparsity
         if update_rule == "hals":
             t0 = tic(dev, alpha)
             ws.g64_ok = ws.G64 is not None and isinstance(eng, _engine.Engine)
-            if ws.g64_ok:
-                eng.gram(Ut, out=ws.G2, out64=ws.G64)   # UtU  (nmf.py:432) -- in line: see _gram_on_side; + its fp64 sums
+            if getattr(eng, "xty_gram", None) is not None:  # UtM and UtU (nmf.py:432-433): the Gram rides in the W^T X launch
+                eng.xty_gram(X, Ut, out=ws.UtM, G=ws.G2, G64=ws.G64 if ws.g64_ok else None)
             else:
-                eng.gram(Ut, out=ws.G2)
-            eng.xty(X, Ut, out=ws.UtM)                  # UtM  (nmf.py:433)
+                if ws.g64_ok:
+                    eng.gram(Ut, out=ws.G2, out64=ws.G64)   # UtU  (nmf.py:432) -- in line: see _gram_on_side; + its fp64 sums
+                else:
+                    eng.gram(Ut, out=ws.G2)
+                eng.xty(X, Ut, out=ws.UtM)                  # UtM  (nmf.py:433)
             if sharded:                                 # sum over the row blocks: r x n and r x r over xGMI, one collective
                 _dist.allreduce_(ws.v_terms, group)
                 if ws.g64_ok:                           # the fp64 sums of the Gram for the identity cost: r x r doubles

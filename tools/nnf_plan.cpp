@@ -21,6 +21,12 @@
 //                                     adds ws_bytes=
 //                          gram <CUs> <K> <K> <r> <pitch of A> 0 <workspace bytes> [align=] [ldg=]     (any rank; ldg: the pitch of
 //                                     G, default r); adds ws_max= ws_bytes=
+//                          xty_gram | xht_gram <CUs> <m> <n> <r> <row pitch of X> 0 <workspace bytes> [align=] [fld=] [falign=] [ldg=]
+//                                     the cross product with the Gram of its factor riding in the launch (nnf_plan_rider; fld /
+//                                     falign: the factor's pitch and offset from a 16-byte boundary, ldg: the pitch of G):
+//                                     "[nnf plan] xty_gram rides= main_grid= rider_grid= rider_offset= grid= main_bytes=
+//                                     rider_bytes= rider_ws_off= ws_bytes=", then gram_nsplit= gram_kps= gram_bytes= of the Gram's
+//                                     own plan; rides=0: the two run as calls of their own
 //                          cost <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [align=] [op=] [kr=] [pin=] [csplit=]
 //                                     op: ratio_kl | ratio_gen | prod (default: the cost of that beta); kr: the Khatri-Rao inner
 //                                     length of the CP cost (T as an (I J) x K matrix: m = I J, n = K, kr = J); pin=1: a later
@@ -200,6 +206,44 @@ int main(int argc, char** argv) {
             snprintf(more, sizeof more, " ws_max=%lld ws_bytes=%zu", (long long)p.ws_max,
                      p.status == NNF_OK && p.form >= NNF_GRAM_SLABS ? (size_t)(p.nsplit * r * r * 4) : (size_t)0);
             if ((status = p.status) == NNF_OK) nnf_report_gram(stdout, (int)r, m, p, more);
+        } else if (strcmp(name, "xty_gram") == 0 || strcmp(name, "xht_gram") == 0) {
+            // the fused launch of a cross product and its factor's Gram (nnf_plan_rider): both plans as their own calls make them,
+            // then the grid and the carve of the launch that holds both
+            const bool xty = name[1] == 't';
+            const long long K = xty ? m : n, fld = key_of(rest, "fld", K), ldg = key_of(rest, "ldg", r);
+            const bool fvec = key_of(rest, "falign", 0) % 4 == 0 && fld % 4 == 0;   // x_vec_ok of the factor
+            const nnf_rank_tiles t = xty ? nnf_xty_tiles((int)r, vec) : nnf_xht_tiles((int)r, vec);
+            const nnf_gram_plan g = nnf_plan_gram((int)C, (int)r, K, ldg == r, fvec, cur.remaining());
+            long long main_grid = -1;
+            size_t main_bytes = 0;
+            bool apart = false;   // forms of the cross product that take no rider: the two run as calls of their own
+            if (fld < K || ldg < r) {
+                status = NNF_ERR_ARG;
+            } else if (r > NNF_MAX_RANK || (!xty && nnf_xht_use_lds(t, vec))) {   // rank passes, the LDS-staged X H^T
+                apart = true;
+            } else if (xty) {
+                const nnf_split_plan p = nnf_plan_xty((int)C, m, n, ld, (int)r, t, 2, cur.remaining());
+                if ((status = p.status) == NNF_OK) {
+                    main_grid = nnf_split_grid(p.nsplit, (int)nnf_cdiv(n, 256));
+                    main_bytes = (size_t)(p.nsplit * r * nnf_rup(n, 4) * 4);
+                }
+            } else if (nnf_xht_offsets_ok(n, ld)) {
+                const nnf_xht_plan p = nnf_plan_xht_direct((int)C, m, n, (int)r, t, -1, 1, cur.remaining());
+                if (p.covers(m)) {
+                    status = NNF_OK;
+                    main_grid = p.grid;
+                    main_bytes = p.tail_parts > 0 ? (size_t)p.tail_parts * r * p.tail_ld * 4 : 0;
+                }
+            }
+            if (main_grid >= 0) {
+                const nnf_rider_plan rp = nnf_plan_rider(main_grid, main_bytes, g, (int)r, t.MT + (t.REM > 0), cur.remaining());
+                snprintf(more, sizeof more, " gram_nsplit=%lld gram_kps=%lld gram_bytes=%zu", (long long)g.nsplit, (long long)g.kps,
+                         g.status == NNF_OK && g.form >= NNF_GRAM_SLABS ? (size_t)(g.nsplit * r * r * 4) : (size_t)0);
+                nnf_report_rider(stdout, name, rp, more);
+            } else if (apart) {
+                status = NNF_OK;
+                nnf_report_rider(stdout, name, nnf_rider_plan{});
+            }
         } else if (r > NNF_MAX_RANK) {
         } else if (strcmp(name, "mttkrp_seg") == 0) {   // m = rows, n = segment length, ld = row pitch
             const long long nseg = key_of(rest, "nseg", 1), segstride = key_of(rest, "segstride", n);
