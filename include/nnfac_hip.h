@@ -19,6 +19,36 @@
  *   - a context is bound to one device and must not be used from two threads at once; one context
  *     per stream if calls on different streams may overlap (they share the workspace otherwise).
  *   - rank limit: 1 <= r <= 128 (NNF_ERR_UNSUPPORTED above).
+ *
+ * Non-finite operands
+ *   Every projection of the reference is np.maximum (nnls.py:162-170, mu.py:84-97, deep_mu.py:11) or np.minimum (ntd.py:613),
+ *   and both keep a NaN: one NaN in a solve's operands makes that column of the factor NaN, the sum of squared steps NaN and
+ *   ends hals_nnls_acc after that sweep (`eps >= delta * eps0` is false); one NaN in X makes a row of an MU update NaN, and
+ *   nmf() returns all-NaN factors and NaN costs two iterations later.  NaN and Inf are ordinary data to every kernel here (no
+ *   address, trip count or wait depends on an operand's value; a stopping decision is taken by every workgroup from the one
+ *   exchanged total), and a NaN is never projected away.  Against the reference operation evaluated in fp64 on the same fp32
+ *   operands (magnitudes such that nothing overflows fp32 that does not overflow fp64):
+ *     1. an output column of a solve, or a row / column of an MU update, that the reference leaves all finite is within the
+ *        kernel's tolerance;
+ *     2. in any other column or row every entry that is NaN in the reference is NaN here, every entry that is non-finite
+ *        there is non-finite here, and an entry the reference leaves finite is within tolerance or NaN -- a kernel may poison
+ *        a whole column, it never returns it clean;
+ *     3. the status of a solve: cnt is the reference's, eps is NaN exactly when the reference's is, eps0 is within tolerance
+ *        or non-finite of the same kind, err stays 0;
+ *     4. blind sweeps: nodelta[s] is NaN exactly for the sweeps where the reference's sum is;   5. snapshots obey 2;
+ *     6. the cost entries (frob_resid, betadiv, cp3_betadiv, cp3_partial_cost, nmf_gram_cost: out[0] with out[1] = 1) return
+ *        NaN when the reference's sum is NaN, frob_resid_rows in exactly the affected rows;
+ *     7. the products (xty, xht, gram and their fused forms, mttkrp3, mttkrp3_from_partial, ttm3, small_gemm, mu_left_num,
+ *        mu_right_accum) have no projection: the set of NaN outputs equals the reference's entry for entry (0 * NaN counts,
+ *        as in numpy), every other entry is within tolerance.
+ *   The sweep kernels whose row update is ONE v_max_f32 -- an instruction that returns the operand that is not NaN --
+ *   (k_hals_wave.hip, the resident rank 33 .. 52 form of k_hals_fast.hip, k_hals_mfma.hip) run that form on finite data only:
+ *   each has a second form of the row update (a compare-and-select, two instructions) and picks it, once per launch, where a
+ *   non-finite value can reach a row update -- a wave of the wave kernel from its start values, right-hand side and first
+ *   residual; a wave of the lane kernel from its loaded column (start values, scaled right-hand side) and the prep kernel's
+ *   flag "the Gram is finite and has no zero on its diagonal"; a workgroup of the matrix-core kernel from its first residual.
+ *   Finite operands stay finite, so the choice costs nothing per row; a finite problem whose fp32 intermediates overflow is
+ *   outside this contract (tests/test_gpu_nonfinite.py).
  */
 #ifndef NNFAC_HIP_H
 #define NNFAC_HIP_H
@@ -457,8 +487,9 @@ int nnf_hals_group_max_columns(nnf_ctx* ctx, int r, int64_t* columns_out);
  * max_group_cols: the caller's bound on the group lengths, <= NNF_HALS_GROUP_MAX_COLUMNS (else NNF_ERR_UNSUPPORTED).  Groups of
  * one column (K diagonal updates in one launch) and empty groups are fine (an empty group changes nothing and reports eps 0,
  * cnt max_sweeps + 1, eps0 0); max_sweeps = 1 on a copy is a probe sweep, max_sweeps = 0 leaves V alone and reports eps 1,
- * cnt 1, eps0 0.  A NaN in a group's operands is not projected away: as with np.maximum it stays in that group's V, makes its
- * sum of squared steps NaN and ends its loop after that sweep (eps NaN); the other groups do not see it. */
+ * cnt 1, eps0 0.  A NaN in a group's operands is not projected away ("Non-finite operands" at the head of this file, which
+ * every solve obeys): as with np.maximum it stays in that group's V, makes its sum of squared steps NaN and ends its loop after
+ * that sweep (eps NaN); the other groups do not see it. */
 int nnf_hals_solve_group_f32(nnf_ctx* ctx, const float* UtM, int64_t ldm, const float* UtU, int64_t ldg, int64_t gstride,
                              float* V, int64_t ldv, int r, const int64_t* off, int ngroups, int64_t max_group_cols,
                              int64_t total_cols, int max_sweeps, double delta, double* status_f64, void* stream);

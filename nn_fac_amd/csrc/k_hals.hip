@@ -27,10 +27,20 @@ __global__ void nnf_hals_prep_kernel(const float* __restrict__ UtU, int64_t ldg,
     const int a = blockIdx.x;                   // 0 .. RP-1
     const float da = (a < r) ? UtU[(int64_t)a * ldg + a] : 0.f;
     const float dia = (da != 0.f) ? (float)(1.0 / (double)da) : 0.f;
+    int odd = 0;                                // this row holds an Inf or a NaN
     for (int b = threadIdx.x; b < RS; b += blockDim.x) {
         const float g = (a < r && b < r) ? UtU[(int64_t)a * ldg + b] : 0.f;
+        odd |= (fabsf(g) < __builtin_inff()) ? 0 : 1;
         Gp[a * RS + b] = g;
         if (Gs) Gs[a * RS + b] = g * dia;      // rows scaled by 1/diag (rows with a zero diagonal: all zero), same padding
+    }
+    // The row-scaled Gram exists for padded ranks 33 .. 52 only, in rows of 64 floats of which the sweep reads at most 52
+    // (hals_sweep_column_xy): its last float says whether the row is all finite -- NaN if not, for the resident lane kernel,
+    // whose one-instruction row update runs on finite data only (nnfac_hip.h "Non-finite operands").  Every workgroup looks at
+    // the row it copies anyway; a scan of the whole Gram by workgroup 0 was 20 more round trips in front of the solve.
+    if (Gs) {
+        const int row_odd = __syncthreads_or(odd);
+        if (threadIdx.x == 0 && RP < RS) Gs[a * RS + RS - 1] = row_odd ? __builtin_nanf("") : 0.f;
     }
     if (blockIdx.x != 0) return;
     for (int k = threadIdx.x; k < RP; k += blockDim.x) {
@@ -129,7 +139,10 @@ __global__ __launch_bounds__(128) void nnf_hals_generic_kernel(const float* __re
                 } else
                 for (int i = 0; i < r; ++i) dot = fmaf(Gp[k * RP + i], mycol[i * cs], dot);
                 const float vk = mycol[k * cs];
-                float step = fmaxf((UtM[(int64_t)k * ldm + col0] - dot - sp) * di, -vk);
+                // np.maximum(x, -v), NaN included (nnls.py:162-170; nnfac_hip.h "Non-finite operands"): fmaxf would drop a NaN
+                // of x, write a clean 0 and go on sweeping
+                const float x = (UtM[(int64_t)k * ldm + col0] - dot - sp) * di;
+                float step = !(x < -vk) ? x : -vk;
                 if (!active) step = 0.f;
                 if constexpr (LPC > 1) {
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // (every lane of the quad has read v[k])
@@ -147,10 +160,11 @@ __global__ __launch_bounds__(128) void nnf_hals_generic_kernel(const float* __re
                 const float vk = mycol[k * cs];
                 double vmax = 0.0;
                 if (flags & NNF_HALS_NONZERO) {
-                    for (int i = q; i < r; i += LPC) vmax = fmax(vmax, (double)mycol[i * cs]);
+                    // np.max(V) (nnls.py:174): a NaN anywhere in V is the maximum
+                    for (int i = q; i < r; i += LPC) vmax = hals_nanmax(vmax, (double)mycol[i * cs]);
                     if constexpr (LPC > 1) {
-                        vmax = fmax(vmax, __shfl_xor(vmax, 1, 64));
-                        vmax = fmax(vmax, __shfl_xor(vmax, 2, 64));
+                        vmax = hals_nanmax(vmax, __shfl_xor(vmax, 1, 64));
+                        vmax = hals_nanmax(vmax, __shfl_xor(vmax, 2, 64));
                     }
                 }
                 double mine[3] = {owner ? (double)vk * (double)vk : 0.0, (owner && vk != 0.f) ? 1.0 : 0.0,
@@ -160,10 +174,10 @@ __global__ __launch_bounds__(128) void nnf_hals_generic_kernel(const float* __re
                 const double b1 = nnf_block_sum_f64(mine[1], red);
                 // block max of mine[2]
                 double bm = mine[2];
-                for (int o = 32; o > 0; o >>= 1) { const double y = __shfl_down(bm, o, 64); bm = y > bm ? y : bm; }
+                for (int o = 32; o > 0; o >>= 1) bm = hals_nanmax(bm, __shfl_down(bm, o, 64));
                 if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bm;
                 __syncthreads();
-                bm = red[0] > red[1] ? red[0] : red[1];
+                bm = hals_nanmax(red[0], red[1]);
                 __syncthreads();
                 double pub[3] = {b0, b1, bm};
                 if (threadIdx.x != 0) { pub[0] = 0; pub[1] = 0; }
@@ -549,7 +563,8 @@ __global__ __launch_bounds__(256) void nnf_hals_row_update_kernel(const float* _
         if (di != 0.f) {                                  // nnls.py:160: a row with a zero Gram diagonal is left alone
             float dot = 0.f;
             for (int i = 0; i < r; ++i) dot = fmaf(UtU[(int64_t)k * ldg + i], V[(int64_t)i * ldv + col], dot);
-            const float step = fmaxf((UtM[(int64_t)k * ldm + col] - dot - sp) * di, -vk);
+            const float x = (UtM[(int64_t)k * ldm + col] - dot - sp) * di;
+            const float step = !(x < -vk) ? x : -vk;      // np.maximum(x, -v), NaN included (nnls.py:162-170)
             vk += step;
             V[(int64_t)k * ldv + col] = vk;
             nd += (double)step * (double)step;

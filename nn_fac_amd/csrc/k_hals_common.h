@@ -16,7 +16,10 @@ struct hals_sync {
     unsigned epoch;      // fast path: per-call tag salt (nnf_ctx::hals_epoch)
 };
 
-// Exchange up to 3 doubles between all workgroups; returns sums of v0, v1 and the max of v2 in out[0..2].
+// np.max of two values: a NaN on either side is the result (`y > x ? y : x` alone would drop a NaN y)
+__device__ __forceinline__ double hals_nanmax(double x, double y) { return (y > x || y != y) ? y : x; }
+
+// Exchange up to 3 doubles between all workgroups; returns sums of v0, v1 and the max of v2 (np.max: NaN kept) in out[0..2].
 // `epoch` counts barrier episodes from 1.  Returns false on timeout (wave-uniform after the barrier).
 template <int NV>
 __device__ __forceinline__ bool grid_exchange(const hals_sync& sy, unsigned epoch, int nblocks, const double (&mine)[NV],
@@ -50,7 +53,7 @@ __device__ __forceinline__ bool grid_exchange(const hals_sync& sy, unsigned epoc
             const double x = __builtin_bit_cast(
                 double, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(base + (size_t)b * 4 + i),
                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if (i == 2) s[i] = x > s[i] ? x : s[i]; else s[i] += x;
+            if (i == 2) s[i] = hals_nanmax(s[i], x); else s[i] += x;
         }
     }
     // block reduce (fixed order) and broadcast through LDS
@@ -61,7 +64,7 @@ __device__ __forceinline__ bool grid_exchange(const hals_sync& sy, unsigned epoc
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const double y = __shfl_down(v, o, 64);
-            if (i == 2) v = y > v ? y : v; else v += y;
+            if (i == 2) v = hals_nanmax(v, y); else v += y;
         }
         if ((threadIdx.x & 63) == 0) red[w * NV + i] = v;
     }
@@ -71,7 +74,7 @@ __device__ __forceinline__ bool grid_exchange(const hals_sync& sy, unsigned epoc
         double v = red[i];
         for (int k = 1; k < nw; ++k) {
             const double y = red[k * NV + i];
-            if (i == 2) v = y > v ? y : v; else v += y;
+            if (i == 2) v = hals_nanmax(v, y); else v += y;
         }
         out[i] = v;
     }

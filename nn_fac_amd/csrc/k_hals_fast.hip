@@ -84,6 +84,11 @@ __device__ __forceinline__ f32x2 sg_pair(const sgbuf<W>& d, int p) {   // floats
 // part and the row bookkeeping -- so the single lgkmcnt(0) per row finds both in (or nearly in) the registers.
 // GUARD: some Gram diagonal is zero (rare).  Such a row must be left alone whatever it holds (nnls.py:160): d is
 // multiplied by the row's nz flag (0/1) fetched with the Y part.  Without GUARD there is no per-row flag at all.
+// GUARD is also the variant that keeps non-finite values as np.maximum does (nnfac_hip.h "Non-finite operands"): v_max_f32
+// returns the operand that is not NaN, so without GUARD a NaN x writes a clean v[k] = 0; with it d is a compare-and-select
+// (two instructions, NaN kept) and the nz flag is applied with v_mul_legacy_f32 (0 * anything = 0: a skipped row stays put next
+// to an Inf or NaN elsewhere in the column).  The streaming kernel always runs with GUARD; the resident one where a Gram
+// diagonal is zero or an operand is not finite (see nnf_hals_kernel).
 template <int R, bool GUARD, class MID>
 __device__ __forceinline__ float hals_sweep_column_xy(f32x2 (&v2)[R / 2], const float (&b)[R], const float* __restrict__ Gs,
                                                       const float* __restrict__ nzp, const MID& mid) {
@@ -135,9 +140,13 @@ __device__ __forceinline__ float hals_sweep_column_xy(f32x2 (&v2)[R / 2], const 
         const f32x2 a = a0 + a1;
         const float vk = v2[k / 2][k & 1];
         const float x = b[k] - (a[0] + a[1]);
-        float dl;   // max(x, -v[k]) in one instruction (fmaxf adds a canonicalising max for the negated operand)
-        asm("v_max_f32 %0, %1, -%2" : "=v"(dl) : "v"(x), "v"(vk));
-        if constexpr (GUARD) dl *= dv[cur][1];
+        float dl;
+        if constexpr (GUARD) {
+            const float sel = !(x < -vk) ? x : -vk;   // np.maximum(x, -v[k]), NaN included
+            asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(dl) : "s"(dv[cur][1]), "v"(sel));
+        } else {   // max(x, -v[k]) in one instruction (fmaxf adds a canonicalising max for the negated operand); finite operands only
+            asm("v_max_f32 %0, %1, -%2" : "=v"(dl) : "v"(x), "v"(vk));
+        }
         v2[k / 2][k & 1] = vk + dl;
         nd = fmaf(dl, dl, nd);
         asm volatile("" : "+v"(nd));  // finish this row's bookkeeping here (otherwise it is sunk to the end of the sweep)
@@ -212,9 +221,14 @@ __device__ __forceinline__ float hals_sweep_column(f32x2 (&v2)[R / 2], const flo
         const float vk = v2[k / 2][k & 1];
         // KEEPB: the resident column already holds UtM - sp.  A zero Gram diagonal (or a padded row) has di = 0: then
         // x = 0 and the row must stay untouched whatever its sign (nnls.py:160) -> force "keep" with a scalar-side test.
-        const float x = (KEEPB ? (bk - dot) : (bk - dot - sp)) * di;
+        // Non-finite values go the way np.maximum sends them (nnfac_hip.h "Non-finite operands"): a NaN t is kept (`t > 0` would
+        // clip it to a clean 0), and a row with di = 0 sees a residual of 0 whatever its all-zero Gram row made of an Inf
+        // elsewhere in the column (0 * Inf is NaN) -- one select on the scalar-side test; the arithmetic of a live row is untouched.
+        const bool skip = __builtin_bit_cast(unsigned, di) == 0u;
+        const float res = KEEPB ? (bk - dot) : (bk - dot - sp);
+        const float x = (skip ? 0.f : res) * di;
         const float t = vk + x;
-        const bool keep = (t > 0.f) | (__builtin_bit_cast(unsigned, di) == 0u);
+        const bool keep = !(t <= 0.f) | skip;
         const float vn = keep ? t : 0.f;
         const float step = keep ? x : -vk;
         v2[k / 2][k & 1] = vn;
@@ -250,9 +264,16 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
     const int ldvs4 = (int)(a.ldvs * 4);
     f32x2 v2[RP / 2];
     float b[KEEPB ? RP : 1];
+    // XY: the one-instruction row update (no GUARD) drops a NaN, so it runs on finite data only.  The streaming form always
+    // runs with GUARD, which keeps NaN and Inf.  The resident form -- config B's U-side solve -- decides once per launch, right
+    // after its column is loaded: 0 * x summed over the scaled right-hand side and the start values is 0 unless one of them is
+    // Inf or NaN (2 RP FMAs); the prep kernel leaves "this Gram row is finite" in the last float of every row of the scaled
+    // Gram (0, or NaN), which rides in the same sum -- one load per lane, in flight with the column's.
+    // Finite operands stay finite (fp32 overflow aside), so a wave that finds all of it finite keeps the one-instruction form.
+    bool plain = false;   // wave-uniform
     auto sweep = [&](int voff, const auto& mid) -> float {
         if constexpr (XY) {
-            return all_live ? hals_sweep_column_xy<RP, false>(v2, b, a.Gs, a.dinv, mid) : hals_sweep_column_xy<RP, true>(v2, b, a.Gs, a.dinv, mid);
+            return plain ? hals_sweep_column_xy<RP, false>(v2, b, a.Gs, a.dinv, mid) : hals_sweep_column_xy<RP, true>(v2, b, a.Gs, a.dinv, mid);
         } else {
             return hals_sweep_column<RP, KEEPB>(v2, b, rb, voff, ldm4, a.Gp, a.sp, mid);
         }
@@ -278,6 +299,17 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
     };
     const int voff0 = gtid < a.ncols ? (int)(gtid * 4) : (int)0x7ffffff0;
     if constexpr (RES) load_col(voff0);
+    if constexpr (RES && XY) {
+        static_assert(!XY || RP < 64, "the scaled Gram's rows have a spare last float");
+        float c = a.Gs[(threadIdx.x & 63) < RP ? (threadIdx.x & 63) * 64 + 63 : 63];   // one register, taken in the order of the loads
+#pragma unroll
+        for (int k = 0; k < RP; ++k) {
+            c = fmaf(v2[k / 2][k & 1], 0.f, c);
+            c = fmaf(b[k], 0.f, c);
+            asm volatile("" : "+v"(c));
+        }
+        plain = all_live && __ballot(!(c == 0.f)) == 0ull;
+    }
     // Sweep loop.  mode 1: fixed count, per-sweep local partials, nothing to decide.
     // mode 0, resident columns, RP <= 64 (240 VGPRs at RP = 64, no spills): lag-one speculation.  After sweep s the workgroup publishes its partial and goes
     // straight on to sweep s+1 in registers; only then does it collect the global sum of sweep s (published by every

@@ -174,21 +174,30 @@ struct mfma_sweeper {
 
     // The VALU work of k-block kb on its residuals w: the four row updates of nnls.py:162-170 in order, the bookkeeping, the
     // leftover rows' push.  Leaves the steps in stp.  l[0..5] = -G'[k0+i][k0+j], j < i.
+    // GUARD is also the variant that keeps non-finite values as np.maximum does (nnfac_hip.h "Non-finite operands"): v_max_f32
+    // returns the operand that is not NaN, so without GUARD a NaN residual gives a clean v[k] = 0.  With it the step is a
+    // compare-and-select and the nz flag is applied with v_mul_legacy_f32 (0 * anything = 0: a skipped or padded row stays put
+    // next to an Inf or NaN elsewhere in its column).  The kernel runs without GUARD only where the first residual is finite.
+    static __device__ __forceinline__ float step_of(float x, float vk, float nz) {
+        float st;
+        if constexpr (GUARD) {
+            const float sel = !(x < -vk) ? x : -vk;   // np.maximum(x, -v[k]), NaN included
+            asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(st) : "s"(nz), "v"(sel));
+        } else {
+            asm("v_max_f32 %0, %1, -%2" : "=v"(st) : "v"(x), "v"(vk));
+        }
+        return st;
+    }
     __device__ __forceinline__ void update(int kb) {
         const int lb = 0;
         const LT l = lt[lb];
-        float s0, s1, s2, s3;
-        asm("v_max_f32 %0, %1, -%2" : "=v"(s0) : "v"(w[0]), "v"(v[4 * kb]));
-        if constexpr (GUARD) s0 *= l[8];
+        const float s0 = step_of(w[0], v[4 * kb], l[GUARD ? 8 : 0]);
         const float x1 = fmaf(l[0], s0, w[1]);
-        asm("v_max_f32 %0, %1, -%2" : "=v"(s1) : "v"(x1), "v"(v[4 * kb + 1]));
-        if constexpr (GUARD) s1 *= l[9];
+        const float s1 = step_of(x1, v[4 * kb + 1], l[GUARD ? 9 : 0]);
         const float x2 = fmaf(l[2], s1, fmaf(l[1], s0, w[2]));
-        asm("v_max_f32 %0, %1, -%2" : "=v"(s2) : "v"(x2), "v"(v[4 * kb + 2]));
-        if constexpr (GUARD) s2 *= l[10];
+        const float s2 = step_of(x2, v[4 * kb + 2], l[GUARD ? 10 : 0]);
         const float x3 = fmaf(l[5], s2, fmaf(l[4], s1, fmaf(l[3], s0, w[3])));
-        asm("v_max_f32 %0, %1, -%2" : "=v"(s3) : "v"(x3), "v"(v[4 * kb + 3]));
-        if constexpr (GUARD) s3 *= l[11];
+        const float s3 = step_of(x3, v[4 * kb + 3], l[GUARD ? 11 : 0]);
         stp = f32x4{s0, s1, s2, s3};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -370,8 +379,8 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
     __shared__ f32x4 tsc[4][2 * 64];   // per wave: gather [ct][n] (1 KB), scatter [lane] (1 KB)
     __shared__ f32x4 bkp[4][4][64];    // per wave: the rows of v the speculative head of a sweep moves
     __shared__ double red2[2][2][4];
-    __shared__ unsigned lds_flag;
-    if (threadIdx.x == 0) lds_flag = 1u;
+    __shared__ unsigned lds_flag, odd_flag;
+    if (threadIdx.x == 0) { lds_flag = 1u; odd_flag = 0u; }   // (odd_flag: a wave found a non-finite residual, see run())
     const int nblocks = gridDim.x;
     const int lane = threadIdx.x & 63;
     const unsigned img_addr = (unsigned)(uintptr_t)&img[lane];
@@ -403,8 +412,27 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
     // The whole solve once per variant, final store included (a branch INSIDE the loop, or a merge of the two variants' v
     // behind it, makes hipcc keep two copies of v and of the tiles).  The loop body runs at least once (checked above); the
     // from-scratch residual sits at its top behind a flag that hipcc cannot see through (it otherwise peels the first sweep).
-    auto run = [&](auto guard_tag) {
+    // Returns true when it ran nothing and the solve has to run with GUARD: without it the row update drops a NaN (update()),
+    // so that variant looks at the residual it starts from -- formed from UtM, V and the Gram, or handed over by the launch
+    // before -- and leaves before its first sweep if any entry is not finite (all 256 threads together: the sweeps' barriers).
+    // Finite operands stay finite (fp32 overflow aside), and a non-finite one shows in the residual: G'[k][k] = 1 carries
+    // v[k], 0 * Inf and 0 * NaN are NaN.
+    auto run = [&](auto guard_tag) -> bool {
         constexpr bool GUARD = decltype(guard_tag)::value;
+        auto state_odd = [&](const f32x4 (&acc_)[RT][4], const float (&accx_)[4]) -> bool {
+            float c = 0.f;   // one register: 0 * x summed up is 0 unless some x is Inf or NaN (once per launch: the chain does not matter)
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) c = fmaf(acc_[rt][ct][i], 0.f, c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c = fmaf(accx_[j], 0.f, c);
+            if (__ballot(!(c == 0.f)) != 0ull && lane == 0) odd_flag = 1u;
+            __syncthreads();
+            return odd_flag != 0u;
+        };
         float v[RP];   // (each variant loads its own start values: shared ones stay live across the other variant's loop)
         f32x4 acc[RT][4];
         float accx[4] = {0.f, 0.f, 0.f, 0.f};
@@ -427,6 +455,9 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) accx[j] = ax[j];
             fresh = 0;
+            if constexpr (!GUARD) {
+                if (state_odd(acc, accx)) return true;
+            }
         }
         mfma_sweeper<RT, REM, NKB, GUARD> sw{acc, accx, v, img_addr, (uint64_t)a.Mlt, t_ta, t_tg, t_ts};
         constexpr int NBK = 4 * (sw.SPB + 1);   // rows of v that head() moves
@@ -438,11 +469,16 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
         // the head's rows of v are backed up in LDS and put back if sweep s-1 was the last one.
         int s = 1;
         bool pending = false;   // sweep s-1 is published, its global sum not looked at yet
-        bool undo = false;
+        bool undo = false, bail = false;
 #pragma unroll 1
         for (;;) {
             asm volatile("" : "+v"(fresh));   // (opaque: hipcc otherwise specialises the first sweep)
-            if (__builtin_amdgcn_readfirstlane(fresh)) mfma_residual<RT, REM, NKB>(acc, accx, v, img_addr, rb, voff0, ldm4, a.Mlt, a.sp);
+            if (__builtin_amdgcn_readfirstlane(fresh)) {
+                mfma_residual<RT, REM, NKB>(acc, accx, v, img_addr, rb, voff0, ldm4, a.Mlt, a.sp);
+                if constexpr (!GUARD) {
+                    if (s == 1 && state_odd(acc, accx)) { bail = true; break; }
+                }
+            }
 #pragma unroll
             for (int b = 0; b < NBK / 4; ++b) bk[b * 64] = f32x4{v[4 * b], v[4 * b + 1], v[4 * b + 2], v[4 * b + 3]};
             sw.head();
@@ -485,6 +521,7 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
             fresh = ((a.sweep0 + s) % MFMA_NREF_V) == 0 || (MFMA_EARLY && a.sweep0 + s == 1);
             ++s;
         }
+        if (bail) return true;
         if (a.mode == 0 && ok && done == s && pending) {   // ran to the sweep budget: the last sweep's sum is still due
             double tot;
             ok = hals_collect1(a.sy, s, nblocks, tot, red2[s & 1][1], &lds_flag, pf);
@@ -509,9 +546,9 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
             }
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), rv, voff0, k * ldv4, 0);
         }
+        return false;
     };
-    if (all_live) run(std::false_type{});
-    else run(std::true_type{});
+    if (!all_live || run(std::false_type{})) (void)run(std::true_type{});
     if (a.mode == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
         a.status[NNF_HALS_ST_EPS] = eps;
         a.status[NNF_HALS_ST_CNT] = (double)(a.sweep0 + done + 1);

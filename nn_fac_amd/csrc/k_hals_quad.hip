@@ -14,6 +14,10 @@
 //         t  = G'[k,:].v - b'[k]               (quad-reduced; identical in the four lanes, fp add is commutative)
 //         d  = max(-t, -v[k]) = -min(t, v[k])  (v[k] broadcast from its owner lane with a DPP quad_perm)
 //         v[k] += d, nodelta += d*d            (owner lane only: the other three multiply by 0)
+//     Non-finite values go the way np.maximum sends them (nnfac_hip.h "Non-finite operands"): the minimum is a compare-and-
+//     select that keeps a NaN (v_min_f32 returns the operand that is not NaN: a clean v[k] = 0), and the two products with the
+//     owner flag are the legacy forms (0 * anything = 0), so that an Inf or NaN in one row's b' or step does not become a NaN
+//     in the three rows the other lanes hold at the same slot;
 //   * rows with a zero Gram diagonal, and the padding rows k >= r, are skipped by a wave-uniform branch on a bit mask
 //     (nnls.py:160), so no per-row guard arithmetic.
 // Stopping rule, lag-one speculation, tagged exchange, fixed-sweep mode and snapshots are those of k_hals_fast.hip.
@@ -69,7 +73,7 @@ __global__ void nnf_hals_prep_quad_kernel(const float* __restrict__ UtU, const f
 // Row update shared by both sweep variants: g = this lane's chunk of G'[k,:] (NP float4), q0/j = owner lane / slot of row k.
 template <int CH, int K>
 __device__ __forceinline__ void quad_row(const f32x4q (&g)[((CH + 3) & ~3) / 4], float (&v)[CH], const float (&b)[CH],
-                                         const float (&own)[4], float& nd) {
+                                         const float (&own)[4], float& nd, int r) {
     constexpr int q0 = K / CH, j = K % CH;
     f32x2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
 #pragma unroll
@@ -80,13 +84,17 @@ __device__ __forceinline__ void quad_row(const f32x4q (&g)[((CH + 3) & ~3) / 4],
         else a0 = __builtin_elementwise_fma(gp, vp, a0);
     }
     const f32x2 a = a0 + a1;
-    float t = fmaf(-b[j], own[q0], a[0] + a[1]);   // the owner lane brings in -b'[k]
+    float bo;                                        // the owner lane brings in -b'[k] (the product is exact: own is 0 or 1)
+    asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(bo) : "v"(b[j]), "v"(own[q0]));
+    float t = (a[0] + a[1]) - bo;
     t += dpp_quad<0xB1>(t);                          // quad_perm [1,0,3,2]
     t += dpp_quad<0x4E>(t);                          // quad_perm [2,3,0,1]: G'[k,:].v - b'[k] in all four lanes
     const float vk = dpp_quad<0x55 * q0>(v[j]);      // v[k] from its owner lane: quad_perm [q0,q0,q0,q0]
-    float mn;   // d = max(-t, -v[k]) = -min(t, v[k]); one instruction (fminf adds a canonicalising max)
-    asm("v_min_f32 %0, %1, %2" : "=v"(mn) : "v"(t), "v"(vk));
-    const float dm = -mn * own[q0];
+    const float mn = !(vk < t) ? t : vk;            // d = max(-t, -v[k]) = -min(t, v[k]), NaN included (a NaN v[k] makes t NaN)
+    float dm;
+    asm("v_mul_legacy_f32 %0, -%1, %2" : "=v"(dm) : "v"(mn), "v"(own[q0]));
+    // a padding row (K >= r: at most the last three) holds 0 and stays 0 -- 0 * Inf from its all-zero Gram row is a NaN otherwise
+    if constexpr (K >= 4 * CH - 3) dm = (K < r) ? dm : 0.f;
     v[j] += dm;
     nd = fmaf(dm, dm, nd);
     asm volatile("" : "+v"(nd));
@@ -106,7 +114,7 @@ struct quad_rows {
     static constexpr int RQ = 4 * CH, CHP = (CH + 3) & ~3, NP = CHP / 4, RS4 = 4 * CHP * 4;
     template <class MID>
     static __device__ __forceinline__ void run(f32x4q (&g)[3][NP], float (&v)[CH], const float (&b)[CH], const float (&own)[4],
-                                               unsigned laddr, float& nd, const MID& mid) {
+                                               unsigned laddr, float& nd, const MID& mid, int r) {
         constexpr int cur = K % 3, nx2 = (K + 2) % 3;
         if constexpr (K == QUAD_MID_AT(RQ)) mid();   // exchange prefetch of the previous sweep's sums (k_hals_common.h)
         if constexpr (K + 1 < RQ) asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(NP) : "memory");   // row K+1 may be in flight
@@ -118,13 +126,13 @@ struct quad_rows {
             for (int i = 0; i < NP; ++i)
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(g[nx2][i]) : "v"(laddr), "i"((K + 2) * RS4 + i * 16));
         }
-        quad_row<CH, K>(g[cur], v, b, own, nd);
-        if constexpr (K + 1 < RQ) quad_rows<CH, K + 1>::run(g, v, b, own, laddr, nd, mid);
+        quad_row<CH, K>(g[cur], v, b, own, nd, r);
+        if constexpr (K + 1 < RQ) quad_rows<CH, K + 1>::run(g, v, b, own, laddr, nd, mid, r);
     }
 };
 template <int CH, class MID>
 __device__ __forceinline__ float quad_sweep_all_live(float (&v)[CH], const float (&b)[CH], const float (&own)[4], unsigned laddr,
-                                                     const MID& mid) {
+                                                     const MID& mid, int r) {
     constexpr int RQ = 4 * CH, CHP = (CH + 3) & ~3, NP = CHP / 4, RS4 = 4 * CHP * 4;
     f32x4q g[3][NP];
     float nd = 0.f;
@@ -134,7 +142,7 @@ __device__ __forceinline__ float quad_sweep_all_live(float (&v)[CH], const float
 #pragma unroll
         for (int i = 0; i < NP; ++i) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(g[1][i]) : "v"(laddr), "i"(RS4 + i * 16));
     }
-    quad_rows<CH, 0>::run(g, v, b, own, laddr, nd, mid);
+    quad_rows<CH, 0>::run(g, v, b, own, laddr, nd, mid, r);
     return nd;
 }
 
@@ -144,15 +152,15 @@ template <int CH, int K>
 struct quad_rows_checked {
     static constexpr int RQ = 4 * CH, CHP = (CH + 3) & ~3, NP = CHP / 4, RS = 4 * CHP;
     static __device__ __forceinline__ void run(const float* lrow0, float (&v)[CH], const float (&b)[CH], const float (&own)[4],
-                                               uint64_t nz_lo, uint64_t nz_hi, float& nd) {
+                                               uint64_t nz_lo, uint64_t nz_hi, float& nd, int r) {
         const bool live = (K < 64) ? ((nz_lo >> (K & 63)) & 1ull) != 0 : ((nz_hi >> (K & 63)) & 1ull) != 0;
         if (live) {
             f32x4q g[NP];
 #pragma unroll
             for (int i = 0; i < NP; ++i) g[i] = *reinterpret_cast<const f32x4q*>(lrow0 + K * RS + 4 * i);
-            quad_row<CH, K>(g, v, b, own, nd);
+            quad_row<CH, K>(g, v, b, own, nd, r);
         }
-        if constexpr (K + 1 < RQ) quad_rows_checked<CH, K + 1>::run(lrow0, v, b, own, nz_lo, nz_hi, nd);
+        if constexpr (K + 1 < RQ) quad_rows_checked<CH, K + 1>::run(lrow0, v, b, own, nz_lo, nz_hi, nd, r);
     }
 };
 
@@ -226,15 +234,15 @@ __global__ __launch_bounds__(64) void nnf_hals_quad_kernel(hals_args a) {
             const int b0 = lane < nblocks ? lane : 0, b1 = lane + 64 < nblocks ? lane + 64 : 0;
             pf.s = want ? s - 1 : 0;
             f = quad_sweep_all_live<CH>(v, b, own, laddr, hals_mid_issue{(unsigned long long)(row + 2 * (size_t)b0),
-                                                                         (unsigned long long)(row + 2 * (size_t)b1), pf});
+                                                                         (unsigned long long)(row + 2 * (size_t)b1), pf}, a.r);
             hals_mid_wait(pf);
         } else if (all_live) {
             if (a.mode == 0 && s >= 2) hals_collect_issue(a.sy, s - 1, nblocks, pf);   // consumed after this sweep
-            f = quad_sweep_all_live<CH>(v, b, own, laddr, hals_mid_none{});
+            f = quad_sweep_all_live<CH>(v, b, own, laddr, hals_mid_none{}, a.r);
         } else {
             if (a.mode == 0 && s >= 2) hals_collect_issue(a.sy, s - 1, nblocks, pf);
             f = 0.f;
-            quad_rows_checked<CH, 0>::run(lg + q * CHP, v, b, own, nz_lo, nz_hi, f);
+            quad_rows_checked<CH, 0>::run(lg + q * CHP, v, b, own, nz_lo, nz_hi, f, a.r);
         }
         const double bs = nnf_wave_sum_f64(valid ? (double)f : 0.0);   // the workgroup IS one wave: no LDS, no barrier
         if (a.mode == 1) {

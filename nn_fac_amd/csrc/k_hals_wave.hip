@@ -141,17 +141,24 @@ __device__ __forceinline__ bool wave_ld_tagged(const unsigned long long* p2, uns
 }
 
 // row update K (compile-time: every operand position is an immediate) of the CPW columns a wave holds -- the columns'
-// chains are independent, so a wave with two columns fills the latency of one chain with the other
-template <int RL, int CPW, int K>
-__device__ __forceinline__ void wave_row(const float* img, float (&acc)[CPW][RL], const float (&nvd)[CPW][RL], float (&dk)[CPW][RL]) {
+// chains are independent, so a wave with two columns fills the latency of one chain with the other.
+// EXACT: the form for a wave that holds a non-finite value (nnfac_hip.h "Non-finite operands").  v_max_f32 returns the operand
+// that is not NaN: a NaN residual would give the step -v[k], a clean v[k] = 0 and a finite sum.  With EXACT the step is a
+// compare-and-select that keeps the NaN, as np.maximum does (one more instruction on the chain of every row), and the step of
+// a row that is skipped (zero diagonal, padding: dead) is 0 whatever its residual holds -- 0 * Inf pushed into it by
+// another row's step is a NaN there, not in the reference.
+template <int RL, int CPW, int K, bool EXACT>
+__device__ __forceinline__ void wave_row(const float* img, float (&acc)[CPW][RL], const float (&nvd)[CPW][RL], float (&dk)[CPW][RL],
+                                         const bool (&dead)[CPW][RL]) {
     constexpr int H = K >> 6, KL = K & 63, W = 64 * RL;
     float g[RL];
 #pragma unroll
     for (int h = 0; h < RL; ++h) g[h] = img[K * W + h];
 #pragma unroll
     for (int c = 0; c < CPW; ++c) {
-        float d;   // max(acc, -v) in one instruction (fmaxf adds a canonicalising max); lane KL's value is the step of row K
-        asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(acc[c][H]), "v"(nvd[c][H]));
+        float d;   // lane KL's value is the step of row K
+        if constexpr (EXACT) d = dead[c][H] ? 0.f : (!(acc[c][H] < nvd[c][H]) ? acc[c][H] : nvd[c][H]);
+        else asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(acc[c][H]), "v"(nvd[c][H]));   // max(acc, -v) in one instruction (fmaxf adds a canonicalising max)
         const float sd = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d), KL));
 #pragma unroll
         for (int h = 0; h < RL; ++h) acc[c][h] = fmaf(g[h], -sd, acc[c][h]);
@@ -159,11 +166,12 @@ __device__ __forceinline__ void wave_row(const float* img, float (&acc)[CPW][RL]
         asm("v_writelane_b32 %0, %1, %2" : "+v"(dk[c][H]) : "s"(sd), "n"(KL));
     }
 }
-template <int RL, int CPW, int K, int RU>
+template <int RL, int CPW, int K, int RU, bool EXACT>
 struct wave_rows {
-    static __device__ __forceinline__ void run(const float* img, float (&acc)[CPW][RL], const float (&nvd)[CPW][RL], float (&dk)[CPW][RL]) {
-        wave_row<RL, CPW, K>(img, acc, nvd, dk);
-        if constexpr (K + 1 < RU) wave_rows<RL, CPW, K + 1, RU>::run(img, acc, nvd, dk);
+    static __device__ __forceinline__ void run(const float* img, float (&acc)[CPW][RL], const float (&nvd)[CPW][RL], float (&dk)[CPW][RL],
+                                               const bool (&dead)[CPW][RL]) {
+        wave_row<RL, CPW, K, EXACT>(img, acc, nvd, dk, dead);
+        if constexpr (K + 1 < RU) wave_rows<RL, CPW, K + 1, RU, EXACT>::run(img, acc, nvd, dk, dead);
     }
 };
 
@@ -389,6 +397,17 @@ __global__ __launch_bounds__(1024) void nnf_hals_wave_kernel(hals_args a, int64_
         }
     };
     if (valid0) refresh();
+    // Which row update this wave runs, decided once: everything that enters a sweep is in the start values, the scaled
+    // right-hand side and the first residual (a non-finite Gram entry makes the residual of its row non-finite whatever v
+    // holds: 0 * Inf and 0 * NaN are NaN).  All finite: they stay finite (fp32 overflow aside) and the one-instruction form
+    // is exact; else the wave runs the form that keeps NaN and Inf as the reference does.
+    bool odd = false;
+#pragma unroll
+    for (int c = 0; c < CPW; ++c)
+#pragma unroll
+        for (int h = 0; h < RL; ++h)
+            odd = odd || (valid0 && !(acc[c][h] * 0.f == 0.f)) || !(v[c][h] * 0.f == 0.f) || !(bs[c][h] * 0.f == 0.f);
+    const bool exact = __ballot(odd) != 0ull;             // wave-uniform
     const int S = a.max_sweeps;
     int judged = 0;                                       // verdicts read so far: sweeps 1 .. judged go on
     unsigned stop = 0u;                                   // the stopping sweep once its verdict has been read; WAVE_ERR
@@ -420,7 +439,10 @@ __global__ __launch_bounds__(1024) void nnf_hals_wave_kernel(hals_args a, int64_
 #pragma unroll
             for (int h = 0; h < RL; ++h) dk[c][h] = 0.f;
         if (valid0 && s > 1 && ((s - 1) & (WAVE_REFRESH - 1)) == 0) refresh();
-        if (valid0 && !(WAVE_DBG & 4)) wave_rows<RL, CPW, 0, RU>::run(img, acc, nvd, dk);
+        if (valid0 && !(WAVE_DBG & 4)) {
+            if (exact) wave_rows<RL, CPW, 0, RU, true>::run(img, acc, nvd, dk, dead);
+            else wave_rows<RL, CPW, 0, RU, false>::run(img, acc, nvd, dk, dead);
+        }
         float f = 0.f;
         const int sl = s & (WAVE_SNAP - 1);
 #pragma unroll

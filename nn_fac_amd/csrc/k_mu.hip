@@ -59,7 +59,8 @@ static __global__ __launch_bounds__(256) void nnf_mu_finish_kernel(const float* 
         else de = slab_sum(sden);
         float ratio = (float)(nu / de);
         if (gamma != 1.f) ratio = powf(ratio, gamma);
-        out[k * ldo + j] = fmaxf(F[k * ldf + j] * ratio, 1e-12f);
+        const float x = F[k * ldf + j] * ratio;
+        out[k * ldo + j] = x < 1e-12f ? 1e-12f : x;   // np.maximum(x, 1e-12), NaN included (mu.py:84-97): fmaxf would drop it
     }
 }
 
@@ -122,7 +123,8 @@ static __global__ __launch_bounds__(256) void nnf_mu2_finish_kernel(const float*
                 for (int u = 0; u < 8; ++u)
                     if (l + u < r) d = fmaf(Gs[k * r + l + u], fv[u], d);
             }
-            out[(int64_t)k * ldo + j] = fmaxf(F[(int64_t)k * ldf + j] * (num[(int64_t)k * ldn + j] / d), 1e-12f);
+            const float x = F[(int64_t)k * ldf + j] * (num[(int64_t)k * ldn + j] / d);
+            out[(int64_t)k * ldo + j] = x < 1e-12f ? 1e-12f : x;   // (a NaN stays a NaN, as np.maximum keeps it)
         }
     }
 }
@@ -537,18 +539,19 @@ __global__ __launch_bounds__(256) void nnf_deep_kl_apply_kernel(const float* __r
         const double q = a / lambda;
         const double Lb = log(b) + q;
         const double Lz = Lb - loglam;
-        if (!(b > 0.0)) {
-            res = 0.0;   // b = 0: numerator 0 (the reference gives 0 / (0 + eps) = 0, then the 1e-12 floor)
+        if (b <= 0.0) {
+            res = 0.0;   // b = 0: numerator 0 (the reference gives 0 / (0 + eps) = 0, then the 1e-12 floor); a NaN b goes on
         } else if (q > 709.782712893384 || Lb > 709.782712893384 || Lz > 709.782712893384) {
             // the reference forms exp(a/lambda), b*exp(.) and then /lambda in float64 (deep_mu.py:11): once any of the three
             // passes log(DBL_MAX) it is +inf (for lambda > 1 the product overflows although the quotient would not),
-            // lambertw(inf) = inf and the quotient is 0 -> the floor.  Kept: results identical to the reference's.
-            res = 0.0;
+            // lambertw(inf) = inf and the quotient is 0 -> the floor.  Kept: results identical to the reference's
+            // (b = +inf: inf / inf, a NaN there and here).
+            res = (b / lambda) / (double)__builtin_inff();
         } else {
             const double w = nnf_lambertw_logarg(Lz);
             res = (b / lambda) / (w + 1e-12);
         }
-        out[k * ldo + i] = (float)fmax(1e-12, res);
+        out[k * ldo + i] = (float)(res < 1e-12 ? 1e-12 : res);   // np.maximum(1e-12, .), NaN included (deep_mu.py:11)
     }
 }
 extern "C" int nnf_deep_kl_apply_f32(nnf_ctx* ctx, const float* F, int64_t ldf, int r, int64_t cols, const float* num,

@@ -746,7 +746,8 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
         }
         float ratio = nu / de;
         if (gamma != 1.f) ratio = powf(ratio, gamma);
-        Ut_out[(int64_t)rk * lduo + i] = fmaxf(old * ratio, 1e-12f);
+        const float x = old * ratio;
+        Ut_out[(int64_t)rk * lduo + i] = x < 1e-12f ? 1e-12f : x;   // np.maximum(x, 1e-12), NaN included (mu.py:84-97)
     };
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {

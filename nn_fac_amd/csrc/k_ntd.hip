@@ -241,7 +241,8 @@ __global__ __launch_bounds__(1024) void nnf_ntd_core_pg_kernel(float* __restrict
         for (int e = threadIdx.x; e < S; e += blockDim.x) {
             const double c = (double)core[e];
             const double grad = -(double)mtx[e] + (double)ta[e] + sparse;
-            const double dc = fmin(step * grad, c);
+            const double sg = step * grad;
+            const double dc = (sg < c || sg != sg) ? sg : c;   // np.minimum(step * grad, c), NaN of either side included (ntd.py:613)
             core[e] = (ST)(c - dc);
             s2 += dc * dc;
         }
@@ -386,7 +387,8 @@ __global__ __launch_bounds__(256) void nnf_ntd_core_pg_multi_kernel(float* __res
         double s2 = 0.0;
         for (int e = threadIdx.x; e < S1; e += blockDim.x) {
             const double grad = -mx[e] + ta[e] + sparse;
-            const double dc = fmin(step * grad, c[e]);
+            const double sg = step * grad;
+            const double dc = (sg < c[e] || sg != sg) ? sg : c[e];   // np.minimum, NaN of either side included (ntd.py:613)
             c[e] -= dc;
             s2 += dc * dc;
         }
