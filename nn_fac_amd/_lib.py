@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("NNF_LIBRARY") or os.path.join(_HERE, "libnnfac_hip.so
 _i64, _i32, _u32 = C.c_int64, C.c_int, C.c_uint
 _p, _f32, _f64 = C.c_void_p, C.c_float, C.c_double
 
-# name -> (restype, argtypes); mirrors include/nnfac_hip.h one to one
+# name -> (restype, argtypes): one entry per prototype of include/nnfac_hip.h, which is the source -- names and types are
+# compared with the header by tests/test_abi_and_host.py::test_binding_table_matches_header
 SIGNATURES = {
     "nnf_version": (_i32, []),
     "nnf_build_flags": (C.c_size_t, [C.c_char_p, C.c_size_t]),
@@ -113,3 +114,9 @@ def check(status, what=""):
     if status != 0:
         msg = load().nnf_status_string(status).decode()
         raise EngineError(f"{what}: libnnfac_hip status {status} ({msg})")
+
+
+def call(lib, name, *args):
+    """The entry point `name` of `lib` -- looked up on the object handed in, so that a proxy around the library sees the call --
+    with `args`; a non-zero status raises EngineError under that same name."""
+    check(getattr(lib, name)(*args), name)

@@ -56,6 +56,166 @@ def _chk2d(t, name):
     return t
 
 
+# ---- marshalling: the recurring shapes of argument ----------------------------------------------------------------------------
+def _mat(t):
+    """A matrix: (pointer, leading dimension)."""
+    return _ptr(t), _ld(t)
+
+
+def _opt(t):
+    """An optional tensor: pointer or NULL."""
+    return None if t is None else _ptr(t)
+
+
+def _optmat(t):
+    """An optional matrix: (pointer or NULL, leading dimension or 0)."""
+    return (None, 0) if t is None else (_ptr(t), _ld(t))
+
+
+def _optblocks(t):
+    """An optional contiguous stack of blocks: (pointer or NULL, block stride or 0)."""
+    return (None, 0) if t is None else (_ptr(t), t.stride(0))
+
+
+def _triple(X, Ut, V):
+    """The argument run of every entry that takes X (m x n), Ut (r x m), V (r x n)."""
+    return _ptr(X), X.shape[0], X.shape[1], _ld(X), _ptr(Ut), _ld(Ut), _ptr(V), _ld(V), Ut.shape[0]
+
+
+def _solve_args(UtM, UtU, V):
+    """The argument run of the sweep entries: right-hand side, Gram, factor, r, ncols."""
+    return _ptr(UtM), _ld(UtM), _ptr(UtU), _ld(UtU), _ptr(V), _ld(V), V.shape[0], V.shape[1]
+
+
+def _cp3_args(T, Ft):
+    """The argument run of the 3-way CP entries: T, its extents, the three transposed factors, R."""
+    return (_ptr(T), *T.shape, *_mat(Ft[0]), *_mat(Ft[1]), *_mat(Ft[2]), Ft[0].shape[0])
+
+
+# ---- operand checks: each rule is written once, here; every message names the method and the operand --------------------------
+def _shaped(t, shape, name):
+    """_chk2d and the extents."""
+    if _chk2d(t, name).shape != shape:
+        raise EngineError(f"{name}: shape mismatch, expected {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _xf(X, F, axis, what, fname):
+    """X (m x n) and one transposed factor whose columns run along `axis` of X (Ut: 0, V: 1) -> (m, n, r)."""
+    _chk2d(X, what + " X"), _chk2d(F, f"{what} {fname}")
+    if F.shape[1] != X.shape[axis]:
+        raise EngineError(f"{what}: shape mismatch, X is {tuple(X.shape)}, {fname} {tuple(F.shape)}")
+    return X.shape[0], X.shape[1], F.shape[0]
+
+
+def _xuv(X, Ut, V, what):
+    """X (m x n), Ut (r x m), V (r x n) -> (m, n, r)."""
+    _chk2d(X, what + " X"), _chk2d(Ut, what + " Ut"), _chk2d(V, what + " V")
+    (m, n), r = X.shape, Ut.shape[0]
+    if Ut.shape[1] != m or V.shape != (r, n):
+        raise EngineError(f"{what}: shape mismatch, X is {m} x {n}, Ut {tuple(Ut.shape)}, V {tuple(V.shape)}")
+    return m, n, r
+
+
+def _solve_ops(UtM, UtU, V, what):
+    """Right-hand side of V's shape and a Gram of at least r x r (it may be larger: a view is not needed) -> (r, ncols)."""
+    _chk2d(UtM, what + " UtM"), _chk2d(UtU, what + " UtU"), _chk2d(V, what + " V")
+    r, ncols = V.shape
+    if UtM.shape != (r, ncols) or UtU.shape[0] < r or UtU.shape[1] < r:
+        raise EngineError(f"{what}: shape mismatch, V is {r} x {ncols}, UtM {tuple(UtM.shape)}, UtU {tuple(UtU.shape)}")
+    return r, ncols
+
+
+def _gram_pair(G, Gb, name):
+    """The second Gram of a Hadamard pair (or None): the entries read one leading dimension for both."""
+    if Gb is not None and (_shaped(Gb, G.shape, name).device != G.device or _ld(Gb) != _ld(G)):
+        raise EngineError(f"{name}: the two Grams of a Hadamard pair must share device and leading dimension")
+
+
+def _t3(T, what, exc=EngineError):
+    """Contiguous 3-way float32 device tensor."""
+    if T.dim() != 3 or T.dtype != torch.float32 or not T.is_cuda or not T.is_contiguous():
+        raise exc(f"{what} must be a contiguous 3-way float32 device tensor, got {tuple(T.shape)} {T.dtype} {T.device}")
+    return T
+
+
+def _f32(t, shape, what, contiguous=False):
+    """float32 device tensor of `shape`, any layout unless `contiguous`."""
+    if t.dtype != torch.float32 or not t.is_cuda or t.shape != shape or (contiguous and not t.is_contiguous()):
+        raise EngineError(f"{what} must be a {'contiguous ' if contiguous else ''}float32 device tensor of shape {tuple(shape)}, "
+                          f"got {tuple(t.shape)} {t.dtype} {t.device}")
+    return t
+
+
+def _core_ops(core, MtX, grams, status, what):
+    """The operands of the Tucker core update: a contiguous float32 device core, an MtX of its shape, one float32 d x d Gram per
+    mode of extent d (MtX and the Grams in any layout: they are copied to contiguous buffers), 6 status doubles.  Returns
+    (contiguous MtX, contiguous Grams, status)."""
+    if not core.is_contiguous() or core.dtype != torch.float32 or not core.is_cuda:
+        raise err.ArgumentException(f"{what} updates a contiguous float32 device core in place")
+    if len(grams) != core.dim() or tuple(MtX.shape) != tuple(core.shape):
+        raise err.ArgumentException(f"{what} needs one Gram per core mode and an MtX of the core's shape")
+    for g, d in zip(grams, core.shape):
+        if tuple(g.shape) != (d, d) or g.dtype != torch.float32 or g.device != core.device:
+            raise err.ArgumentException(f"{what}: the Gram of a mode of extent d is a float32 d x d matrix on the core's device")
+    if MtX.dtype != torch.float32 or MtX.device != core.device:
+        raise err.ArgumentException(f"{what}: MtX must be float32 on the core's device")
+    return MtX.contiguous(), [g.contiguous() for g in grams], _out64(status, 6, core.device, what + " status")
+
+
+def _cp3(T, Ft, what):
+    """T (I x J x K) and its three transposed factors (R x I, R x J, R x K) -> R."""
+    _t3(T, what + ": T")
+    R = _chk2d(Ft[0], what + " factor 0").shape[0]
+    for i in range(3):
+        _shaped(Ft[i], (R, T.shape[i]), f"{what} factor {i}")
+    return R
+
+
+def _f64(t, count, dev, what, exact=False):
+    """Contiguous float64 tensor on `dev` of at least (exact: exactly) `count` elements."""
+    if not torch.is_tensor(t) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev \
+            or (t.numel() != count if exact else t.numel() < count):
+        raise EngineError(f"{what} must be a contiguous float64 tensor on {dev} of {'exactly' if exact else 'at least'} "
+                          f"{count} elements")
+    return t
+
+
+def _snap(S, blocks, r, ncols, what):
+    """Snapshot window: contiguous float32 device tensor [>= blocks, r, ncols]."""
+    if (S.dtype != torch.float32 or not S.is_cuda or not S.is_contiguous() or S.dim() != 3 or S.shape[0] < blocks
+            or tuple(S.shape[1:]) != (r, ncols)):
+        raise EngineError(f"{what} must be a contiguous float32 device tensor [>= {blocks}, {r}, {ncols}]")
+    return S
+
+
+def _off(off, what):
+    """Segment table of the grouped kernels -> ngroups."""
+    if off.dtype != torch.int64 or not off.is_cuda or off.dim() != 1 or not off.is_contiguous() or off.numel() < 2:
+        raise EngineError(f"{what}: the segment table must be a contiguous int64 device vector of ngroups + 1 entries")
+    return off.numel() - 1
+
+
+def _stack(M, what):
+    if M.dim() != 3 or M.dtype != torch.float32 or not M.is_cuda or (M.shape[2] > 1 and M.stride(2) != 1):
+        raise EngineError(f"{what}: expected a float32 device stack [groups, rows, cols] with unit inner stride")
+    return M
+
+
+def _out(out, shape, like, what):
+    """The caller's `out` (a 2-D float32 matrix of `shape` on like's device), or a fresh one."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if _shaped(out, shape, what).device != like.device:
+        raise EngineError(f"{what} must be on {like.device}, got {out.device}")
+    return out
+
+
+def _out64(out, count, dev, what):
+    """The caller's float64 result words (_f64), or fresh ones."""
+    return torch.empty(count, dtype=torch.float64, device=dev) if out is None else _f64(out, count, dev, what)
+
+
 class KernelTime(float):
     """Mean launch duration in ms (the float) + the spread of the samples it came from."""
 
@@ -79,7 +239,7 @@ class Engine:
         self.device = torch.device(device)
         self.lib = _lib.load()
         h = C.c_void_p()
-        _lib.check(self.lib.nnf_ctx_create(C.byref(h), self.device.index or 0, workspace_bytes), "nnf_ctx_create")
+        _lib.call(self.lib, "nnf_ctx_create", C.byref(h), self.device.index or 0, workspace_bytes)
         self.ctx = h
         self._resident_cols = {}
 
@@ -93,93 +253,69 @@ class Engine:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _call(self, name, *args):
+        """The one way into a compute entry: `name`(ctx, *args, current stream), found on self.lib by name (a proxy put there
+        sees every call); a non-zero status raises EngineError under that name."""
+        _lib.call(self.lib, name, self.ctx, *args, self._stream())
+
+    def _query(self, name, *args):
+        """An int64 property of the context: `name`(ctx, *args, &value)."""
+        out = C.c_int64(0)
+        _lib.call(self.lib, name, self.ctx, *args, C.byref(out))
+        return int(out.value)
+
     # ---- contractions -------------------------------------------------------------------------------
     def gram(self, A, out=None, out64=None):
         """A (r x K) -> A A^T (r x r).  out64 (optional, contiguous r x r float64 device tensor): also receives the sums before
         they are rounded to fp32 (nnf_gram_f64_f32), for gram_cost(..., UtU64=...)."""
-        _chk2d(A, "gram A")
-        r, K = A.shape
-        G = out if out is not None else torch.empty((r, r), dtype=torch.float32, device=A.device)
+        r, K = _chk2d(A, "gram A").shape
         if out64 is not None:
-            if out64.dtype != torch.float64 or not out64.is_contiguous() or out64.numel() < r * r or out64.device != A.device:
-                raise EngineError("gram: out64 must be a contiguous float64 device tensor of r*r elements")
-            _lib.check(self.lib.nnf_gram_f64_f32(self.ctx, _ptr(A), r, K, _ld(A), _ptr(G), _ld(G), _ptr(out64), self._stream()),
-                       "nnf_gram_f64_f32")
-            return G
-        _lib.check(self.lib.nnf_gram_f32(self.ctx, _ptr(A), r, K, _ld(A), _ptr(G), _ld(G), self._stream()),
-                   "nnf_gram_f32")
+            _f64(out64, r * r, A.device, "gram out64")
+        G = _out(out, (r, r), A, "gram out")
+        if out64 is None:
+            self._call("nnf_gram_f32", _ptr(A), r, K, _ld(A), *_mat(G))
+        else:
+            self._call("nnf_gram_f64_f32", _ptr(A), r, K, _ld(A), *_mat(G), _ptr(out64))
         return G
 
     def xht(self, X, V, out=None):
         """V (r x n), X (m x n) -> V X^T (r x m)."""
-        _chk2d(X, "xht X"), _chk2d(V, "xht V")
-        m, n = X.shape
-        r = V.shape[0]
-        if V.shape[1] != n:
-            raise EngineError("xht: shape mismatch")
-        O = out if out is not None else torch.empty((r, m), dtype=torch.float32, device=X.device)
-        _lib.check(self.lib.nnf_xht_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(V), r, _ld(V), _ptr(O),
-                                        _ld(O), self._stream()), "nnf_xht_f32")
+        m, n, r = _xf(X, V, 1, "xht", "V")
+        O = _out(out, (r, m), X, "xht out")
+        self._call("nnf_xht_f32", _ptr(X), m, n, _ld(X), _ptr(V), r, _ld(V), *_mat(O))
         return O
 
     def xty(self, X, Ut, out=None):
         """Ut (r x m), X (m x n) -> Ut X (r x n)."""
-        _chk2d(X, "xty X"), _chk2d(Ut, "xty Ut")
-        m, n = X.shape
-        r = Ut.shape[0]
-        if Ut.shape[1] != m:
-            raise EngineError("xty: shape mismatch")
-        O = out if out is not None else torch.empty((r, n), dtype=torch.float32, device=X.device)
-        _lib.check(self.lib.nnf_xty_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), r, _ld(Ut), _ptr(O),
-                                        _ld(O), self._stream()), "nnf_xty_f32")
+        m, n, r = _xf(X, Ut, 0, "xty", "Ut")
+        O = _out(out, (r, n), X, "xty out")
+        self._call("nnf_xty_f32", _ptr(X), m, n, _ld(X), _ptr(Ut), r, _ld(Ut), *_mat(O))
         return O
-
-    def _chk_g64(self, G64, r, dev, what):
-        if G64 is not None and (G64.dtype != torch.float64 or not G64.is_contiguous() or G64.numel() < r * r or G64.device != dev):
-            raise EngineError(f"{what}: out64 must be a contiguous float64 device tensor of r*r elements")
 
     def xty_gram(self, X, Ut, out=None, G=None, G64=None):
         """xty(X, Ut, out) and gram(Ut, G, G64) in one main launch and one slab reduction (nnf_xty_gram_f32): the same bits as
         the two calls.  Returns (Ut X, Ut Ut^T)."""
-        _chk2d(X, "xty_gram X"), _chk2d(Ut, "xty_gram Ut")
-        m, n = X.shape
-        r = Ut.shape[0]
-        if Ut.shape[1] != m:
-            raise EngineError("xty_gram: shape mismatch")
-        O = out if out is not None else torch.empty((r, n), dtype=torch.float32, device=X.device)
-        G = G if G is not None else torch.empty((r, r), dtype=torch.float32, device=X.device)
-        _chk2d(O, "xty_gram out"), _chk2d(G, "xty_gram G")
-        self._chk_g64(G64, r, X.device, "xty_gram")
-        _lib.check(self.lib.nnf_xty_gram_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), r, _ld(Ut), _ptr(O), _ld(O), _ptr(G), _ld(G),
-                                             _ptr(G64) if G64 is not None else None, self._stream()), "nnf_xty_gram_f32")
+        m, n, r = _xf(X, Ut, 0, "xty_gram", "Ut")
+        if G64 is not None:
+            _f64(G64, r * r, X.device, "xty_gram G64")
+        O, G = _out(out, (r, n), X, "xty_gram out"), _out(G, (r, r), X, "xty_gram G")
+        self._call("nnf_xty_gram_f32", _ptr(X), m, n, _ld(X), _ptr(Ut), r, _ld(Ut), *_mat(O), *_mat(G), _opt(G64))
         return O, G
 
     def xht_gram(self, X, V, out=None, G=None):
         """xht(X, V, out) and gram(V, G) in one main launch and one slab reduction (nnf_xht_gram_f32): the same bits as the two
         calls.  Returns (V X^T, V V^T)."""
-        _chk2d(X, "xht_gram X"), _chk2d(V, "xht_gram V")
-        m, n = X.shape
-        r = V.shape[0]
-        if V.shape[1] != n:
-            raise EngineError("xht_gram: shape mismatch")
-        O = out if out is not None else torch.empty((r, m), dtype=torch.float32, device=X.device)
-        G = G if G is not None else torch.empty((r, r), dtype=torch.float32, device=X.device)
-        _chk2d(O, "xht_gram out"), _chk2d(G, "xht_gram G")
-        _lib.check(self.lib.nnf_xht_gram_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(V), r, _ld(V), _ptr(O), _ld(O), _ptr(G), _ld(G),
-                                             self._stream()), "nnf_xht_gram_f32")
+        m, n, r = _xf(X, V, 1, "xht_gram", "V")
+        O, G = _out(out, (r, m), X, "xht_gram out"), _out(G, (r, r), X, "xht_gram G")
+        self._call("nnf_xht_gram_f32", _ptr(X), m, n, _ld(X), _ptr(V), r, _ld(V), *_mat(O), *_mat(G))
         return O, G
 
     def frob_resid(self, X, Ut, V, out=None):
         """sum (X - Ut^T V)^2 as a 1-element float64 device tensor."""
-        _chk2d(X, "frob X"), _chk2d(Ut, "frob Ut"), _chk2d(V, "frob V")
-        m, n = X.shape
-        r = Ut.shape[0]
-        if Ut.shape[1] != m or V.shape != (r, n):
-            raise EngineError("frob_resid: shape mismatch")
-        o = out if out is not None else torch.empty(1, dtype=torch.float64, device=X.device)
+        m, n, r = _xuv(X, Ut, V, "frob_resid")
+        o = _out64(out, 1, X.device, "frob_resid out")
         self._model_scratch(m, n, r)
-        _lib.check(self.lib.nnf_frob_resid_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V),
-                                               _ld(V), r, _ptr(o), self._stream()), "nnf_frob_resid_f32")
+        self._call("nnf_frob_resid_f32", *_triple(X, Ut, V), _ptr(o))
         return o
 
     def _model_scratch(self, m, n, r):
@@ -192,37 +328,28 @@ class Engine:
         if cur is None or cur.numel() < need:
             torch.cuda.current_stream(self.device).synchronize()      # (earlier calls may still read the old buffer)
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.nnf_ctx_set_scratch(self.ctx, _ptr(self._scratch), need), "nnf_ctx_set_scratch")
+            _lib.call(self.lib, "nnf_ctx_set_scratch", self.ctx, _ptr(self._scratch), need)
 
     def gram_cost(self, V, UtM, UtU, normx2, out, UtU_b=None, rounding=None, UtU64=None):
         """||X - U V||^2 through the Gram identity (nnf_nmf_gram_cost_cal_f32): `normx2` a 1-element float64 device tensor holding
         ||X||^2, `out` >= 3 float64 on the device: {cost, 1 if the fp32 operands do not carry it to 5e-4, error estimate}.
         rounding = (relative rms, |relative mean|) of the rounding error of a UtM entry (default: 6e-8, 0)."""
-        _chk2d(V, "gram_cost V"), _chk2d(UtM, "gram_cost UtM"), _chk2d(UtU, "gram_cost UtU")
-        r, n = V.shape
-        if UtM.shape != (r, n) or UtU.shape[0] < r or UtU.shape[1] < r or normx2.dtype != torch.float64 or out.dtype != torch.float64 \
-                or out.numel() < 3:
-            raise EngineError("gram_cost: shape / dtype mismatch")
-        if UtU_b is not None and (UtU_b.shape != UtU.shape or _ld(UtU_b) != _ld(UtU)):
-            raise EngineError("gram_cost: the two Grams of a Hadamard pair must share shape and leading dimension")
-        if UtU64 is not None:
-            # (the kernel reads r x r doubles with row stride r, whatever UtU's leading dimension is)
-            if UtU_b is not None:
-                raise EngineError("gram_cost: UtU64 cannot be combined with a Hadamard pair (UtU_b)")
-            if not torch.is_tensor(UtU64) or UtU64.dtype != torch.float64 or not UtU64.is_contiguous() or UtU64.numel() != r * r \
-                    or UtU64.device != V.device:
-                raise EngineError("gram_cost: UtU64 must be a contiguous float64 device tensor of exactly r*r elements")
+        r, n = _solve_ops(UtM, UtU, V, "gram_cost")
+        _f64(normx2, 1, V.device, "gram_cost normx2"), _f64(out, 3, V.device, "gram_cost out")
+        _gram_pair(UtU, UtU_b, "gram_cost UtU_b")
         sa, ba = (6e-8, 0.0) if rounding is None else (float(rounding[0]), float(rounding[1]))
-        if UtU64 is not None:
-            # the quadratic form on the Gram before its rounding to fp32; rounding[2] = relative rms error of a UtU64 entry
-            sg = float(rounding[2]) if rounding is not None and len(rounding) > 2 else 1e-8
-            _lib.check(self.lib.nnf_nmf_gram_cost_g64_f32(self.ctx, _ptr(V), _ld(V), _ptr(UtM), _ld(UtM), _ptr(UtU), _ptr(UtU64),
-                                                          _ld(UtU), r, n, _ptr(normx2), sa, ba, sg, _ptr(out), self._stream()),
-                       "nnf_nmf_gram_cost_g64_f32")
+        if UtU64 is None:
+            self._call("nnf_nmf_gram_cost_cal_f32", *_mat(V), *_mat(UtM), _ptr(UtU), _opt(UtU_b), _ld(UtU), r, n, _ptr(normx2),
+                       sa, ba, _ptr(out))
             return out
-        _lib.check(self.lib.nnf_nmf_gram_cost_cal_f32(self.ctx, _ptr(V), _ld(V), _ptr(UtM), _ld(UtM), _ptr(UtU),
-                                                      _ptr(UtU_b) if UtU_b is not None else None, _ld(UtU), r, n,
-                                                      _ptr(normx2), sa, ba, _ptr(out), self._stream()), "nnf_nmf_gram_cost_cal_f32")
+        # (the kernel reads r x r doubles with row stride r, whatever UtU's leading dimension is)
+        if UtU_b is not None:
+            raise EngineError("gram_cost: UtU64 cannot be combined with a Hadamard pair (UtU_b)")
+        _f64(UtU64, r * r, V.device, "gram_cost UtU64", exact=True)
+        # the quadratic form on the Gram before its rounding to fp32; rounding[2] = relative rms error of a UtU64 entry
+        sg = float(rounding[2]) if rounding is not None and len(rounding) > 2 else 1e-8
+        self._call("nnf_nmf_gram_cost_g64_f32", *_mat(V), *_mat(UtM), _ptr(UtU), _ptr(UtU64), _ld(UtU), r, n, _ptr(normx2),
+                   sa, ba, sg, _ptr(out))
         return out
 
     def cross_rounding(self, X, Ut, blocks=16):
@@ -260,17 +387,20 @@ class Engine:
         return float(rel.pow(2).mean().sqrt())
 
     def dot(self, A, B):
-        _chk2d(A, "dot A"), _chk2d(B, "dot B")
+        _shaped(B, _chk2d(A, "dot A").shape, "dot B")
         o = torch.empty(1, dtype=torch.float64, device=A.device)
-        _lib.check(self.lib.nnf_dot_f32(self.ctx, _ptr(A), _ld(A), _ptr(B), _ld(B), A.shape[0], A.shape[1],
-                                        _ptr(o), self._stream()), "nnf_dot_f32")
+        self._call("nnf_dot_f32", *_mat(A), *_mat(B), A.shape[0], A.shape[1], _ptr(o))
         return o
 
     def hadamard(self, A, B, out=None):
+        """out = A .* B, element by element.  A and B may be views (they are copied to contiguous buffers first: a non-contiguous
+        A or B is therefore not refused); a caller's `out` is written as it lies and must be contiguous."""
+        _f32(A, A.shape, "hadamard A"), _f32(B, A.shape, "hadamard B")
+        if out is not None:
+            _f32(out, A.shape, "hadamard out", contiguous=True)
         A, B = A.contiguous(), B.contiguous()
-        Cc = out if out is not None else torch.empty_like(A)
-        _lib.check(self.lib.nnf_hadamard_f32(self.ctx, _ptr(A), _ptr(B), _ptr(Cc), A.numel(), self._stream()),
-                   "nnf_hadamard_f32")
+        Cc = torch.empty_like(A) if out is None else out
+        self._call("nnf_hadamard_f32", _ptr(A), _ptr(B), _ptr(Cc), A.numel())
         return Cc
 
     # ---- HALS ---------------------------------------------------------------------------------------
@@ -314,49 +444,39 @@ class Engine:
     def hals_solve(self, UtM, UtU, V, max_sweeps, delta=0.01, sparsity=None, normalize=False, nonzero=False,
                    status=None):
         """In-place accelerated HALS on V (r x ncols); returns the 8-double status tensor (device, not synced)."""
-        _chk2d(UtM, "hals UtM"), _chk2d(UtU, "hals UtU"), _chk2d(V, "hals V")
-        r, ncols = V.shape
-        if UtM.shape != (r, ncols) or UtU.shape[0] < r or UtU.shape[1] < r:
-            raise EngineError("hals_solve: shape mismatch")
-        st = status if status is not None else torch.empty(ST_WORDS, dtype=torch.float64, device=V.device)
-        flags = self._hals_flags(sparsity, normalize, nonzero)
+        r, ncols = _solve_ops(UtM, UtU, V, "hals_solve")
+        st = _out64(status, ST_WORDS, V.device, "hals_solve status")
         if (normalize or nonzero or r > MAX_RANK) and ncols > self.ROWSYNC_MAX_COLUMNS and int(max_sweeps) > 0:
             # (ranks above 128 run in the generic kernel too: one column per resident thread for a persistent solve)
             return self._hals_solve_rowwalk(UtM, UtU, V, max_sweeps, delta, sparsity, st, normalize=normalize, nonzero=nonzero)
         self._check_rowsync_columns(normalize or nonzero, ncols)
+        ops = _solve_args(UtM, UtU, V)
+        rule = (float(delta), float(sparsity or 0.0), self._hals_flags(sparsity, normalize, nonzero), _ptr(st))
         total, first = int(max_sweeps), min(int(max_sweeps), self.HALS_MAX_SWEEPS_PER_LAUNCH)
-        _lib.check(self.lib.nnf_hals_solve_f32(self.ctx, _ptr(UtM), _ld(UtM), _ptr(UtU), _ld(UtU), _ptr(V),
-                                               _ld(V), r, ncols, first, float(delta), float(sparsity or 0.0), flags,
-                                               _ptr(st), self._stream()), "nnf_hals_solve_f32")
+        self._call("nnf_hals_solve_f32", *ops, first, *rule)
         done = first
         while done < total:      # maxiter beyond one launch's tag range: chained launches, no host round trip in between
             step = min(total - done, self.HALS_MAX_SWEEPS_PER_LAUNCH)
-            _lib.check(self.lib.nnf_hals_solve_continue_f32(self.ctx, _ptr(UtM), _ld(UtM), _ptr(UtU), _ld(UtU), _ptr(V),
-                                                            _ld(V), r, ncols, done, step, float(delta),
-                                                            float(sparsity or 0.0), flags, _ptr(st), self._stream()),
-                       "nnf_hals_solve_continue_f32")
+            self._call("nnf_hals_solve_continue_f32", *ops, done, step, *rule)
             done += step
         return st
 
     def hals_solve_cross(self, UtM, Ga, Gb, V_in, V_out, max_sweeps, delta=0.01, sparsity=None, normalize=False, status=None):
         """hals_solve with the Gram Ga .* Gb (Gb may be None), start values V_in and the result in V_out (ntf.py:442-456)."""
-        _chk2d(UtM, "hals UtM"), _chk2d(Ga, "hals Ga"), _chk2d(V_in, "hals V_in"), _chk2d(V_out, "hals V_out")
-        r, ncols = V_out.shape
-        if UtM.shape != (r, ncols) or V_in.shape != (r, ncols) or Ga.shape[0] < r or (Gb is not None and
-                                                                                       (Gb.shape != Ga.shape or _ld(Gb) != _ld(Ga))):
-            raise EngineError("hals_solve_cross: shape mismatch")
-        st = status if status is not None else torch.empty(ST_WORDS, dtype=torch.float64, device=V_out.device)
+        r, ncols = _chk2d(V_out, "hals_solve_cross V_out").shape
+        _shaped(UtM, (r, ncols), "hals_solve_cross UtM"), _shaped(V_in, (r, ncols), "hals_solve_cross V_in")
+        if _chk2d(Ga, "hals_solve_cross Ga").shape[0] < r or Ga.shape[1] < r:
+            raise EngineError(f"hals_solve_cross Ga: a Gram of at least {r} x {r} expected, got {tuple(Ga.shape)}")
+        _gram_pair(Ga, Gb, "hals_solve_cross Gb")
+        st = _out64(status, ST_WORDS, V_out.device, "hals_solve_cross status")
         if normalize and ncols > self.ROWSYNC_MAX_COLUMNS and int(max_sweeps) > 0:
             if V_out.data_ptr() != V_in.data_ptr():
                 V_out.copy_(V_in)
             return self._hals_solve_rowwalk(UtM, Ga if Gb is None else self.hadamard(Ga[:r, :r], Gb[:r, :r]), V_out, max_sweeps,
                                             delta, sparsity, st)
         self._check_rowsync_columns(normalize, ncols)
-        _lib.check(self.lib.nnf_hals_solve_cross_f32(self.ctx, _ptr(UtM), _ld(UtM), _ptr(Ga), _ptr(Gb) if Gb is not None else None,
-                                                     _ld(Ga), _ptr(V_in), _ld(V_in), _ptr(V_out), _ld(V_out), r, ncols,
-                                                     int(max_sweeps), float(delta), float(sparsity or 0.0),
-                                                     self._hals_flags(sparsity, normalize, False), _ptr(st), self._stream()),
-                   "nnf_hals_solve_cross_f32")
+        self._call("nnf_hals_solve_cross_f32", *_mat(UtM), _ptr(Ga), _opt(Gb), _ld(Ga), *_mat(V_in), *_mat(V_out), r, ncols,
+                   int(max_sweeps), float(delta), float(sparsity or 0.0), self._hals_flags(sparsity, normalize, False), _ptr(st))
         return st
 
     def hals_sweeps(self, UtM, UtU, V, nsweeps, sparsity=None, normalize=False, nonzero=False, snapshots=None, snap_first=0,
@@ -366,8 +486,14 @@ class Engine:
         snap_first + j + 1.  sweeps_done / resid_in / resid_out: this call continues a solve of which `sweeps_done` sweeps have
         run (nnf_hals_sweeps_ex_f32): with the residual state handed on (float32 tensors of hals_resid_floats() elements) the
         chunks of a solve are bit for bit one launch of all its sweeps."""
-        _chk2d(UtM, "hals UtM"), _chk2d(UtU, "hals UtU"), _chk2d(V, "hals V")
-        r, ncols = V.shape
+        r, ncols = _solve_ops(UtM, UtU, V, "hals_sweeps")
+        if snapshots is not None:
+            _snap(snapshots, nsweeps - int(snap_first), r, ncols, "hals_sweeps snapshots")
+        need = self.hals_resid_floats(r, ncols) if (resid_in is not None or resid_out is not None) else 0
+        for t in (resid_in, resid_out):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need or t.device != V.device):
+                raise EngineError("hals_sweeps: a residual-state buffer (resid_in, resid_out) must be a contiguous float32 "
+                                  "tensor of hals_resid_floats() elements")
         if (normalize or nonzero) and ncols > self.ROWSYNC_MAX_COLUMNS and snapshots is None and int(nsweeps) > 0:
             # more columns than the generic kernel keeps resident: the rows are walked from the host, one sweep per call of the
             # row-walk (the wall-clock rule's one-sweep probe of nmf() / hals_nnls_acc(deterministic=False) lands here)
@@ -377,46 +503,29 @@ class Engine:
             return torch.tensor(vals, dtype=torch.float64, device=V.device)
         self._check_rowsync_columns(normalize or nonzero, ncols)
         nd = torch.zeros(max(int(nsweeps), 1), dtype=torch.float64, device=V.device)
-        sp, ss = C.c_void_p(0), 0
-        if snapshots is not None:
-            if (snapshots.dtype != torch.float32 or not snapshots.is_contiguous() or snapshots.dim() != 3
-                    or snapshots.shape[0] < nsweeps - int(snap_first) or tuple(snapshots.shape[1:]) != (r, ncols)):
-                raise EngineError("hals_sweeps: snapshots must be a contiguous float32 [>= nsweeps - snap_first, r, ncols] tensor")
-            sp, ss = _ptr(snapshots), snapshots.stride(0)
-        need = self.hals_resid_floats(r, ncols) if (resid_in is not None or resid_out is not None) else 0
-        for t in (resid_in, resid_out):
-            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need or t.device != V.device):
-                raise EngineError("hals_sweeps: a residual-state buffer must be a contiguous float32 tensor of hals_resid_floats() elements")
-        ri = _ptr(resid_in) if (resid_in is not None and need > 0) else C.c_void_p(0)
-        ro = _ptr(resid_out) if (resid_out is not None and need > 0) else C.c_void_p(0)
-        _lib.check(self.lib.nnf_hals_sweeps_ex_f32(self.ctx, _ptr(UtM), _ld(UtM), _ptr(UtU), _ld(UtU), _ptr(V),
-                                                   _ld(V), r, ncols, int(nsweeps), int(sweeps_done), float(sparsity or 0.0),
-                                                   self._hals_flags(sparsity, normalize, nonzero), _ptr(nd), sp, ss,
-                                                   int(snap_first), ri, ro, self._stream()), "nnf_hals_sweeps_ex_f32")
+        keep = need > 0           # (the other kernel layouts carry no state and take NULL)
+        self._call("nnf_hals_sweeps_ex_f32", *_solve_args(UtM, UtU, V), int(nsweeps), int(sweeps_done), float(sparsity or 0.0),
+                   self._hals_flags(sparsity, normalize, nonzero), _ptr(nd), *_optblocks(snapshots), int(snap_first),
+                   _opt(resid_in if keep else None), _opt(resid_out if keep else None))
         return nd[:int(nsweeps)]
 
     def hals_resid_floats(self, r, ncols):
         """Elements of one residual-state buffer for blind chunks on an r x ncols factor (0: the layout that runs keeps no state)."""
-        out = C.c_int64(0)
-        _lib.check(self.lib.nnf_hals_resid_floats(self.ctx, int(r), int(ncols), C.byref(out)), "nnf_hals_resid_floats")
-        return int(out.value)
+        return self._query("nnf_hals_resid_floats", int(r), int(ncols))
 
     def hals_row_update(self, UtM, UtU, V, k, sparsity=None, out=None):
         """Row k of V (this rank's columns) gets the update of nnls.py:162-170, in place; returns a 2-element float64 device
         tensor {sum of squared steps, sum of squares of the updated row} (row-sharded solves with normalize, dist.py)."""
-        _chk2d(UtM, "hals UtM"), _chk2d(UtU, "hals UtU"), _chk2d(V, "hals V")
-        r, ncols = V.shape
-        o = out if out is not None else torch.empty(2, dtype=torch.float64, device=V.device)
-        _lib.check(self.lib.nnf_hals_row_update_f32(self.ctx, _ptr(UtM), _ld(UtM), _ptr(UtU), _ld(UtU), _ptr(V), _ld(V), r, ncols,
-                                                    int(k), float(sparsity or 0.0), self._hals_flags(sparsity, False, False), _ptr(o),
-                                                    self._stream()), "nnf_hals_row_update_f32")
+        _solve_ops(UtM, UtU, V, "hals_row_update")
+        o = _out64(out, 2, V.device, "hals_row_update out")
+        self._call("nnf_hals_row_update_f32", *_solve_args(UtM, UtU, V), int(k), float(sparsity or 0.0),
+                   self._hals_flags(sparsity, False, False), _ptr(o))
         return o
 
     def hals_row_scale(self, V, k, normsq, ncols_total):
         """Row k of V /= sqrt(normsq[0]) (a float64 device scalar), or := 1 / sqrt(ncols_total) when it is 0 (nnls.py:181-185)."""
-        _chk2d(V, "hals V")
-        _lib.check(self.lib.nnf_hals_row_scale_f32(self.ctx, _ptr(V), _ld(V), V.shape[1], int(k), _ptr(normsq), int(ncols_total),
-                                                   self._stream()), "nnf_hals_row_scale_f32")
+        _chk2d(V, "hals_row_scale V"), _f64(normsq, 1, V.device, "hals_row_scale normsq")
+        self._call("nnf_hals_row_scale_f32", *_mat(V), V.shape[1], int(k), _ptr(normsq), int(ncols_total))
         return V
 
     def hals_resident_columns(self, r):
@@ -424,134 +533,100 @@ class Engine:
         sweeps at all, need column blocks of at most this size: dist.sharded_hals_solve)."""
         hit = self._resident_cols.get(int(r))
         if hit is None:
-            out = C.c_int64(0)
-            _lib.check(self.lib.nnf_hals_resident_columns(self.ctx, int(r), C.byref(out)), "nnf_hals_resident_columns")
-            hit = self._resident_cols[int(r)] = int(out.value)
+            hit = self._resident_cols[int(r)] = self._query("nnf_hals_resident_columns", int(r))
         return hit
 
     # ---- grouped kernels (PARAFAC2: K per-slice problems per launch) ------------------------------------
-    @staticmethod
-    def _chk_off(off, what):
-        if off.dtype != torch.int64 or not off.is_cuda or off.dim() != 1 or not off.is_contiguous() or off.numel() < 2:
-            raise EngineError(f"{what}: the segment table must be a contiguous int64 device vector of ngroups + 1 entries")
-        return off.numel() - 1
-
-    @staticmethod
-    def _chk_stack(M, what):
-        if M.dim() != 3 or M.dtype != torch.float32 or not M.is_cuda or (M.shape[2] > 1 and M.stride(2) != 1):
-            raise EngineError(f"{what}: expected a float32 device stack [groups, rows, cols] with unit inner stride")
-        return M
-
     def hals_group_max_columns(self, r):
         """Longest group hals_solve_group takes (nnf_hals_group_max_columns); longer ones go through hals_solve."""
-        out = C.c_int64(0)
-        _lib.check(self.lib.nnf_hals_group_max_columns(self.ctx, int(r), C.byref(out)), "nnf_hals_group_max_columns")
-        return int(out.value)
+        return self._query("nnf_hals_group_max_columns", int(r))
 
     def hals_solve_group(self, UtM, UtU, V, off, max_group_cols, max_sweeps, delta=0.01, status=None):
         """One accelerated-HALS solve per group in ONE launch, in place on V (r x total): group g owns the columns
         [off[g], off[g+1]), its Gram is UtU[g] (a [groups, r, r] stack).  `max_group_cols`: the caller's bound on the group
         lengths (the table lives on the device).  Returns the [groups, 8] float64 status tensor (device, not synced)."""
-        _chk2d(UtM, "group UtM"), _chk2d(V, "group V"), self._chk_stack(UtU, "group UtU")
-        ng = self._chk_off(off, "hals_solve_group")
-        r, total = V.shape
-        if UtM.shape != (r, total) or UtU.shape[0] != ng or UtU.shape[1] < r or UtU.shape[2] < r:
-            raise EngineError("hals_solve_group: shape mismatch")
-        st = status if status is not None else torch.zeros((ng, ST_WORDS), dtype=torch.float64, device=V.device)
-        if st.dtype != torch.float64 or not st.is_contiguous() or st.numel() < ng * ST_WORDS:
-            raise EngineError("hals_solve_group: status must be a contiguous float64 tensor of 8 doubles per group")
-        _lib.check(self.lib.nnf_hals_solve_group_f32(self.ctx, _ptr(UtM), _ld(UtM), _ptr(UtU), UtU.stride(1), UtU.stride(0),
-                                                     _ptr(V), _ld(V), r, _ptr(off), ng, int(max_group_cols), total,
-                                                     int(max_sweeps), float(delta), _ptr(st), self._stream()),
-                   "nnf_hals_solve_group_f32")
+        r, total = _chk2d(V, "hals_solve_group V").shape
+        _shaped(UtM, (r, total), "hals_solve_group UtM"), _stack(UtU, "hals_solve_group UtU")
+        ng = _off(off, "hals_solve_group off")
+        if UtU.shape[0] != ng or UtU.shape[1] < r or UtU.shape[2] < r:
+            raise EngineError(f"hals_solve_group UtU: expected [{ng}, >= {r}, >= {r}], got {tuple(UtU.shape)}")
+        st = torch.zeros((ng, ST_WORDS), dtype=torch.float64, device=V.device) if status is None else \
+            _f64(status, ng * ST_WORDS, V.device, "hals_solve_group status")
+        self._call("nnf_hals_solve_group_f32", *_mat(UtM), _ptr(UtU), UtU.stride(1), UtU.stride(0), *_mat(V), r, _ptr(off), ng,
+                   int(max_group_cols), total, int(max_sweeps), float(delta), _ptr(st))
         return st
 
     def group_gram(self, A, off, B=None, T=None, gram=True, out64=None):
         """Per group of columns of A (r x total), one pass: (G [groups, r, r] float32 = A_g A_g^T or None, dots [groups, r] float64
         = sum_i A[q,i] B[q,i] or None, err [groups] float64 = ||A_g - T_g||_F^2 or None).  out64 (optional, contiguous
         [groups, r, r] float64 device tensor): also receives the Gram sums before they are rounded to fp32."""
-        _chk2d(A, "group_gram A")
-        ng = self._chk_off(off, "group_gram")
-        r, total = A.shape
+        r, total = _chk2d(A, "group_gram A").shape
+        ng = _off(off, "group_gram off")
         for t, nm in ((B, "B"), (T, "T")):
-            if t is not None and _chk2d(t, "group_gram " + nm).shape != A.shape:
-                raise EngineError("group_gram: shape mismatch")
+            if t is not None:
+                _shaped(t, A.shape, "group_gram " + nm)
         if not gram and B is None and T is None:
             raise EngineError("group_gram: nothing asked for")
-        if out64 is not None and (not gram or out64.dtype != torch.float64 or not out64.is_contiguous() or not out64.is_cuda
-                                  or out64.numel() < ng * r * r):
-            raise EngineError("group_gram: out64 must be a contiguous float64 device tensor of groups*r*r elements (with gram=True)")
+        if out64 is not None:
+            if not gram:
+                raise EngineError("group_gram out64: the fp64 Gram sums come with gram=True only")
+            _f64(out64, ng * r * r, A.device, "group_gram out64")
         G = torch.empty((ng, r, r), dtype=torch.float32, device=A.device) if gram else None
         dots = torch.empty((ng, r), dtype=torch.float64, device=A.device) if B is not None else None
         errs = torch.empty(ng, dtype=torch.float64, device=A.device) if T is not None else None
-        _lib.check(self.lib.nnf_group_gram_f32(self.ctx, _ptr(A), _ld(A), r, _ptr(off), ng, total,
-                                               _ptr(G) if gram else None, r, r * r, _ptr(out64) if out64 is not None else None,
-                                               _ptr(B) if B is not None else None, _ld(B) if B is not None else 0,
-                                               _ptr(dots) if dots is not None else None,
-                                               _ptr(T) if T is not None else None, _ld(T) if T is not None else 0,
-                                               _ptr(errs) if errs is not None else None, self._stream()), "nnf_group_gram_f32")
+        self._call("nnf_group_gram_f32", *_mat(A), r, _ptr(off), ng, total, _opt(G), r, r * r, _opt(out64), *_optmat(B), _opt(dots),
+                   *_optmat(T), _opt(errs))
         return G, dots, errs
 
     def group_gemm(self, M, A, off, max_group_cols, out=None):
         """out[:, seg g] = M[g] @ A[:, seg g] for a [groups, p, q] stack M (p, q <= 128) and A (q x total)."""
-        _chk2d(A, "group_gemm A"), self._chk_stack(M, "group_gemm M")
-        ng = self._chk_off(off, "group_gemm")
-        q, total = A.shape
-        p = M.shape[1]
+        q, total = _chk2d(A, "group_gemm A").shape
+        ng, p = _off(off, "group_gemm off"), _stack(M, "group_gemm M").shape[1]
         if M.shape[0] != ng or M.shape[2] != q:
-            raise EngineError("group_gemm: shape mismatch")
-        O = out if out is not None else torch.empty((p, total), dtype=torch.float32, device=A.device)
-        if _chk2d(O, "group_gemm out").shape != (p, total) or O.data_ptr() == A.data_ptr():
-            raise EngineError("group_gemm: out must be a p x total float32 tensor that does not alias A")
-        _lib.check(self.lib.nnf_group_gemm_f32(self.ctx, _ptr(M), M.stride(1), M.stride(0), p, q, _ptr(A), _ld(A), _ptr(off), ng,
-                                               int(max_group_cols), total, _ptr(O), _ld(O), self._stream()), "nnf_group_gemm_f32")
+            raise EngineError(f"group_gemm M: expected [{ng}, p, {q}], got {tuple(M.shape)}")
+        O = _out(out, (p, total), A, "group_gemm out")
+        if O.data_ptr() == A.data_ptr():
+            raise EngineError("group_gemm out must not alias A")
+        self._call("nnf_group_gemm_f32", _ptr(M), M.stride(1), M.stride(0), p, q, *_mat(A), _ptr(off), ng, int(max_group_cols),
+                   total, *_mat(O))
         return O
 
     def frob_resid_rows(self, X, Ut, V, out=None):
         """Per-row ||x_i - (Ut^T V)_i||^2 as m float64 on the device (one streaming pass, nnf_frob_resid_rows_f32)."""
-        _chk2d(X, "frob X"), _chk2d(Ut, "frob Ut"), _chk2d(V, "frob V")
-        m, n = X.shape
-        r = Ut.shape[0]
-        if Ut.shape[1] != m or V.shape != (r, n):
-            raise EngineError("frob_resid_rows: shape mismatch")
-        o = out if out is not None else torch.empty(m, dtype=torch.float64, device=X.device)
-        if o.dtype != torch.float64 or not o.is_contiguous() or o.numel() < m:
-            raise EngineError("frob_resid_rows: out must be a contiguous float64 tensor of m elements")
-        _lib.check(self.lib.nnf_frob_resid_rows_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V), _ld(V), r,
-                                                    _ptr(o), self._stream()), "nnf_frob_resid_rows_f32")
+        m, n, r = _xuv(X, Ut, V, "frob_resid_rows")
+        o = _out64(out, m, X.device, "frob_resid_rows out")
+        self._call("nnf_frob_resid_rows_f32", *_triple(X, Ut, V), _ptr(o))
         return o
 
     def hals_stop_restore(self, sums, head, budget, delta, V, snapshots, status):
-        """Device-side replay of the stopping rule over the all-reduced per-sweep sums of a blind chunk (dist.py)."""
-        _chk2d(V, "hals V")
-        r, ncols = V.shape
-        n = int(sums.numel())
-        if sums.dtype != torch.float64 or not sums.is_contiguous() or status.dtype != torch.float64:
-            raise EngineError("hals_stop_restore: sums / status must be float64 device tensors")
-        sp = _ptr(snapshots) if snapshots is not None else C.c_void_p(0)
-        ss = snapshots.stride(0) if snapshots is not None else 0
-        _lib.check(self.lib.nnf_hals_stop_restore_f32(self.ctx, _ptr(sums), n, int(head), int(budget), float(delta), _ptr(V),
-                                                      _ld(V), r, ncols, sp, ss, _ptr(status), self._stream()),
-                   "nnf_hals_stop_restore_f32")
+        """Device-side replay of the stopping rule over the all-reduced per-sweep sums of a blind chunk (dist.py): `snapshots`
+        (or None) holds V after each of the last sums.numel() - head sweeps.  One block per sweep of the window is asked for, as
+        hals_sweeps writes them; that is one more than the replay can ever restore from (a stop at the last sweep restores
+        nothing), so the rule is stricter than the library needs.  `sums` sets the number of sweeps: it has no wrong length.
+        `status` takes the first four words of a solve's status block (eps, cnt, eps0, err)."""
+        r, ncols = _chk2d(V, "hals_stop_restore V").shape
+        n = _f64(sums, 1, V.device, "hals_stop_restore sums").numel()
+        _f64(status, ST_ERR + 1, V.device, "hals_stop_restore status")
+        if snapshots is not None:
+            _snap(snapshots, n - int(head), r, ncols, "hals_stop_restore snapshots")
+        self._call("nnf_hals_stop_restore_f32", _ptr(sums), n, int(head), int(budget), float(delta), *_mat(V), r, ncols,
+                   *_optblocks(snapshots), _ptr(status))
         return status
 
     # ---- MU / beta-divergence -----------------------------------------------------------------------
     MU_FUSED_MAX_RANK = 64   # the fused COST forms (mu_left(cost_out=...), mu_left_num) are built for r <= 64
     MU_FUSED_UPDATE_MAX_RANK = 128   # the fused two-MFMA updates: r <= 128 for every beta (beta = 2 has no limit: Gram form)
 
-    def _mu_large_rank(self, X, Ut, V, beta, side):
+    def _mu_large_rank(self, X, Ut, V, beta, side, checked=False):
         """r > 128 (any beta; the model then builds up over rank chunks inside R1; callable at any rank, which is how
         tools/time_mu_rank.py times it against the fused kernels): one pass writes the element-wise operands R1 = X.*(UV)^(beta-2), R2 = (UV)^(beta-1)
         (m x n device scratch each), then the numerator / denominator are plain X H^T ('left') or W^T X ('right') products.
-        Returns (num, den or None, den_vec or None) like mu_right_accum."""
-        m, n = X.shape
-        r = Ut.shape[0]
+        Returns (num, den or None, den_vec or None) like mu_right_accum.  `checked`: the caller has run _xuv on the triple."""
+        (m, n) = X.shape if checked else _xuv(X, Ut, V, "_mu_large_rank")[:2]
         kl = float(beta) == 1.0
         R1 = torch.empty((m, n), dtype=torch.float32, device=X.device)
         R2 = None if kl else torch.empty((m, n), dtype=torch.float32, device=X.device)
-        _lib.check(self.lib.nnf_mu_ratio_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V),
-                                             _ld(V), r, float(beta), _ptr(R1), _ptr(R2) if R2 is not None else None,
-                                             _ld(R1), self._stream()), "nnf_mu_ratio_f32")
+        self._call("nnf_mu_ratio_f32", *_triple(X, Ut, V), float(beta), _ptr(R1), _opt(R2), _ld(R1))
         if side == "left":
             num = self.xht(R1, V)
             den = None if kl else self.xht(R2, V)
@@ -562,27 +637,25 @@ class Engine:
             dvec = Ut.sum(dim=1, dtype=torch.float64) if kl else None
         return num, den, dvec
 
+    def _mu_composed(self, r, beta):
+        """Whether an update of rank r goes through _mu_large_rank + mu_apply (no fused kernel there)."""
+        return (r > self.MU_FUSED_UPDATE_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK
+
     def mu_left(self, X, Ut, V, beta, out=None, cost_out=None):
         """`cost_out` (1-element float64 device tensor; beta = 1, r <= 64 only): also receives beta_divergence(X, U V, 1) of
         the INPUT factors (nnf_mu_left_kl_cost_f32)."""
-        _chk2d(X, "mu X"), _chk2d(Ut, "mu Ut"), _chk2d(V, "mu V")
-        m, n = X.shape
-        r = Ut.shape[0]
+        m, n, r = _xuv(X, Ut, V, "mu_left")
         if cost_out is not None:
             if float(beta) != 1.0 or r > self.MU_FUSED_MAX_RANK:
-                raise EngineError("mu_left: the fused cost is built for beta = 1 and r <= 64")
-            O = out if out is not None else torch.empty_like(Ut)
-            _lib.check(self.lib.nnf_mu_left_kl_cost_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V), _ld(V),
-                                                        r, _ptr(O), _ld(O), _ptr(cost_out), self._stream()),
-                       "nnf_mu_left_kl_cost_f32")
-            return O
-        if (r > self.MU_FUSED_UPDATE_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
-            num, den, dvec = self._mu_large_rank(X, Ut, V, beta, "left")
-            return self.mu_apply(Ut, num, den, dvec, beta, out=out)
-        O = out if out is not None else torch.empty_like(Ut)
-        _lib.check(self.lib.nnf_mu_left_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V),
-                                            _ld(V), r, float(beta), _ptr(O), _ld(O), self._stream()),
-                   "nnf_mu_left_f32")
+                raise EngineError("mu_left cost_out: the fused cost is built for beta = 1 and r <= 64")
+            _f64(cost_out, 1, X.device, "mu_left cost_out")
+        O = _out(out, (r, m), Ut, "mu_left out")
+        if cost_out is not None:
+            self._call("nnf_mu_left_kl_cost_f32", *_triple(X, Ut, V), *_mat(O), _ptr(cost_out))
+        elif self._mu_composed(r, beta):
+            self.mu_apply(Ut, *self._mu_large_rank(X, Ut, V, beta, "left", checked=True), beta, out=O)
+        else:
+            self._call("nnf_mu_left_f32", *_triple(X, Ut, V), float(beta), *_mat(O))
         return O
 
     MU_MODE_MAX_RANK = 64   # the mode update on the tensor's own layout (mu_mode)
@@ -591,64 +664,48 @@ class Engine:
         """mu_betadivmin of one mode's factor against tl.unfold(T, n) without forming it: `T3` is the contiguous tensor seen
         as (L, I_n, K), `Ft` the mode's transposed factor (r x I_n), `V` the other operand (r x L*K, column l*K + k for the
         entries T3[l, :, k]).  r <= 64 (nnf_mu_mode_f32)."""
-        _chk2d(Ft, "mu Ft"), _chk2d(V, "mu V")
-        if T3.dim() != 3 or T3.dtype != torch.float32 or not T3.is_cuda or not T3.is_contiguous():
-            raise EngineError("mu_mode: T3 must be a contiguous float32 device tensor seen as (L, I, K)")
-        L, I, K = (int(d) for d in T3.shape)
-        r = Ft.shape[0]
-        if Ft.shape[1] != I or tuple(V.shape) != (r, L * K):
-            raise EngineError("mu_mode: shape mismatch")
+        L, I, K = _t3(T3, "mu_mode: T3, seen as (L, I, K),").shape
+        r = _chk2d(Ft, "mu_mode Ft").shape[0]
+        if Ft.shape[1] != I:
+            raise EngineError(f"mu_mode Ft: shape mismatch, T3 is {tuple(T3.shape)}, Ft {tuple(Ft.shape)}")
+        _shaped(V, (r, L * K), "mu_mode V")
         if r > self.MU_MODE_MAX_RANK:
-            raise EngineError("mu_mode: built for r <= 64")
-        if out is not None and (_chk2d(out, "mu out").shape != Ft.shape or out.device != Ft.device):
-            raise EngineError("mu_mode: out must be an r x I float32 tensor on the factor's device")
-        O = out if out is not None else torch.empty_like(Ft)
-        _lib.check(self.lib.nnf_mu_mode_f32(self.ctx, _ptr(T3), L, I, K, _ptr(Ft), _ld(Ft), _ptr(V), _ld(V), r, float(beta),
-                                            _ptr(O), _ld(O), self._stream()), "nnf_mu_mode_f32")
+            raise EngineError("mu_mode Ft: built for r <= 64")
+        O = _out(out, (r, I), Ft, "mu_mode out")
+        self._call("nnf_mu_mode_f32", _ptr(T3), L, I, K, *_mat(Ft), *_mat(V), r, float(beta), *_mat(O))
         return O
 
     def mu_right(self, X, Ut, V, beta, out=None):
-        _chk2d(X, "mu X"), _chk2d(Ut, "mu Ut"), _chk2d(V, "mu V")
-        m, n = X.shape
-        r = Ut.shape[0]
-        if (r > self.MU_FUSED_UPDATE_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
-            num, den, dvec = self._mu_large_rank(X, Ut, V, beta, "right")
-            return self.mu_apply(V, num, den, dvec, beta, out=out)
-        O = out if out is not None else torch.empty_like(V)
-        _lib.check(self.lib.nnf_mu_right_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V),
-                                             _ld(V), r, float(beta), _ptr(O), _ld(O), self._stream()),
-                   "nnf_mu_right_f32")
+        m, n, r = _xuv(X, Ut, V, "mu_right")
+        O = _out(out, (r, n), V, "mu_right out")
+        if self._mu_composed(r, beta):
+            self.mu_apply(V, *self._mu_large_rank(X, Ut, V, beta, "right", checked=True), beta, out=O)
+        else:
+            self._call("nnf_mu_right_f32", *_triple(X, Ut, V), float(beta), *_mat(O))
         return O
 
     def mu_right_accum(self, X, Ut, V, beta):
         """This row block's numerator / denominator of the right update (row-sharded runs): returns (num r x n,
         den r x n or None, den_vec r doubles or None); all three are sums over the rows and all-reduce additively."""
-        _chk2d(X, "mu X"), _chk2d(Ut, "mu Ut"), _chk2d(V, "mu V")
-        m, n = X.shape
-        r = Ut.shape[0]
-        if (r > self.MU_FUSED_UPDATE_MAX_RANK and float(beta) != 2.0) or r > MAX_RANK:
-            return self._mu_large_rank(X, Ut, V, beta, "right")
+        m, n, r = _xuv(X, Ut, V, "mu_right_accum")
+        if self._mu_composed(r, beta):
+            return self._mu_large_rank(X, Ut, V, beta, "right", checked=True)
         num = torch.empty((r, n), dtype=torch.float32, device=X.device)
         den = torch.empty((r, n), dtype=torch.float32, device=X.device) if float(beta) != 1.0 else None
         dvec = torch.empty(r, dtype=torch.float64, device=X.device) if float(beta) == 1.0 else None
-        _lib.check(self.lib.nnf_mu_right_accum_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V),
-                                                   _ld(V), r, float(beta), _ptr(num), _ld(num),
-                                                   _ptr(den) if den is not None else None,
-                                                   _ld(den) if den is not None else 0,
-                                                   _ptr(dvec) if dvec is not None else None, self._stream()),
-                   "nnf_mu_right_accum_f32")
+        self._call("nnf_mu_right_accum_f32", *_triple(X, Ut, V), float(beta), *_mat(num), *_optmat(den), _opt(dvec))
         return num, den, dvec
 
     def mu_apply(self, F, num, den, den_vec, beta, out=None):
         """out = max(F * (num/den)^gamma(beta), 1e-12) (mu.py:84-97) from already reduced numerator / denominator."""
-        _chk2d(F, "mu F"), _chk2d(num, "mu num")
-        r, cols = F.shape
-        O = out if out is not None else torch.empty_like(F)
-        _lib.check(self.lib.nnf_mu_apply_f32(self.ctx, _ptr(F), _ld(F), r, cols, _ptr(num), _ld(num),
-                                             _ptr(den) if den is not None else None,
-                                             _ld(den) if den is not None else 0,
-                                             _ptr(den_vec) if den_vec is not None else None, float(beta), _ptr(O),
-                                             _ld(O), self._stream()), "nnf_mu_apply_f32")
+        r, cols = _chk2d(F, "mu_apply F").shape
+        _shaped(num, (r, cols), "mu_apply num")
+        if den is not None:
+            _shaped(den, (r, cols), "mu_apply den")
+        if den_vec is not None:
+            _f64(den_vec, r, F.device, "mu_apply den_vec")
+        O = _out(out, (r, cols), F, "mu_apply out")
+        self._call("nnf_mu_apply_f32", *_mat(F), r, cols, *_mat(num), *_optmat(den), _opt(den_vec), float(beta), *_mat(O))
         return O
 
     SIMPLEX_MAX_ITER = 1024   # Newton iterations one nnf_simplex_proj_kl_f32 call takes (one stopping slot each)
@@ -660,68 +717,47 @@ class Engine:
         that puts its columns on the unit simplex.  `num`, and exactly one of `den` (r x cols) and `den_vec` (r float64), are
         what mu_right_accum(..., 1) returns.  Returns (H_out or None, status): status = 2 float64 on the device, {iterations run,
         max |dlambda| of the last one}; `lambda_out` (cols float64) receives the multipliers.  `out` may be H itself."""
-        _chk2d(H, "simplex H"), _chk2d(num, "simplex num")
-        r, cols = H.shape
-        if num.shape != (r, cols) or (den is None) == (den_vec is None):
-            raise EngineError("simplex_proj: num must have H's shape, and exactly one of den / den_vec is given")
-        if den is not None and _chk2d(den, "simplex den").shape != (r, cols):
-            raise EngineError("simplex_proj: den must have H's shape")
-        f64 = [("den_vec", den_vec, r), ("lambda0", lambda0, cols), ("lambda_out", lambda_out, cols), ("status", status, 2)]
-        for name, t, count in f64:
-            if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() < count):
-                raise EngineError(f"simplex_proj: {name} must be a contiguous float64 device tensor of {count} elements")
+        r, cols = _chk2d(H, "simplex_proj H").shape
+        _shaped(num, (r, cols), "simplex_proj num")
+        if (den is None) == (den_vec is None):
+            raise EngineError("simplex_proj: exactly one of den / den_vec is given")
+        if den is not None:
+            _shaped(den, (r, cols), "simplex_proj den")
+        for name, t, count in (("den_vec", den_vec, r), ("lambda0", lambda0, cols), ("lambda_out", lambda_out, cols)):
+            if t is not None:
+                _f64(t, count, H.device, "simplex_proj " + name)
         if r > MAX_RANK or not 1 <= int(max_iter) <= self.SIMPLEX_MAX_ITER:
             raise EngineError(f"simplex_proj: built for r <= {MAX_RANK} and 1 <= max_iter <= {self.SIMPLEX_MAX_ITER}")
-        O = None
-        if update:
-            O = out if out is not None else torch.empty_like(H)
-            if _chk2d(O, "simplex out").shape != (r, cols):
-                raise EngineError("simplex_proj: out must have H's shape")
-        st = status if status is not None else torch.empty(2, dtype=torch.float64, device=H.device)
-        _lib.check(self.lib.nnf_simplex_proj_kl_f32(self.ctx, _ptr(H), _ld(H), r, cols, _ptr(num), _ld(num),
-                                                    _ptr(den) if den is not None else None, _ld(den) if den is not None else 0,
-                                                    _ptr(den_vec) if den_vec is not None else None,
-                                                    _ptr(lambda0) if lambda0 is not None else None, float(tol), int(max_iter),
-                                                    _ptr(O) if O is not None else None, _ld(O) if O is not None else 0,
-                                                    _ptr(lambda_out) if lambda_out is not None else None, _ptr(st),
-                                                    self._stream()), "nnf_simplex_proj_kl_f32")
+        st = _out64(status, 2, H.device, "simplex_proj status")
+        O = _out(out, (r, cols), H, "simplex_proj out") if update else None
+        self._call("nnf_simplex_proj_kl_f32", *_mat(H), r, cols, *_mat(num), *_optmat(den), _opt(den_vec), _opt(lambda0),
+                   float(tol), int(max_iter), *_optmat(O), _opt(lambda_out), _ptr(st))
         return O, st
 
     # ---- deep KL-NMF (deep_mu.py:8-14) -------------------------------------------------------------
     def mu_left_num(self, X, Ut, V, out=None):
         """Raw KL numerator of the left update: num[k,i] = sum_j (X[i,j] / (UV)[i,j]) V[k,j]  (r x m)."""
-        _chk2d(X, "mu X"), _chk2d(Ut, "mu Ut"), _chk2d(V, "mu V")
-        m, n = X.shape
-        r = Ut.shape[0]
-        if Ut.shape[1] != m or V.shape != (r, n):
-            raise EngineError("mu_left_num: shape mismatch")
-        O = out if out is not None else torch.empty((r, m), dtype=torch.float32, device=X.device)
-        _lib.check(self.lib.nnf_mu_left_num_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V), _ld(V), r,
-                                                _ptr(O), _ld(O), self._stream()), "nnf_mu_left_num_f32")
+        m, n, r = _xuv(X, Ut, V, "mu_left_num")
+        O = _out(out, (r, m), X, "mu_left_num out")
+        self._call("nnf_mu_left_num_f32", *_triple(X, Ut, V), *_mat(O))
         return O
 
     def small_gemm(self, A, B, out=None):
         """A (p x q, q <= 2048) @ B (q x cols) -> p x cols: a rank-sized left operand against a wide matrix."""
-        _chk2d(A, "small_gemm A"), _chk2d(B, "small_gemm B")
-        p, q = A.shape
+        (p, q), cols = _chk2d(A, "small_gemm A").shape, _chk2d(B, "small_gemm B").shape[1]
         if B.shape[0] != q:
-            raise EngineError("small_gemm: shape mismatch")
-        cols = B.shape[1]
-        O = out if out is not None else torch.empty((p, cols), dtype=torch.float32, device=A.device)
-        _lib.check(self.lib.nnf_small_gemm_f32(self.ctx, _ptr(A), _ld(A), p, q, _ptr(B), _ld(B), cols, _ptr(O), _ld(O),
-                                               self._stream()), "nnf_small_gemm_f32")
+            raise EngineError(f"small_gemm B: shape mismatch, A is {p} x {q}, B {tuple(B.shape)}")
+        O = _out(out, (p, cols), A, "small_gemm out")
+        self._call("nnf_small_gemm_f32", *_mat(A), p, q, *_mat(B), cols, *_mat(O))
         return O
 
     def deep_kl_apply(self, Ft, num, hsum, WHnext_t, lam, out=None):
         """max(1e-12, (b/lam) / (W0(b exp(a/lam)/lam) + 1e-12)) with b = Ft .* num, a = hsum[k] - lam log(WHnext_t)."""
-        _chk2d(Ft, "deep F"), _chk2d(num, "deep num"), _chk2d(WHnext_t, "deep WHnext")
-        r, cols = Ft.shape
-        if num.shape != (r, cols) or WHnext_t.shape != (r, cols) or hsum.dtype != torch.float64 or hsum.numel() != r:
-            raise EngineError("deep_kl_apply: shape mismatch")
-        O = out if out is not None else torch.empty_like(Ft)
-        _lib.check(self.lib.nnf_deep_kl_apply_f32(self.ctx, _ptr(Ft), _ld(Ft), r, cols, _ptr(num), _ld(num), _ptr(hsum),
-                                                  _ptr(WHnext_t), _ld(WHnext_t), float(lam), _ptr(O), _ld(O),
-                                                  self._stream()), "nnf_deep_kl_apply_f32")
+        r, cols = _chk2d(Ft, "deep_kl_apply Ft").shape
+        _shaped(num, (r, cols), "deep_kl_apply num"), _shaped(WHnext_t, (r, cols), "deep_kl_apply WHnext_t")
+        _f64(hsum, r, Ft.device, "deep_kl_apply hsum", exact=True)
+        O = _out(out, (r, cols), Ft, "deep_kl_apply out")
+        self._call("nnf_deep_kl_apply_f32", *_mat(Ft), r, cols, *_mat(num), _ptr(hsum), *_mat(WHnext_t), float(lam), *_mat(O))
         return O
 
     PROBE_KERNELS = {"xty": 0, "xht": 1, "cost": 2, "hals": 3, "mu_left": 4, "mu_right": 5, "mttkrp": 6}
@@ -733,19 +769,19 @@ class Engine:
         hipEvent_t lazily)."""
         b = C.c_void_p(ev_begin.cuda_event) if ev_begin is not None else None
         e = C.c_void_p(ev_end.cuda_event) if ev_end is not None else None
-        _lib.check(self.lib.nnf_ctx_set_probe_kernel(self.ctx, self.PROBE_KERNELS[kernel]), "nnf_ctx_set_probe_kernel")
-        _lib.check(self.lib.nnf_ctx_set_probe(self.ctx, b, e), "nnf_ctx_set_probe")
+        _lib.call(self.lib, "nnf_ctx_set_probe_kernel", self.ctx, self.PROBE_KERNELS[kernel])
+        _lib.call(self.lib, "nnf_ctx_set_probe", self.ctx, b, e)
 
     def set_probe_ring(self, pairs=None, kernel="xty"):
         """Measurement hook for a whole timed region (bench.py): `pairs` = [(begin, end), ...] of already recorded
         torch.cuda.Event(enable_timing=True); the i-th launch of `kernel` from now on records pair i on its launch stream
         (launches beyond the list record nothing).  None removes the ring (nnf_ctx_set_probe_ring)."""
-        _lib.check(self.lib.nnf_ctx_set_probe_kernel(self.ctx, self.PROBE_KERNELS[kernel]), "nnf_ctx_set_probe_kernel")
+        _lib.call(self.lib, "nnf_ctx_set_probe_kernel", self.ctx, self.PROBE_KERNELS[kernel])
         if not pairs:
-            _lib.check(self.lib.nnf_ctx_set_probe_ring(self.ctx, None, 0), "nnf_ctx_set_probe_ring")
+            _lib.call(self.lib, "nnf_ctx_set_probe_ring", self.ctx, None, 0)
             return
         arr = (C.c_void_p * (2 * len(pairs)))(*[C.c_void_p(e.cuda_event) for pr in pairs for e in pr])
-        _lib.check(self.lib.nnf_ctx_set_probe_ring(self.ctx, arr, len(pairs)), "nnf_ctx_set_probe_ring")
+        _lib.call(self.lib, "nnf_ctx_set_probe_ring", self.ctx, arr, len(pairs))
 
     def probe_ring_count(self):
         """Pairs of the current ring recorded so far."""
@@ -780,123 +816,79 @@ class Engine:
     # ---- NTD -----------------------------------------------------------------------------------------
     def mttkrp3_from_partial(self, Y, Ft, axis, out=None):
         """Y (R x A x B, contiguous) contracted with the rows of Ft over `axis` (1: A, 2: B) -> R x (the other extent)."""
-        if Y.dim() != 3 or Y.dtype != torch.float32 or not Y.is_contiguous():
-            raise EngineError("mttkrp3_from_partial: Y must be a contiguous 3-way float32 tensor")
-        _chk2d(Ft, "partial factor")
-        R, A, B = Y.shape
-        other = B if axis == 1 else A
-        if Ft.shape != (R, A if axis == 1 else B):
-            raise EngineError("mttkrp3_from_partial: shape mismatch")
-        O = out if out is not None else torch.empty((R, other), dtype=torch.float32, device=Y.device)
-        _lib.check(self.lib.nnf_mttkrp3_from_partial_f32(self.ctx, _ptr(Y), A, B, _ptr(Ft), _ld(Ft), R, int(axis), _ptr(O),
-                                                         _ld(O), self._stream()), "nnf_mttkrp3_from_partial_f32")
+        R, A, B = _t3(Y, "mttkrp3_from_partial: Y").shape
+        _shaped(Ft, (R, A if axis == 1 else B), "mttkrp3_from_partial Ft")
+        O = _out(out, (R, B if axis == 1 else A), Y, "mttkrp3_from_partial out")
+        self._call("nnf_mttkrp3_from_partial_f32", _ptr(Y), A, B, *_mat(Ft), R, int(axis), *_mat(O))
         return O
 
     def ttm3(self, T, Ft, mode, out=None):
         """T x_mode F^T for a contiguous 3-way tensor and a transposed factor Ft (r x I_mode).
         Result layout: mode 0 -> (r, J, K); mode 1 -> (I, r, K); mode 2 -> (r, I, J)  (include/nnfac_hip.h)."""
-        if T.dim() != 3 or not T.is_contiguous():
-            raise err.ArgumentException("ttm3 needs a contiguous 3-way tensor")
-        _chk2d(Ft, "ttm3 Ft")
-        I, J, K = T.shape
-        r = Ft.shape[0]
+        I, J, K = _t3(T, "ttm3: T", err.ArgumentException).shape
+        r = _chk2d(Ft, "ttm3 Ft").shape[0]
+        if mode not in (0, 1, 2) or Ft.shape[1] != T.shape[mode]:
+            raise EngineError(f"ttm3 Ft: r x {tuple(T.shape)}[mode] with mode in 0..2 expected, got {tuple(Ft.shape)}, mode {mode}")
         shape = (r, J, K) if mode == 0 else ((I, r, K) if mode == 1 else (r, I, J))
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=T.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
-            raise EngineError("ttm3: `out` must be a contiguous float32 tensor of shape " + str(shape))
-        _lib.check(self.lib.nnf_ttm3_f32(self.ctx, _ptr(T), I, J, K, _ptr(Ft), _ld(Ft), r, int(mode), _ptr(out),
-                                         self._stream()), "nnf_ttm3_f32")
+        elif _t3(out, "ttm3: out").shape != shape or out.device != T.device:
+            raise EngineError(f"ttm3: out must have shape {shape} on {T.device}, got {tuple(out.shape)} on {out.device}")
+        self._call("nnf_ttm3_f32", _ptr(T), I, J, K, *_mat(Ft), r, int(mode), _ptr(out))
         return out
 
     def ntd_core_pg(self, core, MtX, grams, sparse, delta, max_iter, norm_sq, status=None):
         """Projected-gradient core update (ntd.py:588-619), in place on `core`; returns the 6-double status block
         {iterations, last update, first update, step, reconstruction error, 0} (device tensor, no sync)."""
-        if core.dim() != 3 or not core.is_contiguous() or core.dtype != torch.float32:
+        if core.dim() != 3:
             raise err.ArgumentException("ntd_core_pg updates a contiguous float32 3-way core in place")
-        d0, d1, d2 = core.shape
-        st = status if status is not None else torch.empty(6, dtype=torch.float64, device=core.device)
-        MtX = MtX.contiguous()
-        M = [g.contiguous() for g in grams]
-        _lib.check(self.lib.nnf_ntd_core_pg_f32(self.ctx, _ptr(core), _ptr(MtX), _ptr(M[0]), _ptr(M[1]), _ptr(M[2]), d0, d1,
-                                                d2, float(sparse), float(delta), int(max_iter), float(norm_sq), _ptr(st),
-                                                self._stream()), "nnf_ntd_core_pg_f32")
+        MtX, M, st = _core_ops(core, MtX, grams, status, "ntd_core_pg")
+        self._call("nnf_ntd_core_pg_f32", _ptr(core), _ptr(MtX), _ptr(M[0]), _ptr(M[1]), _ptr(M[2]), *core.shape, float(sparse),
+                   float(delta), int(max_iter), float(norm_sq), _ptr(st))
         return st
 
     def ntd_core_pgn(self, core, MtX, grams, sparse, delta, max_iter, norm_sq, status=None):
         """ntd_core_pg for a core of any order 3..8 (nnf_ntd_core_pgn_f32: the mode products run mode by mode, no merged
         trailing mode); in place on `core`, returns the same 6-double status block."""
-        if not core.is_contiguous() or core.dtype != torch.float32:
-            raise err.ArgumentException("ntd_core_pgn updates a contiguous float32 core in place")
-        if len(grams) != core.dim() or tuple(MtX.shape) != tuple(core.shape):
-            raise err.ArgumentException("ntd_core_pgn needs one Gram per core mode and an MtX of the core's shape")
-        for g, d in zip(grams, core.shape):
-            if tuple(g.shape) != (d, d) or g.dtype != torch.float32:
-                raise err.ArgumentException("ntd_core_pgn: the Gram of a mode of extent d is a float32 d x d matrix")
-        st = status if status is not None else torch.empty(6, dtype=torch.float64, device=core.device)
-        MtX = MtX.contiguous()
-        if MtX.dtype != torch.float32:
-            raise err.ArgumentException("ntd_core_pgn: MtX must be float32")
-        M = [g.contiguous() for g in grams]
+        MtX, M, st = _core_ops(core, MtX, grams, status, "ntd_core_pgn")
         n = core.dim()
         ptrs = (C.c_void_p * n)(*[g.data_ptr() for g in M])
         dims = (C.c_int * n)(*[int(d) for d in core.shape])
-        _lib.check(self.lib.nnf_ntd_core_pgn_f32(self.ctx, _ptr(core), _ptr(MtX), ptrs, n, dims, float(sparse), float(delta),
-                                                 int(max_iter), float(norm_sq), _ptr(st), self._stream()),
-                   "nnf_ntd_core_pgn_f32")
+        self._call("nnf_ntd_core_pgn_f32", _ptr(core), _ptr(MtX), ptrs, n, dims, float(sparse), float(delta), int(max_iter),
+                   float(norm_sq), _ptr(st))
         return st
 
     def betadiv(self, X, Ut, V, beta, out=None):
-        _chk2d(X, "betadiv X"), _chk2d(Ut, "betadiv Ut"), _chk2d(V, "betadiv V")
-        m, n = X.shape
-        r = Ut.shape[0]
-        o = out if out is not None else torch.empty(1, dtype=torch.float64, device=X.device)
+        m, n, r = _xuv(X, Ut, V, "betadiv")
+        o = _out64(out, 1, X.device, "betadiv out")
         self._model_scratch(m, n, r)
-        _lib.check(self.lib.nnf_betadiv_f32(self.ctx, _ptr(X), m, n, _ld(X), _ptr(Ut), _ld(Ut), _ptr(V),
-                                            _ld(V), r, float(beta), _ptr(o), self._stream()), "nnf_betadiv_f32")
+        self._call("nnf_betadiv_f32", *_triple(X, Ut, V), float(beta), _ptr(o))
         return o
 
     def mttkrp3(self, T, Ft, mode, out=None):
         """T (I x J x K, contiguous), Ft = [F0^T, F1^T, F2^T] (each R x dim) -> R x dim_mode."""
-        if T.dim() != 3 or T.dtype != torch.float32 or not T.is_contiguous():
-            raise EngineError("mttkrp3: T must be a contiguous 3-way float32 tensor")
-        for f in Ft:
-            _chk2d(f, "mttkrp factor")
-        I, J, K = T.shape
-        R = Ft[0].shape[0]
-        O = out if out is not None else torch.empty((R, T.shape[mode]), dtype=torch.float32, device=T.device)
-        _lib.check(self.lib.nnf_mttkrp3_f32(self.ctx, _ptr(T), I, J, K, _ptr(Ft[0]), _ld(Ft[0]), _ptr(Ft[1]),
-                                            _ld(Ft[1]), _ptr(Ft[2]), _ld(Ft[2]), R, int(mode), _ptr(O),
-                                            _ld(O), self._stream()), "nnf_mttkrp3_f32")
+        R = _cp3(T, Ft, "mttkrp3")
+        O = _out(out, (R, T.shape[mode]), T, "mttkrp3 out")
+        self._call("nnf_mttkrp3_f32", *_cp3_args(T, Ft), int(mode), *_mat(O))
         return O
-
 
     CP3_FUSED_MAX_RANK = 64
 
     def cp3_partial_cost(self, T, Ft, Y, cost):
         """One pass over T: cost[0] = ||T - [[F0,F1,F2]]||^2 (float64 device scalar) and Y[r][i][j] = sum_k T[i,j,k] F2[k,r]."""
-        if T.dim() != 3 or T.dtype != torch.float32 or not T.is_contiguous():
-            raise EngineError("cp3_partial_cost: T must be a contiguous 3-way float32 tensor")
-        I, J, K = T.shape
-        R = Ft[0].shape[0]
-        if tuple(Y.shape) != (R, I, J) or Y.dtype != torch.float32 or not Y.is_contiguous():
-            raise EngineError("cp3_partial_cost: Y must be a contiguous float32 R x I x J tensor")
-        _lib.check(self.lib.nnf_cp3_partial_cost_f32(self.ctx, _ptr(T), I, J, K, _ptr(Ft[0]), _ld(Ft[0]), _ptr(Ft[1]),
-                                                     _ld(Ft[1]), _ptr(Ft[2]), _ld(Ft[2]), R, _ptr(Y), _ptr(cost),
-                                                     self._stream()), "nnf_cp3_partial_cost_f32")
+        R = _cp3(T, Ft, "cp3_partial_cost")
+        if _t3(Y, "cp3_partial_cost: Y").shape != (R, *T.shape[:2]) or Y.device != T.device:
+            raise EngineError(f"cp3_partial_cost: Y must be R x I x J on {T.device}, got {tuple(Y.shape)} on {Y.device}")
+        _f64(cost, 1, T.device, "cp3_partial_cost cost")
+        self._call("nnf_cp3_partial_cost_f32", *_cp3_args(T, Ft), _ptr(Y), _ptr(cost))
         return Y
 
     def cp3_betadiv(self, T, Ft, beta, out=None):
         """beta-divergence between T (I x J x K) and the CP model of Ft = [F0^T, F1^T, F2^T]; float64 device scalar."""
-        if T.dim() != 3 or T.dtype != torch.float32 or not T.is_contiguous():
-            raise EngineError("cp3_betadiv: T must be a contiguous 3-way float32 tensor")
-        I, J, K = T.shape
-        R = Ft[0].shape[0]
-        o = out if out is not None else torch.empty(1, dtype=torch.float64, device=T.device)
-        self._model_scratch(I * J, K, R)
-        _lib.check(self.lib.nnf_cp3_betadiv_f32(self.ctx, _ptr(T), I, J, K, _ptr(Ft[0]), _ld(Ft[0]), _ptr(Ft[1]),
-                                                _ld(Ft[1]), _ptr(Ft[2]), _ld(Ft[2]), R, float(beta), _ptr(o),
-                                                self._stream()), "nnf_cp3_betadiv_f32")
+        R = _cp3(T, Ft, "cp3_betadiv")
+        o = _out64(out, 1, T.device, "cp3_betadiv out")
+        self._model_scratch(T.shape[0] * T.shape[1], T.shape[2], R)
+        self._call("nnf_cp3_betadiv_f32", *_cp3_args(T, Ft), float(beta), _ptr(o))
         return o
 
 
@@ -908,14 +900,14 @@ class Comm:
     @staticmethod
     def unique_id():
         buf = C.create_string_buffer(128)
-        _lib.check(_lib.load().nnf_comm_unique_id(buf), "nnf_comm_unique_id")
+        _lib.call(_lib.load(), "nnf_comm_unique_id", buf)
         return buf.raw
 
     def __init__(self, engine, nranks, rank, unique_id):
         self.engine = engine
         h = C.c_void_p()
-        _lib.check(engine.lib.nnf_comm_create(C.byref(h), engine.ctx, int(nranks), int(rank),
-                                              C.create_string_buffer(unique_id, 128)), "nnf_comm_create")
+        _lib.call(engine.lib, "nnf_comm_create", C.byref(h), engine.ctx, int(nranks), int(rank),
+                  C.create_string_buffer(unique_id, 128))
         self.h = h
 
     def size(self):
@@ -927,8 +919,8 @@ class Comm:
     def allreduce_(self, t):
         if not t.is_cuda or not t.is_contiguous() or t.dtype not in (torch.float32, torch.float64):
             raise EngineError("Comm.allreduce_: contiguous float32 / float64 device tensor expected")
-        fn = self.engine.lib.nnf_allreduce_f32 if t.dtype == torch.float32 else self.engine.lib.nnf_allreduce_f64
-        _lib.check(fn(self.h, _ptr(t), t.numel(), self.engine._stream()), "nnf_allreduce")
+        _lib.call(self.engine.lib, "nnf_allreduce_f32" if t.dtype == torch.float32 else "nnf_allreduce_f64", self.h, _ptr(t),
+                  t.numel(), self.engine._stream())
         return t
 
     def close(self):

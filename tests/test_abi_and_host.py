@@ -32,9 +32,63 @@ def test_library_exports_every_declared_symbol(built_lib):
         assert hasattr(lib, n), f"{n} declared in include/nnfac_hip.h but not exported"
 
 
+def _header():
+    txt = open(os.path.join(ROOT, "include", "nnfac_hip.h")).read()
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
+C_KINDS = ("int64_t", "size_t", "unsigned", "double", "float", "int")
+
+
+def _c_kind(decl):
+    """A parameter or return type of the header as one of {pointer, int, int64_t, unsigned, float, double, size_t}."""
+    if "*" in decl:
+        return "pointer"
+    words = [w for w in re.findall(r"\w+", decl) if w != "const"]
+    kinds = [w for w in words if w in C_KINDS]
+    assert len(kinds) == 1 and words.index(kinds[0]) == 0, f"unparsed type in include/nnfac_hip.h: {decl!r}"
+    return kinds[0]
+
+
+def _ctypes_kind(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
+        return "pointer"
+    return {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_uint: "unsigned", ctypes.c_float: "float",
+            ctypes.c_double: "double", ctypes.c_size_t: "size_t"}[t]
+
+
+def _header_prototypes():
+    """name -> (kind of the return type, [kind of each parameter]) for every prototype of include/nnfac_hip.h."""
+    protos = {}
+    for ret, name, params in re.findall(r"^([A-Za-z_][\w \t\*]*?)\b(nnf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header(), flags=re.M):
+        params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        assert name not in protos, name
+        protos[name] = (_c_kind(ret), [_c_kind(p) for p in params])
+    return protos
+
+
+def _header_defines():
+    return {k: int(v.rstrip("u")) for k, v in re.findall(r"^#define\s+(NNF_\w+)\s+\(?(-?\d+u?)\)?\s*$", _header(), flags=re.M)}
+
+
 def test_binding_table_matches_header(built_lib):
-    from nn_fac_amd import _lib
+    """_lib.SIGNATURES against include/nnfac_hip.h, entry by entry: the same names, and for each the same kind of return value
+    and of every parameter (any `*` is a pointer; an `int` bound as int64_t, or the reverse, would pass every other CPU test
+    and corrupt a call).  The constants engine.py copies from the header equal their #defines."""
+    from nn_fac_amd import _lib, engine
     assert sorted(_lib.SIGNATURES) == _declared_symbols()
+    protos = _header_prototypes()
+    assert sorted(protos) == _declared_symbols(), "a prototype of include/nnfac_hip.h was not parsed"
+    for name, (res, args) in _lib.SIGNATURES.items():
+        assert (_ctypes_kind(res), [_ctypes_kind(a) for a in args]) == protos[name], name
+    d = _header_defines()
+    assert engine.MAX_RANK == d["NNF_MAX_RANK"]
+    assert (engine.HALS_SPARSITY, engine.HALS_NORMALIZE, engine.HALS_NONZERO) == (
+        d["NNF_HALS_SPARSITY"], d["NNF_HALS_NORMALIZE"], d["NNF_HALS_NONZERO"])
+    assert (engine.ST_EPS, engine.ST_CNT, engine.ST_EPS0, engine.ST_ERR, engine.ST_WORDS) == (
+        d["NNF_HALS_ST_EPS"], d["NNF_HALS_ST_CNT"], d["NNF_HALS_ST_EPS0"], d["NNF_HALS_ST_ERR"], d["NNF_HALS_ST_WORDS"])
+    probes = {k[len("NNF_PROBE_"):].lower(): v for k, v in d.items() if k.startswith("NNF_PROBE_") and k != "NNF_PROBE_COUNT"}
+    assert engine.Engine.PROBE_KERNELS == probes and d["NNF_PROBE_COUNT"] == len(probes)
     lib = _lib.load()
     assert lib.nnf_version() >= 100
     assert lib.nnf_status_string(0) == b"ok"
@@ -234,3 +288,20 @@ def test_engine_double_keeps_the_engine_signatures():
     missing = sorted(set(methods) - set(CONTRACT))
     assert not missing, f"OracleEngine methods without a GPU contract case: {missing}"
     assert all(CONTRACT[m] for m in methods)
+
+
+def test_every_engine_method_has_its_refusals_tested():
+    """tests/test_gpu_engine_args.py spoils one operand at a time of every public Engine method that takes a tensor: a method
+    added to Engine gets rows there (or a place in NO_TENSOR), a row is (operands, call, ways not refused[, more of them
+    without the optional outputs]), and no row is left behind for a method that is gone."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from nn_fac_amd.engine import Engine
+    from test_gpu_engine_args import NO_TENSOR, ROWS
+    public = {n for n, v in vars(Engine).items() if not n.startswith("_") and callable(getattr(Engine, n))}
+    assert not set(ROWS) & NO_TENSOR
+    assert set(ROWS) | NO_TENSOR == public, sorted(public ^ (set(ROWS) | NO_TENSOR))
+    for name, rows in ROWS.items():
+        assert rows and all(len(row) in (3, 4) and callable(row[0]) and callable(row[1]) for row in rows), name
+        known = {"d", "c", "n"} | {s + str(k) for s in "+-" for k in range(8)}
+        assert all(set(ways) <= known for row in rows for free in row[2:] for ways in free.values()), name
