@@ -367,7 +367,11 @@ int nnf_simplex_proj_kl_f32(nnf_ctx* ctx, const float* H, int64_t ldh, int r, in
 /* Ranks beyond the fused kernels (r > NNF_MAX_RANK, every beta): the element-wise operands of mu_betadivmin (mu.py:84-97),
  *   R1 = X .* (UV)^(beta-2)   and, unless beta == 1,   R2 = (UV)^(beta-1)        (both m x n, row stride ldr, caller-owned),
  * written in one pass over X; the two contractions are then plain nnf_xht_f32 / nnf_xty_f32 calls on R1 / R2 and
- * nnf_mu_apply_f32 finishes (nn_fac_amd/engine.py composes them when the fused entry points return NNF_ERR_UNSUPPORTED). */
+ * nnf_mu_apply_f32 finishes (nn_fac_amd/engine.py composes them when the fused entry points return NNF_ERR_UNSUPPORTED).
+ * Callable at every rank r >= 1.  Above NNF_MAX_RANK the model U V builds up over rank chunks of NNF_MAX_RANK inside R1 (no other
+ * scratch): R1 is written before it is read, so what it held before the call is ignored.  Where X is 0, R1 is +0.  beta == 1
+ * leaves R2 untouched (it may be NULL).  NNF_ERR_ARG, nothing launched and R1 / R2 untouched: ldr < n, R1 == NULL, R2 == NULL with
+ * beta != 1, beta negative or NaN. */
 int nnf_mu_ratio_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
                      const float* V, int64_t ldv, int r, double beta, float* R1, float* R2, int64_t ldr, void* stream);
 

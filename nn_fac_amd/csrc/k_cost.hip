@@ -478,8 +478,10 @@ extern "C" int nnf_betadiv_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t 
     return launch_betadiv(ctx, q, beta, (hipStream_t)stream);
 }
 
-// Element-wise operands of mu_betadivmin (mu.py:84-97) for ranks beyond the fused kernels (64 < r <= 128):
+// Element-wise operands of mu_betadivmin (mu.py:84-97) at any rank r >= 1 (the drivers take this route above NNF_MAX_RANK, where
+// there is no fused kernel):
 //   R1 = X .* (U V)^(beta-2)   and, unless beta == 1,   R2 = (U V)^(beta-1),   both m x n with row stride ldr.
+// Above NNF_MAX_RANK R1 is also the model buffer of launch_cost_any_rank: written before it is read, whatever it held.
 extern "C" int nnf_mu_ratio_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
                                 const float* V, int64_t ldv, int r, double beta, float* R1, float* R2, int64_t ldr,
                                 void* stream) {

@@ -1,6 +1,7 @@
 """Every row of test_gpu_launch_plans.plan_cases (MU, X H^T, W^T X, Gram, cost; cp3_partial_cost is a left MU update at a fixed
 shape and has its plan checked on the device only) and every row of test_gpu_tensor_plans.tensor_cases (MTTKRP by segments and by
-rows, the two dimension-tree contractions, the CP cost) against the library's own plan arithmetic, at 256 and at 304 compute units.  No GPU: the launchers take their plans from HIP-free
+rows, the two dimension-tree contractions, the CP cost) and every pass of test_gpu_mu_above_128.ratio_cases (the ratio pass of the
+MU route above rank 128) against the library's own plan arithmetic, at 256 and at 304 compute units.  No GPU: the launchers take their plans from HIP-free
 headers (nn_fac_amd/csrc/k_stream_plan.h, k_mu_plan.h), and tools/nnf_plan.cpp, a plain host program over the same headers,
 prints the plan of a case as the library reports it under NNF_PLAN_DEBUG.  This is what keeps the tables' shapes on the side of
 the thresholds they name on a machine that cannot ask the library (test_plan_table and test_tensor_plan_table do, on the device)."""
@@ -14,6 +15,7 @@ import tempfile
 
 import pytest
 
+import test_gpu_mu_above_128 as above
 import test_gpu_tensor_plans as tensor
 from test_gpu_launch_plans import REQUIRED, REQUIRED_BIG, ROOT, _cdiv, note_plan, parse_plans, plan_cases
 
@@ -281,3 +283,42 @@ def test_gram_and_cost_cases_take_the_plans_they_name(C):
     for key in (("gram", "form"), ("gram", "bound"), ("cost", "NN"), ("cost", "vdb"), ("cost", "VEC")):
         assert REQUIRED[key] <= seen[key], (key, REQUIRED[key] - seen[key])
     assert seen[("cost", "csplit")] == {"1", ">1"}
+
+
+def ratio_lines(C, case, beta):
+    """The passes of one nnf_mu_ratio_f32 call of test_gpu_mu_above_128.ratio_cases as launch_cost_any_rank makes them: rank
+    chunks of 128, all but the last writing the model (prod), all but the first reading it back from R1 (pin, at R1's pitch)."""
+    return ["cost %d %d %d %d %d %r %d align=%d op=%s pin=%d ldr=%d" % (
+        C, case.m, case.n, p["r"], case.x_pitch or case.n, float(beta), WS_DEFAULT, case.x_off, p["op"], p["pin"], case.ldr or case.n)
+        for p in above.expected_passes(case, beta)]
+
+
+@pytest.mark.parametrize("C", CUS)
+def test_ratio_cases_take_the_plans_they_name(C):
+    """Every pass of every (case, beta) of test_gpu_mu_above_128.ratio_cases -- the rank edges, n = 577 and n = 2200, the layouts --
+    takes the load width its layout gives and, in its last pass, the column splits, load group and V buffers the case names; the
+    list reaches REQUIRED_RATIO and REQUIRED_COMBOS; the last of the 8 column splits at n = 2200 is empty."""
+    calls = [(name, beta) for name, case in above.RATIO_CASES.items() for beta in case.betas]
+    lines = [ratio_lines(C, above.RATIO_CASES[name], beta) for name, beta in calls]
+    answers = iter(ask([l for ls in lines for l in ls]))
+    bad, seen, combos = [], collections.defaultdict(set), set()
+    for (name, beta), ls in zip(calls, lines):
+        plans = [next(answers) for _ in ls]
+        assert all("status" not in p for p in plans), (name, beta, plans)
+        above.check_passes(name, beta, plans, bad, seen, combos)
+        case = above.RATIO_CASES[name]
+        for p in plans:
+            assert 1 <= p["csplit"] <= max(1, _cdiv(case.n, 64) // 4) and p["KS"] == _cdiv(p["r"], 4), (name, p)
+            assert p["partial_bytes"] == 8 * p["grid"] * p["csplit"] and p["vf_bytes"] == 1024 * _cdiv(case.n, 64) * p["KS"], (name, p)
+            assert p["shm"] == 2048 * p["KS"] + (2 if p["vdb"] else 1) * 1024 * p["KS"] + 64 <= 160 * 1024, (name, p)
+            if case.n == 2200:      # 35 column blocks in splits of cdiv(35, 8) = 5: seven hold them all
+                per = _cdiv(_cdiv(case.n, 64), p["csplit"])
+                assert p["csplit"] == 8 and per * (p["csplit"] - 1) >= _cdiv(case.n, 64), (name, p)
+            elif p["csplit"] > 1:   # no empty split anywhere else
+                assert _cdiv(_cdiv(case.n, 64), p["csplit"]) * (p["csplit"] - 1) < _cdiv(case.n, 64), (name, p)
+    assert not bad, "\n".join(map(str, bad))
+    above.check_reach(seen, combos)
+    named = {nm for nm, c in above.RATIO_CASES.items() if c.expect}
+    assert {c.r for nm, c in above.RATIO_CASES.items() if nm in named and c.n == 68} == {1, 4, 5, 9, 50, 64, 100, 120, 128, 129, 131, 200, 256,
+                                                                                       257, 385}
+    assert {c.n for nm, c in above.RATIO_CASES.items() if nm in named} == {68, 577, 2200}

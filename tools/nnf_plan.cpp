@@ -27,12 +27,17 @@
 //                                     "[nnf plan] xty_gram rides= main_grid= rider_grid= rider_offset= grid= main_bytes=
 //                                     rider_bytes= rider_ws_off= ws_bytes=", then gram_nsplit= gram_kps= gram_bytes= of the Gram's
 //                                     own plan; rides=0: the two run as calls of their own
-//                          cost <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [align=] [op=] [kr=] [pin=] [csplit=]
-//                                     op: ratio_kl | ratio_gen | prod (default: the cost of that beta); kr: the Khatri-Rao inner
+//                          cost <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [align=] [op=] [kr=] [pin=] [ldr=] [ralign=]
+//                                     [csplit=]
+//                                     op: ratio_kl | ratio_gen | prod (default: the cost of that beta; prod: a pass that only
+//                                     writes the model, every rank pass but the last of a rank above 128); kr: the Khatri-Rao inner
 //                                     length of the CP cost (T as an (I J) x K matrix: m = I J, n = K, kr = J); pin=1: a later
-//                                     rank pass of a rank above 128 (the model buffer aligned, as the library's own is; the CP
-//                                     cost of rank R is asked for its last pass: pin=1, r = R - 128 ((R - 1) / 128)); csplit:
-//                                     NNF_COST_CSPLIT; adds KS= shm= partial_bytes= vf_bytes=
+//                                     rank pass of a rank above 128, which reads the model back (the CP cost of rank R is asked
+//                                     for its last pass: pin=1, r = R - 128 ((R - 1) / 128)); ldr, ralign: the pitch of the model
+//                                     buffer and its offset from a 16-byte boundary, in floats (default: aligned, as the
+//                                     library's own buffer is; the first output of nnf_mu_ratio_f32 is the caller's) -- X and the
+//                                     model are loaded at one width; csplit: NNF_COST_CSPLIT; adds KS= shm= partial_bytes=
+//                                     vf_bytes=
 //                        The HALS sweep plan (k_hals_plan.h) reads key=value fields only:
 //                          hals <CUs> mode= r= ncols= nsweeps= [sweep0=] [flags=] [ldm=] [ldv=] [ldvs=] [gram2=] [own_start=]
 //                               [snapshots=] [force=] [pc_...=]     the fields of hals_shape: mode 0 a solve, 1 blind sweeps; flags
@@ -263,13 +268,15 @@ int main(int argc, char** argv) {
         } else if (strcmp(name, "cost") == 0) {
             const char* op = cost_op(rest, beta);
             const bool pin = key_of(rest, "pin", 0) != 0;
-            if (!op || !(beta >= 0.0)) {
+            // (launch_cost: a pass that reads the model back loads X and the model at one width)
+            const bool cvec = vec && (!pin || (key_of(rest, "ralign", 0) % 4 == 0 && key_of(rest, "ldr", 0) % 4 == 0));
+            if (!op || !(beta >= 0.0) || (pin && key_of(rest, "ldr", n) < n)) {
                 status = NNF_ERR_ARG;
             } else if (nnf_cost_offsets_ok(ld, n)) {
                 const nnf_cost_plan p = nnf_plan_cost((int)C, m, n, (int)r, key_of(rest, "kr", 0) > 0, (int)key_of(rest, "csplit", 0), pin,
                                                       strcmp(op, "prod") == 0, cur.remaining());
                 snprintf(more, sizeof more, " KS=%d shm=%zu partial_bytes=%zu vf_bytes=%zu", p.KS, p.shm, p.partial_bytes, p.vf_bytes);
-                if ((status = p.status) == NNF_OK) nnf_report_cost(stdout, m, n, (int)r, op, vec, pin, key_of(rest, "kr", 0), p, more);
+                if ((status = p.status) == NNF_OK) nnf_report_cost(stdout, m, n, (int)r, op, cvec, pin, key_of(rest, "kr", 0), p, more);
             }
         } else if (strcmp(name, "xty") == 0) {
             const nnf_rank_tiles t = nnf_xty_tiles((int)r, vec);
