@@ -10,7 +10,7 @@
 // Every sum has a fixed order (two calls are bitwise equal).  A segment table the kernels cannot trust (negative, decreasing,
 // beyond `total_cols`, or a group longer than the caller declared) makes the group a no-op: nothing of it is read or written
 // (the solve says so in its status block, NNF_HALS_ST_ERR = 5).
-#include "nnf_internal.h"
+#include "k_hals_common.h"   // the stopping rule and the status block of a solve
 
 #define GRP_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -44,9 +44,7 @@ __global__ __launch_bounds__(128) void nnf_hals_group_kernel(const float* __rest
     double* st = status + (size_t)g * NNF_HALS_ST_WORDS;
     int64_t lo, hi;
     if (!grp_range(off, g, total, maxlen, lo, hi)) {
-        if (tid == 0) {
-            st[NNF_HALS_ST_EPS] = 1.0; st[NNF_HALS_ST_CNT] = 1.0; st[NNF_HALS_ST_EPS0] = 0.0; st[NNF_HALS_ST_ERR] = 5.0;
-        }
+        if (tid == 0) hals_status_defaults(st, 5.0);
         return;
     }
     const float* Gg = UtU + (int64_t)g * gstride;
@@ -101,24 +99,19 @@ __global__ __launch_bounds__(128) void nnf_hals_group_kernel(const float* __rest
             if (!resident && active)
                 for (int k = 0; k < r; ++k) V[(int64_t)k * ldv + col] = vl[k * 128 + tid];
         }
-        done = s;
         // the group's sum of squared steps: lanes (fixed DPP tree), then the two waves in index order; every thread gets it
         nd = nnf_wave_sum_f64(nd);
         if ((tid & 63) == 0) red[tid >> 6] = nd;
         __syncthreads();
         const double tot = red[0] + red[1];
         __syncthreads();
-        if (s == 1) eps0 = tot;
-        eps = tot;
-        if (!(eps >= delta * eps0)) break;
+        if (!hals_note_sum(tot, s, 0, delta, eps0, eps, done)) break;
     }
     if (resident && lo + tid < hi)
         for (int k = 0; k < r; ++k) V[(int64_t)k * ldv + lo + tid] = vl[k * 128 + tid];
-    if (tid == 0) {
-        st[NNF_HALS_ST_EPS] = (max_sweeps >= 1) ? eps : 1.0;
-        st[NNF_HALS_ST_CNT] = (max_sweeps >= 1) ? (double)(done + 1) : 1.0;
-        st[NNF_HALS_ST_EPS0] = (max_sweeps >= 1) ? eps0 : 0.0;
-        st[NNF_HALS_ST_ERR] = 0.0;
+    if (tid == 0) {   // (no prep launch: the defaults first, then the three words of a solve that ran over them)
+        hals_status_defaults(st);
+        hals_status_finish(st, max_sweeps >= 1, 0, done, eps, eps0, false);
     }
 }
 

@@ -56,12 +56,7 @@ __global__ void nnf_hals_prep_kernel(const float* __restrict__ UtU, int64_t ldg,
     }
     if (threadIdx.x == 0) {
         *counter = 0u;
-        if (status) {
-            status[NNF_HALS_ST_EPS] = 1.0;
-            status[NNF_HALS_ST_CNT] = 1.0;
-            status[NNF_HALS_ST_EPS0] = 0.0;
-            status[NNF_HALS_ST_ERR] = 0.0;
-        }
+        if (status) hals_status_defaults(status);
     }
 }
 
@@ -202,7 +197,7 @@ __global__ __launch_bounds__(128) void nnf_hals_generic_kernel(const float* __re
             }
         }
         if (!ok) break;
-        done = s;
+        done = s;   // (mode 1, and a time-out below: hals_note_sum is not reached there)
         const double bs = nnf_block_sum_f64(nd, red);
         if (MODE == 1) {
             if (threadIdx.x == 0) sweep_partials[(size_t)(s - 1) * nblocks + blockIdx.x] = bs;
@@ -214,21 +209,14 @@ __global__ __launch_bounds__(128) void nnf_hals_generic_kernel(const float* __re
             double mine[1] = {bs}, tot[1];
             ok = grid_exchange<1>(sy, ++epoch, nblocks, mine, tot, red, &lds_flag);
             if (!ok) break;
-            if (s == 1 && sweep0 == 0) eps0 = tot[0];
-            eps = tot[0];
-            if (!(eps >= delta * eps0)) break;
+            if (!hals_note_sum(tot[0], s, sweep0, delta, eps0, eps, done)) break;
         }
     }
     if (!GCOL && active)
         for (int k = q; k < r; k += LPC) V[(int64_t)k * ldv + col0] = mycol[k * CW];
     if (blockIdx.x == 0 && threadIdx.x == 0 && status) {
-        if (MODE == 0 && max_sweeps >= 1) {
-            status[NNF_HALS_ST_EPS] = eps;
-            status[NNF_HALS_ST_CNT] = (double)(sweep0 + done + 1);
-            status[NNF_HALS_ST_EPS0] = eps0;
-        }
-        if (!ok) status[NNF_HALS_ST_ERR] = 1.0;
-        else if (err) status[NNF_HALS_ST_ERR] = (double)err;
+        hals_status_finish(status, MODE == 0 && max_sweeps >= 1, sweep0, done, eps, eps0, !ok);
+        if (ok && err) status[NNF_HALS_ST_ERR] = (double)err;
     }
 }
 
@@ -365,8 +353,8 @@ static int hals_entry(nnf_ctx* ctx, hals_request q, hipStream_t st) {
     if (p.copy && native && copy_start_values() != NNF_OK) return NNF_ERR_LAUNCH;
     if (!sweeps) return NNF_OK;
 
-    ctx->hals_epoch = (ctx->hals_epoch + 1u) & 0x3fffffu;   // tag = epoch*1024 + sweep stays below 2^32
-    if (ctx->hals_epoch == 0u) {   // wrapped (2^22 solves): clear the region so that tags of the previous round cannot match
+    ctx->hals_epoch = (ctx->hals_epoch + 1u) & HALS_EPOCH_MASK;   // hals_tag() stays below 2^32
+    if (ctx->hals_epoch == 0u) {   // wrapped: clear the region so that tags of the previous round cannot match
         if (hipMemsetAsync(ctx->xch, 0, ctx->xch_bytes, st) != hipSuccess) return NNF_ERR_LAUNCH;
         ctx->hals_epoch = 1u;
     }
@@ -475,7 +463,7 @@ __global__ __launch_bounds__(256) void nnf_hals_stop_restore_kernel(const double
         int stop = -1;
         const double eps0 = sums[0];
         for (int s = 0; s < nsweeps; ++s)
-            if (!(sums[s] >= delta * eps0) || s + 1 >= budget) { stop = s; break; }
+            if (!hals_goes_on(sums[s], delta, eps0) || s + 1 >= budget) { stop = s; break; }
         s_stop = stop;
         if (blockIdx.x == 0) {
             status[NNF_HALS_ST_EPS0] = eps0;

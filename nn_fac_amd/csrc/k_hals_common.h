@@ -85,15 +85,42 @@ __device__ __forceinline__ bool grid_exchange(const hals_sync& sy, unsigned epoc
 
 // Fast path, non-blocking form of the exchange (cdna_hip_programming.md Guideline 16, form R2: the data IS the flag).
 // A workgroup's fp64 partial of sweep s travels as two 8-byte granules {tag, lo32} {tag, hi32}, each ONE write-through
-// (sc1) store: fire and forget, no drain, no counter.  tag = epoch*1024 + s with a per-call epoch from the context, so
+// (sc1) store: fire and forget, no drain, no counter.  tag = epoch * HALS_TAG_STRIDE + s with a per-call epoch from the context, so
 // words left behind by earlier solves never match (the workspace is zeroed once at context creation).
 // collect: every thread re-reads its share of the granules (sc1 loads) until both tags match (bounded), then all
 // workgroups sum all partials in index order -> the same double everywhere, bit for bit.
-__device__ __forceinline__ void hals_publish(const hals_sync& sy, int s, int nblocks, double mine) {
-    if (threadIdx.x == 0) {
-        const unsigned long long bits = __builtin_bit_cast(unsigned long long, mine);
-        const unsigned long long tag = (unsigned long long)(sy.epoch * 1024u + (unsigned)s) << 32;
-        unsigned long long* g = reinterpret_cast<unsigned long long*>(sy.sslots) + ((size_t)s * nblocks + blockIdx.x) * 2;
+// The format, stated once: the words of workgroup b for sweep s are hals_row(sy, s, nblocks)[2 b], [2 b + 1], each
+// {hals_tag(sy, s) : 32 | half of the double : 32}.
+constexpr unsigned HALS_TAG_STRIDE = 1024u;                           // tags per epoch: sweep rows 0 .. max_sweeps + 1 of one launch
+constexpr unsigned HALS_EPOCH_MASK = 0xffffffffu / HALS_TAG_STRIDE;   // largest epoch: epoch * stride + s stays below 2^32
+static_assert(NNF_HALS_MAX_SWEEPS + 2 <= HALS_TAG_STRIDE, "every sweep row of a launch has a tag of its own");
+static_assert((HALS_EPOCH_MASK & (HALS_EPOCH_MASK + 1u)) == 0u, "the host wraps the epoch with this mask");
+typedef unsigned long long hals_word;
+__device__ __forceinline__ unsigned hals_tag(const hals_sync& sy, int s) { return sy.epoch * HALS_TAG_STRIDE + (unsigned)s; }
+__device__ __forceinline__ const hals_word* hals_row(const hals_sync& sy, int s, int nblocks) {
+    return reinterpret_cast<const hals_word*>(sy.sslots) + (size_t)s * nblocks * 2;
+}
+__device__ __forceinline__ double hals_granule_value(hals_word g0, hals_word g1) {
+    return __builtin_bit_cast(double, (g1 << 32) | (g0 & 0xffffffffull));
+}
+// Re-read workgroup b's pair of `row` until both halves carry `tag` (bounded); g0 / g1 come in holding what the caller has
+// already (0: nothing).  false: time-out.
+__device__ __forceinline__ bool hals_granule_wait(const hals_word* row, int b, unsigned tag, hals_word& g0, hals_word& g1) {
+    unsigned spins = 0;
+    while (!((unsigned)(g0 >> 32) == tag && (unsigned)(g1 >> 32) == tag)) {
+        if (spins > 0) __builtin_amdgcn_s_sleep(1);
+        if (++spins > HALS_SPIN_LIMIT) return false;
+        g0 = __hip_atomic_load(row + 2 * (size_t)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        g1 = __hip_atomic_load(row + 2 * (size_t)b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return true;
+}
+// `me`: the workgroup's publishing lane
+__device__ __forceinline__ void hals_publish(const hals_sync& sy, int s, int nblocks, double mine, bool me = threadIdx.x == 0) {
+    if (me) {
+        const hals_word bits = __builtin_bit_cast(hals_word, mine);
+        const hals_word tag = (hals_word)hals_tag(sy, s) << 32;
+        hals_word* g = reinterpret_cast<hals_word*>(sy.sslots) + ((size_t)s * nblocks + blockIdx.x) * 2;
         __hip_atomic_store(g, tag | (bits & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(g + 1, tag | (bits >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -104,11 +131,11 @@ __device__ __forceinline__ void hals_publish(const hals_sync& sy, int s, int nbl
 // partials in the same order (thread-strided by index, DPP wave sum, waves in index order): same double everywhere.
 constexpr int HALS_PF = 2;   // granule pairs per thread that can be in flight (covers nblocks <= 2 * blockDim.x)
 struct hals_prefetch {
-    unsigned long long g0[HALS_PF], g1[HALS_PF];
+    hals_word g0[HALS_PF], g1[HALS_PF];
     int s;   // sweep the granules belong to (0: nothing issued)
 };
 __device__ __forceinline__ void hals_collect_issue(const hals_sync& sy, int s, int nblocks, hals_prefetch& pf) {
-    const unsigned long long* base = reinterpret_cast<const unsigned long long*>(sy.sslots) + (size_t)s * nblocks * 2;
+    const hals_word* base = hals_row(sy, s, nblocks);
     pf.s = s;
 #pragma unroll
     for (int i = 0; i < HALS_PF; ++i) {
@@ -124,25 +151,21 @@ __device__ __forceinline__ bool hals_collect(const hals_sync& sy, int s, int nbl
                                              unsigned* lds_flag, const hals_prefetch* pf = nullptr) {
     if (threadIdx.x == 0) *lds_flag = 1u;
     __syncthreads();
-    const unsigned tag = sy.epoch * 1024u + (unsigned)s;
-    const unsigned long long* base = reinterpret_cast<const unsigned long long*>(sy.sslots) + (size_t)s * nblocks * 2;
+    const unsigned tag = hals_tag(sy, s);
+    const hals_word* base = hals_row(sy, s, nblocks);
     double v = 0.0;
     int i = 0;
     for (int b = threadIdx.x; b < nblocks; b += blockDim.x, ++i) {
-        unsigned long long g0 = 0ull, g1 = 0ull;
-        if (pf != nullptr && pf->s == s) {   // prefetched copy (tag 0 never matches: epochs start at 1)
+        hals_word g0 = 0ull, g1 = 0ull;
+        // prefetched copy (tag 0 never matches: epochs start at 1); taken here, in hals_collect1 and in hals_collect_wave, not by a
+        // shared helper: through one the quad kernel's s_waitcnt count changes (CH = 28: 1076 -> 1074)
+        if (pf != nullptr && pf->s == s) {
 #pragma unroll
             for (int u = 0; u < HALS_PF; ++u)
                 if (u == i) { g0 = pf->g0[u]; g1 = pf->g1[u]; }
         }
-        unsigned spins = 0;
-        while (!((unsigned)(g0 >> 32) == tag && (unsigned)(g1 >> 32) == tag)) {
-            if (spins > 0) __builtin_amdgcn_s_sleep(1);
-            if (++spins > HALS_SPIN_LIMIT) { *lds_flag = 0u; break; }
-            g0 = __hip_atomic_load(base + 2 * (size_t)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g1 = __hip_atomic_load(base + 2 * (size_t)b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        v += __builtin_bit_cast(double, (g1 << 32) | (g0 & 0xffffffffull));
+        if (!hals_granule_wait(base, b, tag, g0, g1)) *lds_flag = 0u;
+        v += hals_granule_value(g0, g1);
     }
     v = nnf_wave_sum_f64(v);
     const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
@@ -177,7 +200,7 @@ struct hals_mid_none {
     __device__ __forceinline__ void operator()() const {}
 };
 struct hals_mid_issue {
-    unsigned long long a0, a1;
+    unsigned long long a0, a1;   // addresses of the thread's two granule pairs
     hals_prefetch& pf;
     __device__ __forceinline__ void operator()() const {
         static_assert(HALS_PF == 2, "two granule pairs per thread");
@@ -194,36 +217,27 @@ __device__ __forceinline__ void hals_mid_wait(hals_prefetch& pf) {
 // Barrier-lean forms for the persistent sweep loop: `red` is a per-sweep-parity slot array ((blockDim/64) doubles each),
 // so a slot is rewritten only two sweeps later, with a barrier in between -- no trailing barrier is needed, and the
 // time-out flag is armed once before the loop instead of per call.  One __syncthreads each.
-__device__ __forceinline__ double hals_block_sum1(double v, double* red_p) {
-    v = nnf_wave_sum_f64(v);
-    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    if ((threadIdx.x & 63) == 0) red_p[w] = v;
-    __syncthreads();
-    double t = red_p[0];
-    for (int k = 1; k < nw; ++k) t += red_p[k];
-    return t;   // every thread
-}
 __device__ __forceinline__ bool hals_collect1(const hals_sync& sy, int s, int nblocks, double& total, double* red_p,
                                               unsigned* lds_flag, const hals_prefetch& pf) {
-    const unsigned tag = sy.epoch * 1024u + (unsigned)s;
-    const unsigned long long* base = reinterpret_cast<const unsigned long long*>(sy.sslots) + (size_t)s * nblocks * 2;
+    const unsigned tag = hals_tag(sy, s);
+    const hals_word* base = hals_row(sy, s, nblocks);
     double v = 0.0;
     int i = 0;
     for (int b = threadIdx.x; b < nblocks; b += blockDim.x, ++i) {
-        unsigned long long g0 = 0ull, g1 = 0ull;
+        hals_word g0 = 0ull, g1 = 0ull;
         if (pf.s == s) {
 #pragma unroll
             for (int u = 0; u < HALS_PF; ++u)
                 if (u == i) { g0 = pf.g0[u]; g1 = pf.g1[u]; }
         }
-        unsigned spins = 0;
+        unsigned spins = 0;   // (hals_granule_wait written out: through it the matrix-core kernel gains 40 s_waitcnt per instantiation)
         while (!((unsigned)(g0 >> 32) == tag && (unsigned)(g1 >> 32) == tag)) {
             if (spins > 0) __builtin_amdgcn_s_sleep(1);
             if (++spins > HALS_SPIN_LIMIT) { *lds_flag = 0u; break; }
             g0 = __hip_atomic_load(base + 2 * (size_t)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             g1 = __hip_atomic_load(base + 2 * (size_t)b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        v += __builtin_bit_cast(double, (g1 << 32) | (g0 & 0xffffffffull));
+        v += hals_granule_value(g0, g1);
     }
     v = nnf_wave_sum_f64(v);
     const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
@@ -239,26 +253,20 @@ __device__ __forceinline__ bool hals_collect1(const hals_sync& sy, int s, int nb
 // sum -- with no LDS and no barrier at all.  Returns false on a time-out (wave-uniform).
 __device__ __forceinline__ bool hals_collect_wave(const hals_sync& sy, int s, int nblocks, double& total,
                                                   const hals_prefetch* pf = nullptr) {
-    const unsigned tag = sy.epoch * 1024u + (unsigned)s;
-    const unsigned long long* base = reinterpret_cast<const unsigned long long*>(sy.sslots) + (size_t)s * nblocks * 2;
+    const unsigned tag = hals_tag(sy, s);
+    const hals_word* base = hals_row(sy, s, nblocks);
     double v = 0.0;
     bool late = false;
     int i = 0;
     for (int b = threadIdx.x; b < nblocks; b += 64, ++i) {
-        unsigned long long g0 = 0ull, g1 = 0ull;
+        hals_word g0 = 0ull, g1 = 0ull;
         if (pf != nullptr && pf->s == s) {
 #pragma unroll
             for (int u = 0; u < HALS_PF; ++u)
                 if (u == i) { g0 = pf->g0[u]; g1 = pf->g1[u]; }
         }
-        unsigned spins = 0;
-        while (!((unsigned)(g0 >> 32) == tag && (unsigned)(g1 >> 32) == tag)) {
-            if (spins > 0) __builtin_amdgcn_s_sleep(1);
-            if (++spins > HALS_SPIN_LIMIT) { late = true; break; }
-            g0 = __hip_atomic_load(base + 2 * (size_t)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            g1 = __hip_atomic_load(base + 2 * (size_t)b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        v += __builtin_bit_cast(double, (g1 << 32) | (g0 & 0xffffffffull));
+        if (!hals_granule_wait(base, b, tag, g0, g1)) late = true;
+        v += hals_granule_value(g0, g1);
     }
     total = nnf_wave_sum_f64(v);
     return __ballot(late) == 0ull;
@@ -276,11 +284,11 @@ __device__ __forceinline__ bool hals_sum_collect1(const hals_sync& sy, double nd
                                                   double* red_bs, double* red_tot, unsigned* lds_flag,
                                                   const hals_prefetch& pf) {
     static_assert(NT == 256 && HALS_PF == 2, "two granule pairs per thread cover nblocks <= 512");
-    const unsigned tag = sy.epoch * 1024u + (unsigned)c;
-    const unsigned long long* base = reinterpret_cast<const unsigned long long*>(sy.sslots) + (size_t)c * nblocks * 2;
+    const unsigned tag = hals_tag(sy, c);
+    const hals_word* base = hals_row(sy, c, nblocks);
     // fast path: both pairs arrived with the prefetch -- two compares per pair, ONE wave-uniform test, no exec-mask branches;
     // a granule that is not there yet sends the whole wave through the re-read loop (rare; bounded)
-    unsigned long long g0[HALS_PF], g1[HALS_PF];
+    hals_word g0[HALS_PF], g1[HALS_PF];
     bool want[HALS_PF], need = false;
 #pragma unroll
     for (int i = 0; i < HALS_PF; ++i) {
@@ -293,23 +301,15 @@ __device__ __forceinline__ bool hals_sum_collect1(const hals_sync& sy, double nd
 #pragma unroll 1
         for (int i = 0; i < HALS_PF; ++i) {
             const int b = (int)threadIdx.x + NT * i;
-            unsigned long long a0 = i == 0 ? g0[0] : g0[HALS_PF - 1], a1 = i == 0 ? g1[0] : g1[HALS_PF - 1];
-            if (b < nblocks) {
-                unsigned spins = 0;
-                while (!((unsigned)(a0 >> 32) == tag && (unsigned)(a1 >> 32) == tag)) {
-                    if (spins > 0) __builtin_amdgcn_s_sleep(1);
-                    if (++spins > HALS_SPIN_LIMIT) { *lds_flag = 0u; break; }
-                    a0 = __hip_atomic_load(base + 2 * (size_t)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    a1 = __hip_atomic_load(base + 2 * (size_t)b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
+            hals_word a0 = i == 0 ? g0[0] : g0[HALS_PF - 1], a1 = i == 0 ? g1[0] : g1[HALS_PF - 1];
+            if (b < nblocks && !hals_granule_wait(base, b, tag, a0, a1)) *lds_flag = 0u;
             if (i == 0) { g0[0] = a0; g1[0] = a1; } else { g0[HALS_PF - 1] = a0; g1[HALS_PF - 1] = a1; }
         }
     }
     double v = 0.0;
 #pragma unroll
     for (int i = 0; i < HALS_PF; ++i)
-        v += want[i] ? __builtin_bit_cast(double, (g1[i] << 32) | (g0[i] & 0xffffffffull)) : 0.0;
+        v += want[i] ? hals_granule_value(g0[i], g1[i]) : 0.0;
     v = nnf_wave_sum_f64(v);
     nd = nnf_wave_sum_f64(nd);
     constexpr int nw = NT / 64;
@@ -361,16 +361,45 @@ struct hals_args {
     int snap_first;          // mode 1: the first sweep (0-based, within this launch) that writes a snapshot
 };
 
+// The stopping rule of nnls.py:156: the first sweep of a solve sets eps0, and the loop goes on while eps >= delta * eps0
+// (false for a NaN on either side: a NaN sum ends the solve).
+__device__ __forceinline__ bool hals_goes_on(double eps, double delta, double eps0) { return eps >= delta * eps0; }
+// Note the global sum `tot` of sweep c (counted within this launch, which follows `sweep0` sweeps of earlier launches of the
+// same solve).  Returns the verdict: false = sweep c was the last one.
+__device__ __forceinline__ bool hals_note_sum(double tot, int c, int sweep0, double delta, double& eps0, double& eps, int& done) {
+    if (c == 1 && sweep0 == 0) eps0 = tot;
+    eps = tot;
+    done = c;
+    return hals_goes_on(eps, delta, eps0);
+}
 // Continuation of a solve longer than one launch can tag (NNF_HALS_MAX_SWEEPS): `status` holds the state the previous launch
 // left.  Returns false when that launch already ended the solve (stopping rule, error) -- the caller returns at once, V and
 // the status block stay as they are; else eps0 / eps are taken over.  Every workgroup reads the same words (written by the
 // previous launch, stream-ordered; rewritten by this one only after every workgroup has published its first sweep).
+// (The rule is written out here and in the lane and matrix-core kernels: through hals_goes_on they spill other scalar registers.)
 __device__ __forceinline__ bool hals_take_over(const double* status, int sweep0, double delta, double& eps0, double& eps) {
     const double pe = status[NNF_HALS_ST_EPS], pe0 = status[NNF_HALS_ST_EPS0];
     if ((int)status[NNF_HALS_ST_CNT] - 1 != sweep0 || !(pe >= delta * pe0) || status[NNF_HALS_ST_ERR] != 0.0) return false;
     eps0 = pe0;
     eps = pe;
     return true;
+}
+
+// The status block of a solve (NNF_HALS_ST_*): the defaults of one that runs no sweep, written in front of it, and the closing
+// write by one thread -- the three words of a solve that `ran` at least one sweep, and error 1 after a time-out.
+__device__ __forceinline__ void hals_status_defaults(double* st, double err = 0.0) {
+    st[NNF_HALS_ST_EPS] = 1.0;
+    st[NNF_HALS_ST_CNT] = 1.0;
+    st[NNF_HALS_ST_EPS0] = 0.0;
+    st[NNF_HALS_ST_ERR] = err;
+}
+__device__ __forceinline__ void hals_status_finish(double* st, bool ran, int sweep0, int done, double eps, double eps0, bool timed_out) {
+    if (ran) {
+        st[NNF_HALS_ST_EPS] = eps;
+        st[NNF_HALS_ST_CNT] = (double)(sweep0 + done + 1);
+        st[NNF_HALS_ST_EPS0] = eps0;
+    }
+    if (timed_out) st[NNF_HALS_ST_ERR] = 1.0;
 }
 
 // Workgroups per CU a persistent launch relies on, from the occupancy API's answer `nb`: one fewer from three up (the API can

@@ -344,9 +344,8 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
             } else if constexpr (SPEC) {
                 // granules of sweep s-1, consumed after this sweep: their loads go out in the middle of it (hals_mid_issue);
                 // nothing to collect (fixed-count mode, first sweep): row 0 of the region is read and ignored (pf.s = 0)
-                const bool want = a.mode == 0 && s >= 2;
-                const unsigned long long* row = reinterpret_cast<const unsigned long long*>(a.sy.sslots) +
-                                                (size_t)(want ? s - 1 : 0) * nblocks * 2;
+                const bool want = a.mode == 0 && s >= 2;   // (set up here and in k_hals_quad.hip, not by a shared builder: it moved the quad kernel's instruction count)
+                const hals_word* row = hals_row(a.sy, want ? s - 1 : 0, nblocks);
                 const int b0 = (int)threadIdx.x < nblocks ? (int)threadIdx.x : 0;
                 const int b1 = (int)threadIdx.x + 256 < nblocks ? (int)threadIdx.x + 256 : 0;
                 pf.s = want ? s - 1 : 0;
@@ -398,10 +397,10 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
             else if constexpr (RES) ok = hals_collect1(a.sy, c, nblocks, tot, red2[s & 1][1], &lds_flag, pf);
             else ok = hals_collect(a.sy, c, nblocks, tot, red, &lds_flag, &pf);
             if (!ok) break;
-            if (c == 1 && a.sweep0 == 0) eps0 = tot;
+            if (c == 1 && a.sweep0 == 0) eps0 = tot;   // (hals_note_sum written out: through it hipcc allocates the sweep's registers differently)
             eps = tot;
             done = c;
-            if (!(eps >= a.delta * eps0) && !HALS_DBG) { stopped = true; break; }   // nnls.py:156: sweep c was the last one
+            if (!(eps >= a.delta * eps0) && !HALS_DBG) { stopped = true; break; }   // nnls.py:156: sweep c was the last one (the rule written out: see hals_take_over)
         }
     }
     if constexpr (RES) {
@@ -420,20 +419,14 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
     } else if (SPEC && ok && !stopped && a.max_sweeps >= 1 && !HALS_DBG) {
         double tot;                             // ran to the sweep budget: the last sweep's sum is still due
         ok = hals_collect(a.sy, a.max_sweeps, nblocks, tot, red, &lds_flag);
-        if (ok) {
+        if (ok) {   // (hals_note_sum written out: through it the rank 32 and 64 kernels spill other scalar registers)
             if (a.max_sweeps == 1 && a.sweep0 == 0) eps0 = tot;
             eps = tot;
             done = a.max_sweeps;
         }
     }
-    if (a.mode == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
-        if (a.max_sweeps >= 1) {
-            a.status[NNF_HALS_ST_EPS] = eps;
-            a.status[NNF_HALS_ST_CNT] = (double)(a.sweep0 + done + 1);
-            a.status[NNF_HALS_ST_EPS0] = eps0;
-        }
-        if (!ok) a.status[NNF_HALS_ST_ERR] = 1.0;
-    }
+    if (a.mode == 0 && blockIdx.x == 0 && threadIdx.x == 0)
+        hals_status_finish(a.status, a.max_sweeps >= 1, a.sweep0, done, eps, eps0, !ok);
 }
 
 template <int RP>

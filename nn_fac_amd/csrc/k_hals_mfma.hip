@@ -486,10 +486,10 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
                 double tot;
                 ok = hals_collect1(a.sy, s - 1, nblocks, tot, red2[(s - 1) & 1][1], &lds_flag, pf);
                 if (ok) {
-                    if (s == 2 && a.sweep0 == 0) eps0 = tot;
+                    if (s == 2 && a.sweep0 == 0) eps0 = tot;   // (hals_note_sum written out: through it every instantiation spills other scalar registers)
                     eps = tot;
                 }
-                if (!ok || !(eps >= a.delta * eps0)) {   // nnls.py:156: sweep s-1 was the last one -> sweep s does not take place:
+                if (!ok || !(eps >= a.delta * eps0)) {   // nnls.py:156 (written out: see hals_take_over): sweep s-1 was the last one -> sweep s does not take place:
                     undo = true;                          // its head's rows of v are taken from the backup when V is stored
                     break;                                // (assigning them to v here makes hipcc keep two copies of everything)
                 }
@@ -525,10 +525,7 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
         if (a.mode == 0 && ok && done == s && pending) {   // ran to the sweep budget: the last sweep's sum is still due
             double tot;
             ok = hals_collect1(a.sy, s, nblocks, tot, red2[s & 1][1], &lds_flag, pf);
-            if (ok) {
-                if (s == 1 && a.sweep0 == 0) eps0 = tot;
-                eps = tot;
-            }
+            if (ok) (void)hals_note_sum(tot, s, a.sweep0, a.delta, eps0, eps, done);   // (no verdict: the budget is spent)
         }
         if (st_out != nullptr) {   // (the tiles are complete: the sweep ends with the MFMA -> reader distance)
 #pragma unroll
@@ -549,12 +546,8 @@ __global__ __launch_bounds__(256, 2) void nnf_hals_mfma_kernel(hals_args a) {
         return false;
     };
     if (!all_live || run(std::false_type{})) (void)run(std::true_type{});
-    if (a.mode == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
-        a.status[NNF_HALS_ST_EPS] = eps;
-        a.status[NNF_HALS_ST_CNT] = (double)(a.sweep0 + done + 1);
-        a.status[NNF_HALS_ST_EPS0] = eps0;
-        if (!ok) a.status[NNF_HALS_ST_ERR] = 1.0;
-    }
+    if (a.mode == 0 && blockIdx.x == 0 && threadIdx.x == 0)   // (max_sweeps >= 1: checked above)
+        hals_status_finish(a.status, true, a.sweep0, done, eps, eps0, !ok);
 }
 
 // Gram image + coupling table in the kernel's order (see above); g(row, k) = -UtU[row][k] / UtU[row][row], 0 outside r x r and

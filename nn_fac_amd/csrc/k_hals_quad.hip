@@ -59,12 +59,7 @@ __global__ void nnf_hals_prep_quad_kernel(const float* __restrict__ UtU, const f
     if (threadIdx.x == 0) dinvq[k] = di;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *counter = 0u;
-        if (status) {
-            status[NNF_HALS_ST_EPS] = 1.0;
-            status[NNF_HALS_ST_CNT] = 1.0;
-            status[NNF_HALS_ST_EPS0] = 0.0;
-            status[NNF_HALS_ST_ERR] = 0.0;
-        }
+        if (status) hals_status_defaults(status);
     }
 }
 
@@ -228,9 +223,8 @@ __global__ __launch_bounds__(64) void nnf_hals_quad_kernel(hals_args a) {
         if (all_live && HALS_LATE_ISSUE && nblocks <= 128) {
             // the granules of sweep s-1 (consumed after this sweep) are fetched late IN the sweep: issued before it, most
             // come back stale -- the other workgroups finish their sweep s-1 at the same moment (k_hals_common.h)
-            const bool want = a.mode == 0 && s >= 2;
-            const unsigned long long* row = reinterpret_cast<const unsigned long long*>(a.sy.sslots) +
-                                            (size_t)(want ? s - 1 : 0) * nblocks * 2;
+            const bool want = a.mode == 0 && s >= 2;   // (set up here, not by a shared builder: it moved this kernel's instruction count)
+            const hals_word* row = hals_row(a.sy, want ? s - 1 : 0, nblocks);
             const int b0 = lane < nblocks ? lane : 0, b1 = lane + 64 < nblocks ? lane + 64 : 0;
             pf.s = want ? s - 1 : 0;
             f = quad_sweep_all_live<CH>(v, b, own, laddr, hals_mid_issue{(unsigned long long)(row + 2 * (size_t)b0),
@@ -262,10 +256,10 @@ __global__ __launch_bounds__(64) void nnf_hals_quad_kernel(hals_args a) {
             double tot;
             ok = hals_collect_wave(a.sy, c, nblocks, tot, &pf);
             if (!ok) break;
-            if (c == 1 && a.sweep0 == 0) eps0 = tot;
+            if (c == 1 && a.sweep0 == 0) eps0 = tot;   // (hals_note_sum written out: through it hipcc allocates the sweep's registers differently)
             eps = tot;
             done = c;
-            if (!(eps >= a.delta * eps0)) { stopped = true; break; }   // nnls.py:156: sweep c was the last one
+            if (!hals_goes_on(eps, a.delta, eps0)) { stopped = true; break; }   // nnls.py:156: sweep c was the last one
         }
     }
     if (a.mode == 0 && (stopped || !ok)) {   // the registers hold one sweep too many
@@ -276,20 +270,14 @@ __global__ __launch_bounds__(64) void nnf_hals_quad_kernel(hals_args a) {
     if (a.mode == 0 && ok && !stopped && a.max_sweeps >= 1) {
         double tot;   // ran to the sweep budget: the last sweep's sum is still due
         ok = hals_collect_wave(a.sy, a.max_sweeps, nblocks, tot);
-        if (ok) {
+        if (ok) {   // (hals_note_sum written out: through it CH = 28 spills ten more scalar registers)
             if (a.max_sweeps == 1 && a.sweep0 == 0) eps0 = tot;
             eps = tot;
             done = a.max_sweeps;
         }
     }
-    if (a.mode == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
-        if (a.max_sweeps >= 1) {
-            a.status[NNF_HALS_ST_EPS] = eps;
-            a.status[NNF_HALS_ST_CNT] = (double)(a.sweep0 + done + 1);
-            a.status[NNF_HALS_ST_EPS0] = eps0;
-        }
-        if (!ok) a.status[NNF_HALS_ST_ERR] = 1.0;
-    }
+    if (a.mode == 0 && blockIdx.x == 0 && threadIdx.x == 0)
+        hals_status_finish(a.status, a.max_sweeps >= 1, a.sweep0, done, eps, eps0, !ok);
 }
 
 static size_t quad_lds(int ch) { return (size_t)(4 * ch) * (size_t)(4 * ((ch + 3) & ~3)) * 4; }

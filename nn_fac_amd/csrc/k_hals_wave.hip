@@ -99,12 +99,7 @@ __global__ void nnf_hals_prep_wave_kernel(const float* __restrict__ UtU, const f
         for (int i = r + threadIdx.x; i < 128; i += blockDim.x) dinv[i] = 0.f;
         if (threadIdx.x == 0) {
             *counter = 0u;
-            if (status) {
-                status[NNF_HALS_ST_EPS] = 1.0;
-                status[NNF_HALS_ST_CNT] = 1.0;
-                status[NNF_HALS_ST_EPS0] = 0.0;
-                status[NNF_HALS_ST_ERR] = 0.0;
-            }
+            if (status) hals_status_defaults(status);
         }
     }
 }
@@ -190,8 +185,8 @@ __device__ __forceinline__ double wave_sum16_f64(double v) {
 // global sum of sweep s: the granules of all blocks, strided over the lanes (late ones are re-read, bounded), added in block
 // order per lane, DPP wave sum -- the same double in every workgroup.  false = time-out or `fin` set (wave-uniform).
 __device__ __forceinline__ bool wave_total(const hals_sync& sy, const wave_ctl* ctl, int s, int nblocks, int lane, double& total) {
-    const unsigned tag = sy.epoch * 1024u + (unsigned)s;
-    const unsigned long long* base = reinterpret_cast<const unsigned long long*>(sy.sslots) + (size_t)s * nblocks * 2;
+    const unsigned tag = hals_tag(sy, s);
+    const hals_word* base = hals_row(sy, s, nblocks);
     unsigned long long g0[WAVE_NP], g1[WAVE_NP];
     // every request of the wave goes out before the first answer is looked at: no load under a branch (lanes past the last
     // block re-read block 0 and ignore it) -- one round trip for the lot, not one per pair
@@ -213,7 +208,7 @@ __device__ __forceinline__ bool wave_total(const hals_sync& sy, const wave_ctl* 
 #pragma unroll
             for (int u = 0; u < WAVE_NP; ++u)
                 if (u == i) { a0 = g0[u]; a1 = g1[u]; }
-            unsigned spins = 0;
+            unsigned spins = 0;   // (not hals_granule_wait: this loop sleeps before its first re-read too and looks at `fin`; and through the helper every instantiation spills other scalar registers)
             while (!((unsigned)(a0 >> 32) == tag && (unsigned)(a1 >> 32) == tag)) {
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > HALS_SPIN_LIMIT || ((spins & 63u) == 0u && wave_ld(&ctl->fin) != 0ull)) { late = true; break; }
@@ -228,7 +223,7 @@ __device__ __forceinline__ bool wave_total(const hals_sync& sy, const wave_ctl* 
     double v = 0.0;
 #pragma unroll
     for (int i = 0; i < WAVE_NP; ++i)
-        v += (lane + 64 * i < nblocks) ? __builtin_bit_cast(double, (g1[i] << 32) | (g0[i] & 0xffffffffull)) : 0.0;
+        v += (lane + 64 * i < nblocks) ? hals_granule_value(g0[i], g1[i]) : 0.0;
     total = nnf_wave_sum_f64(v);
     return __ballot(late) == 0ull;
 }
@@ -253,15 +248,6 @@ __device__ __forceinline__ bool wave_block_sum(wave_ctl* ctl, int c, int NW, int
     bs = wave_sum16_f64(v);
     return true;
 }
-__device__ __forceinline__ void wave_publish(const hals_sync& sy, int s, int nblocks, int lane, double mine) {
-    if (lane == 0) {
-        const unsigned long long bits = __builtin_bit_cast(unsigned long long, mine);
-        const unsigned long long tag = (unsigned long long)(sy.epoch * 1024u + (unsigned)s) << 32;
-        unsigned long long* g = reinterpret_cast<unsigned long long*>(sy.sslots) + ((size_t)s * nblocks + blockIdx.x) * 2;
-        __hip_atomic_store(g, tag | (bits & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(g + 1, tag | (bits >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
 // total + verdict of sweep cd into the rings (nnls.py:156: the loop goes on while eps >= delta * eps0).  false: give up.
 __device__ __forceinline__ bool wave_judge(const hals_args& a, wave_ctl* ctl, int cd, int nblocks, int lane) {
     double tot = 0.0;
@@ -281,7 +267,7 @@ __device__ __forceinline__ bool wave_judge(const hals_args& a, wave_ctl* ctl, in
                     if (++spins > HALS_SPIN_LIMIT || wave_ld(&ctl->fin) != 0ull) return false;
                 }
             }
-            flag = (tot >= a.delta * e0) ? 0u : 1u;
+            flag = hals_goes_on(tot, a.delta, e0) ? 0u : 1u;
         }
     }
     if (lane == 0) {
@@ -297,7 +283,7 @@ __device__ __forceinline__ void wave_comm_loop(const hals_args& a, wave_ctl* ctl
     for (; c <= S; c += WAVE_COMM) {
         double bs;
         if (!wave_block_sum(ctl, c, NW, lane, bs)) return;
-        wave_publish(a.sy, c, nblocks, lane, bs);
+        hals_publish(a.sy, c, nblocks, bs, lane == 0);
         const int cd = c - WAVE_COMM;                     // published by everybody a few sweeps ago
         if (cd >= 1 && !wave_judge(a, ctl, cd, nblocks, lane)) return;
     }
@@ -335,12 +321,7 @@ __global__ __launch_bounds__(1024) void nnf_hals_wave_kernel(hals_args a, int64_
     }
     for (int e = threadIdx.x; e < (int)(sizeof(wave_ctl) / 8); e += blockDim.x)
         reinterpret_cast<unsigned long long*>(ctl)[e] = 0ull;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {            // (rewritten by this same thread at the end)
-        a.status[NNF_HALS_ST_EPS] = 1.0;
-        a.status[NNF_HALS_ST_CNT] = 1.0;
-        a.status[NNF_HALS_ST_EPS0] = 0.0;
-        a.status[NNF_HALS_ST_ERR] = 0.0;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) hals_status_defaults(a.status);   // (rewritten by this same thread at the end)
     __syncthreads();                                      // the only barrier: image and control block are in LDS
     if (w >= NW) {
         wave_comm_loop(a, ctl, NW, w - NW, lane, nblocks);
@@ -489,18 +470,16 @@ __global__ __launch_bounds__(1024) void nnf_hals_wave_kernel(hals_args a, int64_
         }
     }
     if (blockIdx.x == 0 && w == 0 && lane == 0) {
-        if (S >= 1 && last != WAVE_ERR) {
-            double eps = 1.0, eps0 = 0.0;
+        double eps = 1.0, eps0 = 0.0;
+        const bool judged_all = S >= 1 && last != WAVE_ERR;
+        if (judged_all) {
             (void)wave_ld_tagged(&ctl->tot[(int)last & (WAVE_SNAP - 1)][0], last, eps);
             (void)wave_ld_tagged(&ctl->eps0[0], 1u, eps0);
             if (last == 1u) eps0 = eps;
             if (WAVE_DBG & 1) { eps = 1.0; eps0 = 0.0; }
-            a.status[NNF_HALS_ST_EPS] = eps;
-            a.status[NNF_HALS_ST_CNT] = (double)(last + 1u);
-            a.status[NNF_HALS_ST_EPS0] = eps0;
         }
-        if (last == WAVE_ERR || __hip_atomic_load(a.sy.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == err_tag)
-            a.status[NNF_HALS_ST_ERR] = 1.0;
+        hals_status_finish(a.status, judged_all, 0, (int)last, eps, eps0,   // (no chained launches: sweep0 = 0)
+                           last == WAVE_ERR || __hip_atomic_load(a.sy.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == err_tag);
     }
 }
 
