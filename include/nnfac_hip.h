@@ -466,6 +466,17 @@ int nnf_dot_f32(nnf_ctx* ctx, const float* A, int64_t lda, const float* B, int64
                 double* out_f64, void* stream);
 /* C = A .* B elementwise, r x r  (Hadamard of Grams, ntf.py:442-445) */
 int nnf_hadamard_f32(nnf_ctx* ctx, const float* A, const float* B, float* C, int64_t count, void* stream);
+/* The two fixed-order fp64 reductions every split launch of the library ends in, on the caller's data (tests/test_gpu_reduce.py
+ * checks every form of them bit for bit; tests/reduce_restatement.py states the form a set of slabs takes and the order of its
+ * sums; NNF_REDUCE_DEBUG: "[nnf reduce] rows= cols= nslab= lds= ldo= out64= form= blocks= set= block0=" on stderr, one line per
+ * set of every reduction launch of the library).  Both refuse with NNF_ERR_ARG, launching nothing: a null pointer (but out64),
+ * nslab, rows, cols or count < 1, lds < cols, ldo < cols, slab_stride < (rows - 1) * lds + cols. */
+/* out[row][col] = (float) sum_s slabs[s*slab_stride + row*lds + col], fp64, slab order; out64 (may be NULL): the sums
+ * before rounding, rows x cols contiguous.  The reduction behind every split launch, on the caller's slabs. */
+int nnf_reduce_slabs_f32(nnf_ctx* ctx, const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols,
+                         int64_t lds, float* out, int64_t ldo, double* out64, void* stream);
+/* out_f64[0] = scale * sum of count doubles, index order, one workgroup (the tail of the cost kernels). */
+int nnf_sum_f64(nnf_ctx* ctx, const double* partial_f64, int64_t count, double scale, double* out_f64, void* stream);
 
 /* ---- grouped kernels: the K slices of nonnegative PARAFAC2 (nn_fac/parafac2.py:509-600) in one launch each --------------
  * Group g owns the columns [off[g], off[g+1]) of stacked operands with `total_cols` columns; `off` is a DEVICE array of

@@ -80,6 +80,8 @@ SIGNATURES = {
     "nnf_cp3_betadiv_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _f64, _p, _p]),
     "nnf_dot_f32": (_i32, [_p, _p, _i64, _p, _i64, _i64, _i64, _p, _p]),
     "nnf_hadamard_f32": (_i32, [_p, _p, _p, _p, _i64, _p]),
+    "nnf_reduce_slabs_f32": (_i32, [_p, _p, _i32, _i64, _i32, _i64, _i64, _p, _i64, _p, _p]),
+    "nnf_sum_f64": (_i32, [_p, _p, _i64, _f64, _p, _p]),
     "nnf_hals_group_max_columns": (_i32, [_p, _i32, C.POINTER(_i64)]),
     "nnf_hals_solve_group_f32": (_i32, [_p, _p, _i64, _p, _i64, _i64, _p, _i64, _i32, _p, _i32, _i64, _i64, _i32, _f64, _p, _p]),
     "nnf_group_gram_f32": (_i32, [_p, _p, _i64, _i32, _p, _i32, _i64, _p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _p, _p]),

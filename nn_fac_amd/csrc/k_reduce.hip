@@ -1,5 +1,11 @@
 // Fixed-order fp64 reductions behind the split launches of the library (W^T X, the X H^T tail, the Gram, the MU updates, MTTKRP,
 // NTD): the slabs of a split added in slab order, and a vector of fp64 partials added in index order.  Bitwise reproducible.
+// Which form a set of slabs takes is decided in k_stream_plan.h (nnf_plan_reduce_set; tools/nnf_plan.cpp `reduce` prints it
+// without a device) and reported per set under NNF_REDUCE_DEBUG ("[nnf reduce] ... form= blocks= set= block0="); the kernels and
+// launchers are here.  nnf_reduce_slabs_f32 and nnf_sum_f64 (include/nnfac_hip.h, at the end of this file) run the two
+// reductions on the caller's data: tests/test_gpu_reduce.py checks every form bit for bit against tests/reduce_restatement.py
+// (the rule of the plan and the order of the sums, restated), tests/test_reduce_plan.py holds the plan to it on the CPU, and
+// tests/test_gpu_fused_cross.py the multi-set launch.
 #include "nnf_internal.h"
 
 // One set of slabs and where its sums go, with the form nnf_plan_reduce_set chose for it.  A launch handles one set
@@ -123,34 +129,16 @@ __global__ __launch_bounds__(256) void nnf_reduce_sets_kernel(nnf_reduce_sets a)
     }
 }
 
-// the form and the workgroups a set takes (the same for a launch of its own and for a share of a fused one)
-nnf_reduce_set nnf_plan_reduce_set(const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols, int64_t lds,
-                                   float* out, int64_t ldo, double* out64) {
-    nnf_reduce_set q{slabs, out, out64, slab_stride, cols, lds, ldo, nslab, rows, 0, 0, 0, 0};
-    const int64_t total = (int64_t)rows * cols;
-    // enough threads to fill the chip: 2^lg parts per element when the output is small
-    while (q.lg < 4 && (total << q.lg) < ((int64_t)1 << 19) && (2 << q.lg) <= nslab) ++q.lg;
-    if (q.lg > 0) {
-        const int64_t grid = nnf_cdiv(total, 256 >> q.lg);
-        q.blocks = grid > 4096 ? 4096 : (int)grid;
-        return q;
-    }
-    // (four columns per thread only when that still leaves enough threads to fill the chip: 20 vs 16 us at r x n = 1e5)
-    if (out64 == nullptr && (lds & 3) == 0 && (slab_stride & 3) == 0 && (((uintptr_t)slabs) & 15) == 0 && total >= ((int64_t)1 << 21)) {
-        const int64_t total4 = (int64_t)rows * ((cols + 3) >> 2);
-        const int64_t grid4 = (total4 + 255) / 256;
-        q.vec4 = 1;
-        q.blocks = grid4 > 2048 ? 2048 : (int)grid4;
-        return q;
-    }
-    const int64_t grid = (total + 255) / 256;
-    q.blocks = grid > 2048 ? 2048 : grid < 1 ? 1 : (int)grid;
-    return q;
+// NNF_REDUCE_DEBUG (read once): one "[nnf reduce]" line per set of every launch below (nnf_report_reduce, k_stream_plan.h)
+static inline bool nnf_reduce_debug() {
+    static const bool dbg = getenv("NNF_REDUCE_DEBUG") != nullptr;
+    return dbg;
 }
 
 int nnf_launch_reduce_slabs(const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols, int64_t lds,
                             float* out, int64_t ldo, hipStream_t st, double* out64) {
     const nnf_reduce_set q = nnf_plan_reduce_set(slabs, nslab, slab_stride, rows, cols, lds, out, ldo, out64);
+    if (nnf_reduce_debug()) nnf_report_reduce(stderr, q, 0, 1);
     if (q.lg > 0)
         return nnf_dispatch<4>(q.lg, [&](auto k) -> int {
             constexpr int P = 1 << decltype(k)::value;
@@ -178,6 +166,7 @@ int nnf_launch_reduce_sets(const nnf_reduce_set* sets, int nsets, hipStream_t st
         a.set[i] = sets[i];
         a.set[i].block0 = grid;
         grid += sets[i].blocks;
+        if (nnf_reduce_debug()) nnf_report_reduce(stderr, a.set[i], i, nsets);
     }
     hipLaunchKernelGGL(nnf_reduce_sets_kernel, dim3(grid), dim3(256), 0, st, a);
     NNF_CHECK_LAUNCH();
@@ -204,4 +193,18 @@ int nnf_launch_sum_f64(const double* partial, int64_t count, double scale, doubl
     hipLaunchKernelGGL(nnf_sum_partials_kernel, dim3(1), dim3(256), 0, st, partial, count, scale, out);
     NNF_CHECK_LAUNCH();
     return NNF_OK;
+}
+
+// ---- the two reductions on the caller's data (include/nnfac_hip.h; tests/test_gpu_reduce.py) ----
+extern "C" int nnf_reduce_slabs_f32(nnf_ctx* ctx, const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols,
+                                    int64_t lds, float* out, int64_t ldo, double* out64, void* stream) {
+    if (!ctx || !slabs || !out || nslab < 1 || rows < 1 || cols < 1 || lds < cols || ldo < cols ||
+        slab_stride < (int64_t)(rows - 1) * lds + cols)
+        return NNF_ERR_ARG;
+    return nnf_launch_reduce_slabs(slabs, nslab, slab_stride, rows, cols, lds, out, ldo, (hipStream_t)stream, out64);
+}
+
+extern "C" int nnf_sum_f64(nnf_ctx* ctx, const double* partial_f64, int64_t count, double scale, double* out_f64, void* stream) {
+    if (!ctx || !partial_f64 || !out_f64 || count < 1) return NNF_ERR_ARG;
+    return nnf_launch_sum_f64(partial_f64, count, scale, out_f64, (hipStream_t)stream);
 }

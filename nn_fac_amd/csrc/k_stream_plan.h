@@ -385,6 +385,57 @@ inline void nnf_report_rider(FILE* f, const char* what, const nnf_rider_plan& p,
             (long long)p.rider_offset, (long long)p.grid, p.main_bytes, p.rider_bytes, p.rider_ws_off, p.ws_bytes, more);
 }
 
+// ---- the fixed-order slab reduction behind every split launch (k_reduce.hip) ----
+// One set of slabs, where its sums go and the form the reduction takes for it: lg > 0: 2^lg threads per element ("par2" ..
+// "par16"); else vec4: four columns per thread; else one element per thread ("plain").  blocks: its workgroups; block0: where
+// they start in a launch shared with other sets (nnf_launch_reduce_sets fills it in).
+#define NNF_REDUCE_MAX_SETS 3
+struct nnf_reduce_set {
+    const float* slabs;
+    float* out;
+    double* out64;
+    int64_t slab_stride, cols, lds, ldo;
+    int nslab, rows;
+    int lg, vec4, blocks, block0;
+};
+// the form and the workgroups a set takes (the same for a launch of its own and for a share of a fused one); the slab pointer
+// is read for its 16-byte alignment only.  The order of the sums each form keeps is restated in tests/reduce_restatement.py.
+// (The 4096-workgroup cap of the parts forms never binds: rows * cols < 2^(20 - lg) elements at 2^(8 - lg) per workgroup are at
+// most 4096 workgroups, so a workgroup of those forms walks its loop once -- tests/test_reduce_plan.py holds that as a property.)
+inline nnf_reduce_set nnf_plan_reduce_set(const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols, int64_t lds,
+                                          float* out, int64_t ldo, double* out64 = nullptr) {
+    nnf_reduce_set q{slabs, out, out64, slab_stride, cols, lds, ldo, nslab, rows, 0, 0, 0, 0};
+    const int64_t total = (int64_t)rows * cols;
+    // enough threads to fill the chip: 2^lg parts per element when the output is small
+    while (q.lg < 4 && (total << q.lg) < ((int64_t)1 << 19) && (2 << q.lg) <= nslab) ++q.lg;
+    if (q.lg > 0) {
+        const int64_t grid = nnf_cdiv(total, 256 >> q.lg);
+        q.blocks = grid > 4096 ? 4096 : (int)grid;
+        return q;
+    }
+    // (four columns per thread only when that still leaves enough threads to fill the chip: 20 vs 16 us at r x n = 1e5)
+    if (out64 == nullptr && (lds & 3) == 0 && (slab_stride & 3) == 0 && (((uintptr_t)slabs) & 15) == 0 && total >= ((int64_t)1 << 21)) {
+        const int64_t total4 = (int64_t)rows * ((cols + 3) >> 2);
+        const int64_t grid4 = (total4 + 255) / 256;
+        q.vec4 = 1;
+        q.blocks = grid4 > 2048 ? 2048 : (int)grid4;
+        return q;
+    }
+    const int64_t grid = (total + 255) / 256;
+    q.blocks = grid > 2048 ? 2048 : grid < 1 ? 1 : (int)grid;
+    return q;
+}
+constexpr const char* nnf_reduce_form_name(int lg, int vec4) {
+    return lg == 1 ? "par2" : lg == 2 ? "par4" : lg == 3 ? "par8" : lg >= 4 ? "par16" : vec4 ? "vec4" : "plain";
+}
+// NNF_REDUCE_DEBUG: one line per set of every reduction launch (set `set` of `nsets`, counted from 0).  A tag of its own:
+// the "[nnf plan]" lines of a call are counted by the tests that key on them.
+inline void nnf_report_reduce(FILE* f, const nnf_reduce_set& q, int set, int nsets, const char* more = "") {
+    fprintf(f, "[nnf reduce] rows=%d cols=%lld nslab=%d lds=%lld ldo=%lld out64=%d form=%s blocks=%d set=%d/%d block0=%d%s\n", q.rows,
+            (long long)q.cols, q.nslab, (long long)q.lds, (long long)q.ldo, (int)(q.out64 != nullptr), nnf_reduce_form_name(q.lg, q.vec4),
+            q.blocks, set, nsets, q.block0, more);
+}
+
 // ---- the cost / ratio pass (launch_cost): 128-row workgroups x column splits ----
 // 32 rows of X (or of the model buffer of a rank above 128) at pitch ld and a factor chunk inside 32-bit offsets
 constexpr bool nnf_cost_offsets_ok(int64_t ld, int64_t n) { return 32 * ld * 4 + 4 * (n + 128) < NNF_OFFSET32_END; }

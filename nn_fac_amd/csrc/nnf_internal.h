@@ -122,21 +122,8 @@ __device__ __forceinline__ void nnf_xcd_map(int bid, int members, int& group, in
 int nnf_launch_reduce_slabs(const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols, int64_t lds,
                             float* out, int64_t ldo, hipStream_t st, double* out64 = nullptr);   // out64: the sums before rounding (rows x cols, contiguous)
 
-// One set of slabs, where its sums go and the form the reduction takes for it (nnf_plan_reduce_set, k_reduce.hip): lg > 0: 2^lg
-// threads per element; else vec4: four columns per thread; else one element per thread.  blocks: its workgroups; block0: where
-// they start in a launch shared with other sets (nnf_launch_reduce_sets fills it in).
-#define NNF_REDUCE_MAX_SETS 3
-struct nnf_reduce_set {
-    const float* slabs;
-    float* out;
-    double* out64;
-    int64_t slab_stride, cols, lds, ldo;
-    int nslab, rows;
-    int lg, vec4, blocks, block0;
-};
-nnf_reduce_set nnf_plan_reduce_set(const float* slabs, int nslab, int64_t slab_stride, int rows, int64_t cols, int64_t lds,
-                                   float* out, int64_t ldo, double* out64 = nullptr);
-// up to NNF_REDUCE_MAX_SETS planned sets in one launch; every set's sums are the bits nnf_launch_reduce_slabs gives it
+// up to NNF_REDUCE_MAX_SETS sets planned by nnf_plan_reduce_set (k_stream_plan.h) in one launch; every set's sums are the bits
+// nnf_launch_reduce_slabs gives it.  NNF_REDUCE_DEBUG: both launchers write one "[nnf reduce]" stderr line per set.
 int nnf_launch_reduce_sets(const nnf_reduce_set* sets, int nsets, hipStream_t st);
 
 // the Gram that may ride in a cross-product launch (nnf_xty_gram_f32, nnf_xht_gram_f32): G (pitch ldg) and, if not null, its

@@ -58,6 +58,12 @@
 //                                     cols); both=1 / both=-1: den and den_vec both given / both missing.  Answer: the
 //                                     "[nnf plan] simplex ..." line of that call, or "status=<code>" for a refusal (the argument
 //                                     checks of nnf_simplex_proj_kl_f32 included).
+//                        The slab reduction behind every split launch (nnf_plan_reduce_set, k_stream_plan.h), key=value only:
+//                          reduce rows= cols= nslab= [lds=] [stride=] [ldo=] [align=] [out64=]     lds / ldo default to cols, stride
+//                                     (floats from one slab to the next) to rows * lds; align: the slabs' offset from a 16-byte
+//                                     boundary in floats; out64=1: the fp64 sums are asked for.  Answer: the "[nnf reduce] ..."
+//                                     line of that launch (NNF_REDUCE_DEBUG), or "status=<code>" (the argument checks of
+//                                     nnf_reduce_slabs_f32).
 //   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
 //                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
 //
@@ -165,6 +171,23 @@ static int answer_simplex(const char* line) {
     return 0;
 }
 
+static int answer_reduce(const char* line) {
+    const char* rest = line + strcspn(line, " \t");
+    const long long rows = key_of(rest, "rows", 0), cols = key_of(rest, "cols", 0), nslab = key_of(rest, "nslab", 0);
+    const long long lds = key_of(rest, "lds", cols), ldo = key_of(rest, "ldo", cols), stride = key_of(rest, "stride", rows * lds);
+    // (the argument checks of nnf_reduce_slabs_f32, k_reduce.hip)
+    if (nslab < 1 || rows < 1 || cols < 1 || lds < cols || ldo < cols || stride < (rows - 1) * lds + cols) {
+        printf("status=%d\n", NNF_ERR_ARG);
+        return 0;
+    }
+    // pointers that only carry what the plan reads of them: the slabs' offset from a 16-byte boundary, whether out64 is given
+    static double sums64;
+    const nnf_reduce_set q = nnf_plan_reduce_set((const float*)(uintptr_t)(4096 + 4 * (key_of(rest, "align", 0) & 3)), (int)nslab, stride,
+                                                 (int)rows, cols, lds, nullptr, ldo, key_of(rest, "out64", 0) != 0 ? &sums64 : nullptr);
+    nnf_report_reduce(stdout, q, 0, 1);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "shm") == 0) return print_shm();
     char line[512], name[32], more[192];
@@ -172,6 +195,10 @@ int main(int argc, char** argv) {
         long long C, m, n, r, ld, ws;
         double beta;
         int used = 0;
+        if (sscanf(line, "%31s", name) == 1 && strcmp(name, "reduce") == 0) {
+            answer_reduce(line);
+            continue;
+        }
         if (sscanf(line, "%31s", name) == 1 && (strncmp(name, "hals", 4) == 0 || strcmp(name, "simplex") == 0)) {
             if ((name[0] == 's' ? answer_simplex(line) : answer_hals(name, line)) != 0) {
                 fprintf(stderr, "nnf_plan: bad case line: %s", line);
