@@ -531,6 +531,45 @@ int nnf_group_gemm_f32(nnf_ctx* ctx, const float* M, int64_t ldm, int64_t mstrid
 int nnf_frob_resid_rows_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Ut, int64_t ldu,
                             const float* V, int64_t ldv, int r, double* rows_f64, void* stream);
 
+/* ---- sparse data: NMF on a CSR matrix, over the stored entries only (nn_fac_amd/sparse_nmf.py) ----------------------------
+ * The matrix (nrows x ncols, nnz < 2^31 stored entries) is canonical CSR on the device: rowptr int64 [nrows + 1] with
+ * rowptr[0] = 0, colidx int32 sorted inside a row and without duplicates, vals float; stored zeros are allowed.  A factor that
+ * is GATHERED is passed node-major: ncols x ldn, row j holds the r components of node j, ldn >= r a multiple of 4 floats, the
+ * base 16-byte aligned (one stored entry is one contiguous read; the columns r .. ldn are never used).  Results are
+ * component-major (r x nrows), what nnf_hals_solve_f32 and nnf_mu_apply_f32 take.
+ * Work is cut into chunks of at most `ch` consecutive stored entries of one row, one wave each, so that the time does not
+ * depend on how the row lengths are distributed.  The chunk table is built ONCE per matrix by the caller (on the device):
+ *   rowchunk int64 [nrows + 1] = exclusive prefix sum of ceil(len_i / ch)  (an empty row owns no chunk),
+ *   chunk_row int32 [nchunks]  = the row of every chunk,  nchunks = rowchunk[nrows],
+ * with ch = nnf_csr_chunk_entries (a power of two in 64 .. 1024 from the CU count and nnz: k_sparse_plan.h; NNF_SPARSE_CH in the
+ * environment overrides it for measurements); any 1 <= ch <= 2^20 the table was built with is accepted.  The host cannot see
+ * the tables: the kernels hold every index they read from them against nrows, ncols, nnz and nchunks, so that a table that does
+ * not belong to the matrix gives wrong sums and never an access outside the arrays.
+ * Every chunk leaves its r sums (fp32 FMAs in a fixed order) in one node-major row of the context workspace (4 nchunks
+ * roundup4(r) bytes, NNF_ERR_WORKSPACE if that does not fit); a second kernel adds the rows of each matrix row's chunks in
+ * chunk order in fp64, rounds once and writes the component-major result.  No atomics and no waiting between workgroups: two
+ * calls are bitwise equal.  NaN / Inf in vals or the factors propagate.  r <= NNF_MAX_RANK (NNF_ERR_UNSUPPORTED above, as for
+ * nnz or ncols >= 2^31); NNF_ERR_ARG, nothing launched: null pointers, ldn not a multiple of 4 or < r, a misaligned node-major
+ * operand, short output pitches, nchunks outside [nnz / ch, nnz]. */
+int nnf_csr_chunk_entries(nnf_ctx* ctx, int64_t nnz, int64_t* out);
+/* out[k,i] = sum_{p in row i} vals[p] Fn[colidx[p], k]   (r x nrows, pitch ldo).  With the CSR of X and Fn = V^T this is V X^T
+ * (r x m); with the CSR of X^T and Fn = U it is U^T X (r x n). */
+int nnf_csr_xf_f32(nnf_ctx* ctx, const int64_t* rowptr, const int32_t* colidx, const float* vals, int64_t nrows, int64_t ncols,
+                   int64_t nnz, const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, const float* Fn,
+                   int64_t ldn, int r, float* out, int64_t ldo, void* stream);
+/* The beta = 1 sums over the stored entries (mu.py:84-97 and beta_divergence at beta = 1 vanish wherever x = 0, up to the
+ * terms the caller adds): per stored entry x at (i, j),  p = <Own_n[i, :], Fn[j, :]> (fp32: four products per lane in index
+ * order, then a fixed tree),  q = x / p,
+ *   num[k,i] = sum q Fn[j,k]     (r x nrows, pitch ldnum; may be NULL: cost only),
+ *   cost_f64[0] = sum (x log(x / p) - x) in fp64     (may be NULL: numerator only);
+ * a stored x = 0 adds 0 to both (0 log 0 := 0).  Own_n: nrows x ldo_n, node-major like Fn.  The caller adds
+ * colsum(U) . rowsum(V) to the cost and hands num with the row sums to nnf_mu_apply_f32.  The U side takes the CSR of X
+ * (Own_n = U, Fn = V^T), the V side the CSR of X^T (Own_n = V^T, Fn = U).  The three forms (both, num only, cost only) give the
+ * same bits for what they share. */
+int nnf_csr_kl_f32(nnf_ctx* ctx, const int64_t* rowptr, const int32_t* colidx, const float* vals, int64_t nrows, int64_t ncols,
+                   int64_t nnz, const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, const float* Own_n,
+                   int64_t ldo_n, const float* Fn, int64_t ldn, int r, float* num, int64_t ldnum, double* cost_f64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,42 @@ def to_dev_t(x, device):
     return t
 
 
+def _is_scipy_sparse(x):
+    return type(x).__module__.startswith("scipy.sparse") and hasattr(x, "tocsr")
+
+
+def is_sparse(x):
+    """A scipy.sparse matrix or array of any format, or a torch sparse-CSR tensor (the inputs of nn_fac_amd.sparse_nmf)."""
+    if isinstance(x, torch.Tensor):
+        return x.layout == torch.sparse_csr
+    return _is_scipy_sparse(x)
+
+
+def to_dev_csr(x, device, transpose=False):
+    """Canonical CSR of a sparse input (of its transpose: `transpose`) on the device: (rowptr int64, colidx int32, vals float32,
+    shape) with sorted indices and no duplicates; stored zeros stay.  Never through a dense copy: a SciPy input is converted
+    on the host (`.tocsr()`, `sum_duplicates()`, `sort_indices()`; the transpose by `.T.tocsr()`), a torch CSR tensor -- host or
+    device, taken as canonical -- on the device (the transpose by a stable sort of the entries by column)."""
+    if isinstance(x, torch.Tensor):
+        m, n = x.shape
+        rowptr = x.crow_indices().to(device=device, dtype=torch.int64)
+        colidx = x.col_indices().to(device=device, dtype=torch.int64)
+        vals = x.values().to(device=device, dtype=torch.float32)
+        if transpose:
+            rows = torch.repeat_interleave(torch.arange(m, dtype=torch.int64, device=device), rowptr[1:] - rowptr[:-1])
+            order = torch.argsort(colidx, stable=True)      # row-major in, so every new row keeps its entries sorted
+            counts = torch.bincount(colidx, minlength=n)
+            rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+            torch.cumsum(counts, 0, out=rowptr[1:])
+            colidx, vals, (m, n) = rows[order], vals[order], (n, m)
+        return rowptr.contiguous(), colidx.to(torch.int32).contiguous(), vals.contiguous(), (int(m), int(n))
+    a = (x.T if transpose else x).tocsr(copy=True)      # (a copy: the caller's matrix is not canonicalised in place)
+    a.sum_duplicates()
+    a.sort_indices()
+    return (torch.from_numpy(a.indptr.astype(np.int64)).to(device), torch.from_numpy(a.indices.astype(np.int32)).to(device),
+            torch.from_numpy(a.data.astype(np.float32)).to(device), (int(a.shape[0]), int(a.shape[1])))
+
+
 def like_input(t, proto):
     """Return device tensor `t` in the type/dtype of the caller's `proto` (ndarray -> ndarray of its dtype)."""
     if isinstance(proto, torch.Tensor):

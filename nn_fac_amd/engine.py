@@ -216,6 +216,77 @@ def _out64(out, count, dev, what):
     return torch.empty(count, dtype=torch.float64, device=dev) if out is None else _f64(out, count, dev, what)
 
 
+def _csr_triple(rowptr, colidx, vals, shape, what):
+    """A canonical CSR triple on one device -- rowptr int64 [nrows + 1] from 0 to nnz and non-decreasing, colidx int32 [nnz]
+    inside [0, ncols), vals float32 [nnz], all contiguous, nnz < 2^31 -> (nrows, ncols, nnz).  Reads four words back from the
+    device: called once per matrix (CsrMatrix), not per launch."""
+    nrows, ncols = int(shape[0]), int(shape[1])
+    for t, dt, nm in ((rowptr, torch.int64, "rowptr"), (colidx, torch.int32, "colidx"), (vals, torch.float32, "vals")):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda \
+                or t.device != rowptr.device:
+            raise EngineError(f"{what} {nm}: expected a contiguous 1-D {dt} tensor on the device of rowptr")
+    nnz = vals.numel()
+    if nrows < 1 or ncols < 1 or ncols >= 2 ** 31 or nnz >= 2 ** 31:
+        raise EngineError(f"{what}: a {nrows} x {ncols} matrix with {nnz} stored entries is outside 1 <= extents, ncols and nnz < 2^31")
+    if rowptr.numel() != nrows + 1 or colidx.numel() != nnz:
+        raise EngineError(f"{what}: lengths do not fit, {nrows} rows, rowptr {rowptr.numel()}, colidx {colidx.numel()}, vals {nnz}")
+    ends = torch.stack([rowptr[0], rowptr[-1], (rowptr[1:] - rowptr[:-1]).min()]).tolist()
+    if ends[0] != 0 or ends[1] != nnz or ends[2] < 0:
+        raise EngineError(f"{what} rowptr: must rise from rowptr[0] == 0 to rowptr[-1] == nnz ({nnz}); got {ends[0]} .. {ends[1]}")
+    if nnz and not bool(((colidx >= 0) & (colidx < ncols)).all()):
+        raise EngineError(f"{what} colidx: an index outside [0, {ncols})")
+    return nrows, ncols, nnz
+
+
+def csr_chunk_table(rowptr, ch):
+    """The chunk table of include/nnfac_hip.h for chunks of at most `ch` stored entries: (rowchunk int64 [nrows + 1], chunk_row
+    int32 [nchunks]); plain index arithmetic on rowptr's device (host tensors too: tests/test_sparse_plan.py)."""
+    counts = (rowptr[1:] - rowptr[:-1] + (int(ch) - 1)) // int(ch)
+    rowchunk = torch.zeros(rowptr.numel(), dtype=torch.int64, device=rowptr.device)
+    torch.cumsum(counts, 0, out=rowchunk[1:])
+    rows = torch.arange(counts.numel(), dtype=torch.int32, device=rowptr.device)
+    return rowchunk, torch.repeat_interleave(rows, counts).contiguous()
+
+
+class CsrMatrix:
+    """A device CSR matrix with the chunk table the CSR kernels walk (Engine.csr_matrix): checked and cut into chunks once."""
+
+    def __init__(self, eng, rowptr, colidx, vals, shape, ch=None):
+        self.nrows, self.ncols, self.nnz = _csr_triple(rowptr, colidx, vals, shape, "csr_matrix")
+        self.shape = (self.nrows, self.ncols)
+        self.rowptr, self.colidx, self.vals, self.device = rowptr, colidx, vals, rowptr.device
+        self.ch = int(ch) if ch is not None else eng.csr_chunk_entries(self.nnz)
+        if not 1 <= self.ch <= 1 << 20:
+            raise EngineError(f"csr_matrix: a chunk size of {self.ch} is outside 1 .. 2^20")
+        self.rowchunk, self.chunk_row = csr_chunk_table(rowptr, self.ch)
+        self.nchunks = self.chunk_row.numel()
+
+    def args(self):
+        """The argument run of the CSR entries."""
+        return (_ptr(self.rowptr), _ptr(self.colidx), _ptr(self.vals), self.nrows, self.ncols, self.nnz, _ptr(self.rowchunk),
+                _ptr(self.chunk_row), self.nchunks, self.ch)
+
+
+def _node_major(F, nodes, what):
+    """A gathered operand: nodes x r float32 on the device, unit inner stride, pitch a multiple of 4 floats, base 16-byte aligned
+    -> r."""
+    if _chk2d(F, what).shape[0] != nodes:
+        raise EngineError(f"{what}: a node-major operand of {nodes} rows expected, got {tuple(F.shape)}")
+    if _ld(F) % 4 != 0 or F.data_ptr() % 16 != 0:
+        raise EngineError(f"{what}: a node-major operand needs a pitch that is a multiple of 4 floats and a 16-byte aligned base "
+                          f"(node_major() makes one), got pitch {_ld(F)}")
+    return F.shape[1]
+
+
+def node_major(Ft):
+    """The node-major copy (nodes x r, pitch r rounded up to 4 floats) of a component-major factor Ft (r x nodes): data movement."""
+    r, nodes = Ft.shape
+    buf = torch.zeros((nodes, (r + 3) // 4 * 4), dtype=torch.float32, device=Ft.device)
+    view = buf[:, :r]
+    view.copy_(Ft.t())
+    return view
+
+
 class KernelTime(float):
     """Mean launch duration in ms (the float) + the spread of the samples it came from."""
 
@@ -230,7 +301,55 @@ class KernelTime(float):
         return {"samples": self.n, "mean_ms": float(self), "median_ms": self.median, "min_ms": self.min, "max_ms": self.max}
 
 
-class Engine:
+class CsrOps:
+    """The CSR entries of the engine (Engine inherits them): NMF on sparse data, over the stored entries only.  Their operand
+    refusals are tested in tests/test_gpu_sparse_kernels.py, one spoilt operand at a time, as tests/test_gpu_engine_args.py does
+    for the methods Engine defines itself."""
+
+    def csr_chunk_entries(self, nnz):
+        """Stored entries per chunk the library cuts a matrix of `nnz` stored entries into (nnf_csr_chunk_entries)."""
+        return self._query("nnf_csr_chunk_entries", int(nnz))
+
+    def csr_matrix(self, rowptr, colidx, vals, shape, ch=None):
+        """A checked device CSR matrix with its chunk table (once per matrix; `ch`: another chunk size than the library's)."""
+        return CsrMatrix(self, rowptr, colidx, vals, shape, ch=ch)
+
+    @staticmethod
+    def _csr_rank(A, Fn, what):
+        if not isinstance(A, CsrMatrix):
+            raise EngineError(f"{what}: the matrix must be a CsrMatrix (Engine.csr_matrix)")
+        r = _node_major(Fn, A.ncols, what + " Fn")
+        if Fn.device != A.device:
+            raise EngineError(f"{what} Fn must be on {A.device}, got {Fn.device}")
+        if r > MAX_RANK:
+            raise EngineError(f"{what}: rank {r} is above the {MAX_RANK} the CSR kernels are built for")
+        return r
+
+    def csr_xf(self, A, Fn, out=None):
+        """A (CsrMatrix, nrows x ncols), Fn (ncols x r, node-major) -> out[k, i] = sum_{p in row i} vals[p] Fn[colidx[p], k]
+        (r x nrows): V X^T from the CSR of X and V^T, U^T X from the CSR of X^T and U (nnf_csr_xf_f32)."""
+        r = self._csr_rank(A, Fn, "csr_xf")
+        O = _out(out, (r, A.nrows), Fn, "csr_xf out")
+        self._call("nnf_csr_xf_f32", *A.args(), *_mat(Fn), r, *_mat(O))
+        return O
+
+    def csr_kl(self, A, Own_n, Fn, num=True, cost_out=None, out=None):
+        """The beta = 1 sums over the stored entries of A (nnf_csr_kl_f32): with p = <Own_n[i, :], Fn[j, :]> and q = x / p per
+        stored x at (i, j), the numerator num[k, i] = sum q Fn[j, k] (r x nrows; `num=False`: not asked for) and, into the
+        1-element float64 `cost_out`, sum (x log(x / p) - x).  Returns the numerator or None."""
+        r = self._csr_rank(A, Fn, "csr_kl")
+        if _node_major(Own_n, A.nrows, "csr_kl Own_n") != r or Own_n.device != A.device:
+            raise EngineError(f"csr_kl Own_n: {A.nrows} x {r} on {A.device} expected, got {tuple(Own_n.shape)} on {Own_n.device}")
+        if not num and cost_out is None:
+            raise EngineError("csr_kl: nothing asked for")
+        if cost_out is not None:
+            _f64(cost_out, 1, A.device, "csr_kl cost_out")
+        O = _out(out, (r, A.nrows), Fn, "csr_kl out") if num else None
+        self._call("nnf_csr_kl_f32", *A.args(), *_mat(Own_n), *_mat(Fn), r, *_optmat(O), _opt(cost_out))
+        return O
+
+
+class Engine(CsrOps):
     """One context (workspace + device properties) per device."""
 
     def __init__(self, device, workspace_bytes=0):

@@ -25,7 +25,7 @@ import torch
 from .utils import errors as err
 from .utils import initialize_factors as init_factors
 from . import engine as _engine
-from ._convert import device_of, to_dev, to_dev_t, like_input
+from ._convert import device_of, to_dev, to_dev_t, like_input, is_sparse
 from . import dist as _dist
 from . import _outer_loop as _loop
 from ._status import NMF_COST, NMF_IDENT_COST, NMF_IDENT_VERDICT, NMF_IDENT_ESTIMATE, NMF_WORDS, write_status
@@ -45,6 +45,10 @@ def nmf(data, rank, init="random", U_0=None, V_0=None, n_iter_max=100, tol=1e-8,
 
     if deterministic:
         np.random.seed(seed)
+
+    if is_sparse(data):      # sparse_nmf.py: what that path refuses is said before the start values are drawn
+        from . import sparse_nmf
+        sparse_nmf.check_request(rank, update_rule, beta, init=init)
 
     if init.lower() == "custom":
         if U_0 is None or V_0 is None:
@@ -66,7 +70,14 @@ def compute_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8,
     ``group`` (extension): a torch.distributed process group -- `data` and `U_in` are then THIS RANK'S row block of a
     row-sharded problem (contiguous blocks, nn_fac_amd.dist.shard_rows), `V_in` is replicated; the Gram / cross terms, the
     stopping scalars and the cost are all-reduced over the group (RCCL over xGMI) and every rank returns its
-    block of U, the whole V and the global costs (start values: nn_fac_amd.dist.sharded_random_init)."""
+    block of U, the whole V and the global costs (start values: nn_fac_amd.dist.sharded_random_init).
+    Sparse `data` (a scipy.sparse matrix, a torch sparse-CSR tensor) runs in nn_fac_amd.sparse_nmf, over its stored entries."""
+    if is_sparse(data):
+        from . import sparse_nmf
+        return sparse_nmf.compute_sparse_nmf(data, rank, U_in, V_in, n_iter_max=n_iter_max, tol=tol, update_rule=update_rule,
+                                             beta=beta, sparsity_coefficients=sparsity_coefficients, fixed_modes=fixed_modes,
+                                             normalize=normalize, verbose=verbose, return_costs=return_costs,
+                                             deterministic=deterministic, sweep_log=sweep_log, group=group)
     dev = device_of(data, U_in, V_in)
     eng = _engine.get_engine(dev)
     X = to_dev(data, dev)
@@ -96,6 +107,10 @@ def compute_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8,
 def one_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta,
                  sparsity_coefficients, fixed_modes, normalize, deterministic):
     """One pass of updates on U then V, then the cost (nmf.py:387-458).  Returns (U, V, cost)."""
+    if is_sparse(data):
+        from . import sparse_nmf
+        return sparse_nmf.one_sparse_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta, sparsity_coefficients,
+                                              fixed_modes, normalize, deterministic)
     dev = device_of(data, U_in, V_in)
     eng = _engine.get_engine(dev)
     X = to_dev(data, dev)

@@ -64,6 +64,15 @@
 //                                     boundary in floats; out64=1: the fp64 sums are asked for.  Answer: the "[nnf reduce] ..."
 //                                     line of that launch (NNF_REDUCE_DEBUG), or "status=<code>" (the argument checks of
 //                                     nnf_reduce_slabs_f32).
+//                        The CSR kernels' plan (k_sparse_plan.h), key=value only:
+//                          sparse <CUs> r= lens=<len0,len1,...> [ch=] [out=] [cost=] [ws=]     lens: the stored entries of every row
+//                                     (the tool forms rowptr and the chunk table from them with the header's own functions); ch:
+//                                     the chunk size (default: sparse_chunk_entries of the CU count and nnz); out / cost (default
+//                                     1 / 0): a component-major result / the fp64 cost is asked for (csr_xf: out=1 cost=0; csr_kl:
+//                                     any pair but 0 0); ws: free workspace bytes (default 1 GiB).  Answer: the "[nnf plan] csr_..."
+//                                     line of that call (csr_xf / csr_kl), then carved= (the bytes a cursor has handed out after the launcher's
+//                                     carves) and chunks=<row>:<first>:<end>,... (every chunk in chunk order, spans from
+//                                     sparse_chunk_span as the kernel takes them; "-" for none), or "status=<code>".
 //   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
 //                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
 //
@@ -75,6 +84,9 @@
 #include "k_mu_plan.h"
 #include "k_hals_plan.h"
 #include "k_simplex_plan.h"
+#include "k_sparse_plan.h"
+#include <string>
+#include <vector>
 
 static long long key_of(const char* rest, const char* key, long long dflt) {
     char pat[32];
@@ -171,6 +183,59 @@ static int answer_simplex(const char* line) {
     return 0;
 }
 
+static int answer_sparse(const char* line) {
+    int C = 0, used = 0;
+    if (sscanf(line, "%*s %d%n", &C, &used) != 1 || C < 1) return 2;
+    const char* rest = line + used;
+    const char* at = strstr(rest, " lens=");
+    if (!at) return 2;
+    std::vector<int64_t> rowptr(1, 0);
+    for (const char* q = at + 6; *q && !strchr(" \t\r\n", *q);) {
+        char* end = nullptr;
+        const long long len = strtoll(q, &end, 10);
+        if (end == q || len < 0) return 2;
+        rowptr.push_back(rowptr.back() + len);
+        q = *end == ',' ? end + 1 : end;
+    }
+    const int64_t nrows = (int64_t)rowptr.size() - 1, nnz = rowptr.back();
+    const long long r = key_of(rest, "r", 0), ws = key_of(rest, "ws", 1024ll << 20);
+    const int ch = (int)key_of(rest, "ch", sparse_chunk_entries(C, nnz));
+    const bool out = key_of(rest, "out", 1) != 0, cost = key_of(rest, "cost", 0) != 0;
+    // (the argument checks of csr_args_ok, k_sparse.hip)
+    if (nrows < 1 || r < 1 || !sparse_chunk_ok(ch) || (!out && !cost)) {
+        printf("status=%d\n", NNF_ERR_ARG);
+        return 0;
+    }
+    // the chunk table as the caller builds it: rowchunk = exclusive prefix sum of the rows' chunk counts, chunk -> row
+    std::vector<int64_t> rowchunk(1, 0);
+    std::vector<int> chunk_row;
+    for (int64_t i = 0; i < nrows; ++i) {
+        const int64_t k = sparse_chunks_of_row(rowptr[i + 1] - rowptr[i], ch);
+        rowchunk.push_back(rowchunk.back() + k);
+        chunk_row.insert(chunk_row.end(), (size_t)k, (int)i);
+    }
+    const int64_t nchunks = rowchunk.back();
+    const sparse_plan p = sparse_make_plan((int)(r > 1000000 ? 1000000 : r), nrows, nchunks, out, cost, (size_t)ws);
+    if (p.status != NNF_OK) {
+        printf("status=%d\n", p.status);
+        return 0;
+    }
+    nnf_ws_cursor cur(nullptr, (size_t)ws);      // the launcher's carves, in its order
+    if (nchunks > 0 && out) cur.reserve(p.part_bytes);
+    if (nchunks > 0 && cost) cur.reserve(p.cost_bytes);
+    std::string chunks;
+    for (int64_t c = 0; c < nchunks; ++c) {
+        const int row = chunk_row[(size_t)c];
+        const sparse_span sp = sparse_chunk_span(rowptr[row], rowptr[row + 1], c - rowchunk[row], ch, nnz);
+        char one[96];
+        snprintf(one, sizeof one, "%s%d:%lld:%lld", c ? "," : "", row, (long long)sp.first, (long long)sp.end);
+        chunks += one;
+    }
+    std::string more = " carved=" + std::to_string(cur.off) + " chunks=" + (nchunks ? chunks : std::string("-"));
+    sparse_report(stdout, out && !cost ? "csr_xf" : "csr_kl", (int)r, nrows, nnz, nchunks, ch, p, more.c_str());
+    return 0;
+}
+
 static int answer_reduce(const char* line) {
     const char* rest = line + strcspn(line, " \t");
     const long long rows = key_of(rest, "rows", 0), cols = key_of(rest, "cols", 0), nslab = key_of(rest, "nslab", 0);
@@ -190,13 +255,20 @@ static int answer_reduce(const char* line) {
 
 int main(int argc, char** argv) {
     if (argc > 1 && strcmp(argv[1], "shm") == 0) return print_shm();
-    char line[512], name[32], more[192];
+    char line[4096], name[32], more[192];
     while (fgets(line, sizeof line, stdin)) {
         long long C, m, n, r, ld, ws;
         double beta;
         int used = 0;
         if (sscanf(line, "%31s", name) == 1 && strcmp(name, "reduce") == 0) {
             answer_reduce(line);
+            continue;
+        }
+        if (sscanf(line, "%31s", name) == 1 && strcmp(name, "sparse") == 0) {
+            if (answer_sparse(line) != 0) {
+                fprintf(stderr, "nnf_plan: bad case line: %s", line);
+                return 2;
+            }
             continue;
         }
         if (sscanf(line, "%31s", name) == 1 && (strncmp(name, "hals", 4) == 0 || strcmp(name, "simplex") == 0)) {
