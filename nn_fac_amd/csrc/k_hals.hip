@@ -289,7 +289,7 @@ static int generic_per_cu(int mode, hals_layout l, int r, size_t lds, int cap) {
     return c - 1;
 }
 static const hals_occupancy hals_device_occupancy = {nnf_hals_wave_per_cu, nnf_hals_quad_per_cu, nnf_hals_fast_per_cu,
-                                                     nnf_hals_mfma_per_cu, generic_per_cu};
+                                                     nnf_hals_mfma_per_cu, generic_per_cu, nnf_hals_comm_per_cu};
 
 // Checks the arguments, reads NNF_HALS_FORCE, makes the plan, reports it, takes the workspace, runs the launches in front of the
 // sweep, launches the layout's kernel and, in mode 1, sums the per-workgroup partials of every sweep.
@@ -373,6 +373,8 @@ static int hals_entry(nnf_ctx* ctx, hals_request q, hipStream_t st) {
         case HL_QUAD: rc = nnf_hals_quad_launch(p.ch, a, Gp, p.nblocks, st); break;
         case HL_MFMA: rc = nnf_hals_mfma_launch(p.RP, q.UtU, q.ldg, Gm, a, p.nblocks, st); break;
         case HL_LANE_RES:
+            if (p.comm) { rc = nnf_hals_comm_launch(p.RP, a, p.nblocks, st); break; }
+            [[fallthrough]];
         case HL_LANE_STREAM: rc = nnf_hals_fast_launch(p.RP, p.layout == HL_LANE_RES, a, p.nblocks, st); break;
         default:
             hipLaunchKernelGGL(generic_kernel(q.mode, p.layout), dim3(p.nblocks), dim3(128), p.lds, st, q.UtM, q.ldm, Gp, dinv, RS, q.V,

@@ -189,7 +189,8 @@ __device__ __forceinline__ bool hals_collect(const hals_sync& sy, int s, int nbl
 // granule 0 and ignore it.  The consumer waits with vmcnt(0) (hals_mid_wait) before it looks at the registers.
 #ifndef HALS_DBG
 #define HALS_DBG 0             // timing-only ablations of the exchange (tools/probes/exchange_cost_probe.py): 1 granules taken as they
-#endif                         // come (no tag wait), 2 no collect at all, 4 no publish either; decisions are ignored then
+#endif                         // come (no tag wait), 2 no collect at all, 4 no publish either, 8 (lane kernel, resident) no block sum
+                               // and no barrier either; decisions are ignored then
 #ifndef HALS_LATE_ISSUE
 #define HALS_LATE_ISSUE 1      // 0: the exchange prefetch goes out before the sweep (A/B builds)
 #endif
@@ -418,6 +419,11 @@ static inline int hals_per_cu(hipError_t e, int nb, int cap) {
 // co-resident), else the streaming form strides over column sets.  Lane cap: 3 workgroups per CU.
 int nnf_hals_fast_per_cu(int RP, bool resident);
 int nnf_hals_fast_launch(int RP, bool resident, const hals_args& a, int nblocks, hipStream_t);
+
+// k_hals_comm.hip: the resident lane solve (mode 0) of padded ranks 40 .. 52 in workgroups of 8 compute waves + 1 communication
+// wave, 512 columns each, at most one per CU (0: the instance does not fit, or no such rank)
+int nnf_hals_comm_per_cu(int RP);
+int nnf_hals_comm_launch(int RP, const hals_args& a, int nblocks, hipStream_t);
 
 // k_hals_wave.hip: one wave per column (lane = row), push form of the sweep; solve mode from the first sweep, r <= 128
 int nnf_hals_wave_per_cu(int r, int cpw, int nw);

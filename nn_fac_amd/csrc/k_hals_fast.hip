@@ -2,6 +2,7 @@
 // Compiled once per part, -DHALS_PART=p (k_parts.h; each part instantiates the padded ranks HALS_TABLE gives it), so the parts build
 // in parallel.  See k_hals.hip for the algorithm, the grid-exchange protocol and the entry points.
 #include "k_hals_common.h"
+#include "k_hals_lane_sweep.h"   // the row-split sweep of ranks 33 .. 64 (shared with k_hals_comm.hip)
 #include "k_parts.h"
 
 #ifndef HALS_PART
@@ -10,9 +11,6 @@
 #define NNF_PART HALS_PART
 
 NNF_BUILD_FLAGS(NNF_CAT(k_hals_fast, HALS_PART), "HALS_LATE_ISSUE=" NNF_STR(HALS_LATE_ISSUE) " HALS_MID_AT(R)=" NNF_STR(HALS_MID_AT(R)) " HALS_DBG=" NNF_STR(HALS_DBG))
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 // Scalar (SMEM) loads issued by hand.  SMEM returns out of order, so the only usable wait is lgkmcnt(0) and hipcc cannot
 // software-pipeline such loads itself (it sinks every load to its use: one exposed scalar-cache round trip per 16 values).
@@ -26,133 +24,6 @@ typedef float f32x8 __attribute__((ext_vector_type(8)));
                  : "=&s"(d0), "=&s"(d1), "=&s"(dd) : "s"(base), "i"((off) * 4), "i"((off) * 4 + 64), "i"((doff) * 4))
 #define NNF_SWAIT2(d0, d1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(d0), "+s"(d1))
 #define NNF_SWAIT3(d0, d1, dd) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(d0), "+s"(d1), "+s"(dd))
-
-// ---- scalar-cache operand buffers -------------------------------------------------------------------------
-// W floats of a Gram row held in SGPRs as 16/8/4-dword pieces (s_load_dwordx16/x8/x4).  Scalar loads return out of
-// order, so the only usable wait is lgkmcnt(0): the schedule below is built so that everything outstanding at a wait
-// was issued at least ~half a row of FMAs earlier (tools/smem_probe.hip: ~60 ns for two x16 hits, ~105 ns from L2).
-template <int W>
-struct sgbuf {
-    f32x16 a, b;
-    f32x8 q;
-    f32x4 r;
-};
-template <int W, bool TIED>
-__device__ __forceinline__ void sg_issue(sgbuf<W>& d, uint64_t base, int off) {
-    constexpr int N16 = W / 16, N8 = (W % 16) / 8, N4 = (W % 8) / 4;
-    static_assert(W % 4 == 0 && N16 <= 2, "piece decomposition");
-    // TIED: the destination registers are the ones that held the previous row's piece (consumed just above)
-    if constexpr (TIED) {
-        if constexpr (N16 >= 1) asm volatile("s_load_dwordx16 %0, %1, %2" : "+s"(d.a) : "s"(base), "i"(off * 4));
-        if constexpr (N16 >= 2) asm volatile("s_load_dwordx16 %0, %1, %2" : "+s"(d.b) : "s"(base), "i"(off * 4 + 64));
-        if constexpr (N8 == 1) asm volatile("s_load_dwordx8 %0, %1, %2" : "+s"(d.q) : "s"(base), "i"(off * 4 + 64 * N16));
-        if constexpr (N4 == 1) asm volatile("s_load_dwordx4 %0, %1, %2" : "+s"(d.r) : "s"(base), "i"(off * 4 + 64 * N16 + 32 * N8));
-    } else {
-        if constexpr (N16 >= 1) asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(d.a) : "s"(base), "i"(off * 4));
-        if constexpr (N16 >= 2) asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(d.b) : "s"(base), "i"(off * 4 + 64));
-        if constexpr (N8 == 1) asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(d.q) : "s"(base), "i"(off * 4 + 64 * N16));
-        if constexpr (N4 == 1) asm volatile("s_load_dwordx4 %0, %1, %2" : "=s"(d.r) : "s"(base), "i"(off * 4 + 64 * N16 + 32 * N8));
-    }
-}
-// after s_waitcnt: tell the compiler the pieces now hold their loaded values (nothing may be read above this point)
-template <int W>
-__device__ __forceinline__ void sg_arrived(sgbuf<W>& d) {
-    constexpr int N16 = W / 16, N8 = (W % 16) / 8, N4 = (W % 8) / 4;
-    if constexpr (N16 >= 1) asm volatile("" : "+s"(d.a));
-    if constexpr (N16 >= 2) asm volatile("" : "+s"(d.b));
-    if constexpr (N8 == 1) asm volatile("" : "+s"(d.q));
-    if constexpr (N4 == 1) asm volatile("" : "+s"(d.r));
-}
-template <int W>
-__device__ __forceinline__ f32x2 sg_pair(const sgbuf<W>& d, int p) {   // floats 2p, 2p+1 of the buffer
-    constexpr int N16 = W / 16, N8 = (W % 16) / 8;
-    const int j = 2 * p;
-    if (N16 >= 1 && j < 16) return f32x2{d.a[j], d.a[j + 1]};
-    if (N16 >= 2 && j < 32) return f32x2{d.b[j - 16], d.b[j - 15]};
-    const int j2 = j - 16 * N16;
-    if (N8 == 1 && j2 < 8) return f32x2{d.q[j2], d.q[j2 + 1]};
-    const int j3 = j2 - 8 * N8;
-    return f32x2{d.r[j3], d.r[j3 + 1]};
-}
-
-// One Gauss-Seidel sweep for 32 < R <= 64 with the UtM column resident.  Operands are pre-scaled by 1/diag:
-// Gs = diag(1/diag) UtU (rows with a zero diagonal are all zero) and b = (UtM - sp)/diag, so a row update is
-//     x = b[k] - Gs[k,:].v ;  d = max(x, -v[k]) ;  v[k] += d ;  nodelta += d*d          (nnls.py:162-170)
-// i.e. 6 vector instructions after the R/2 packed FMAs of the dot product.
-// A Gram row is split into X = columns [0, XW) and Y = columns [XW, XW+24).  Y is double-buffered and fetched a whole
-// row ahead; X is single-buffered and refilled for the next row as soon as its FMAs have issued, i.e. before the Y
-// part and the row bookkeeping -- so the single lgkmcnt(0) per row finds both in (or nearly in) the registers.
-// GUARD: some Gram diagonal is zero (rare).  Such a row must be left alone whatever it holds (nnls.py:160): d is
-// multiplied by the row's nz flag (0/1) fetched with the Y part.  Without GUARD there is no per-row flag at all.
-// GUARD is also the variant that keeps non-finite values as np.maximum does (nnfac_hip.h "Non-finite operands"): v_max_f32
-// returns the operand that is not NaN, so without GUARD a NaN x writes a clean v[k] = 0; with it d is a compare-and-select
-// (two instructions, NaN kept) and the nz flag is applied with v_mul_legacy_f32 (0 * anything = 0: a skipped row stays put next
-// to an Inf or NaN elsewhere in the column).  The streaming kernel always runs with GUARD; the resident one where a Gram
-// diagonal is zero or an operand is not finite (see nnf_hals_kernel).
-template <int R, bool GUARD, class MID>
-__device__ __forceinline__ float hals_sweep_column_xy(f32x2 (&v2)[R / 2], const float (&b)[R], const float* __restrict__ Gs,
-                                                      const float* __restrict__ nzp, const MID& mid) {
-    constexpr int RS = 64, P = R / 2, YW = 24, XW = (R - YW + 3) & ~3, XP = XW / 2;
-    static_assert(YW == 24, "the Y issue statement below is written for x16 + x8");
-    static_assert(R > 32 && R <= 64 && R % 2 == 0 && XW + YW <= RS && XW >= 8, "row split");
-    const uint64_t base = (uint64_t)Gs, nzb = (uint64_t)nzp;
-    sgbuf<XW> X;
-    sgbuf<YW> Y[2];
-    f32x2 dv[2];   // (1/diag, nz) pair of the row (GUARD only)
-    float nd = 0.f;
-    sg_issue<XW, false>(X, base, 0);
-    sg_issue<YW, false>(Y[0], base, XW);
-    if constexpr (GUARD) asm volatile("s_load_dwordx2 %0, %1, %2" : "=s"(dv[0]) : "s"(nzb), "i"(0));
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int cur = k & 1, nxt = cur ^ 1;
-        if (k == HALS_MID_AT(R)) mid();
-        if constexpr (GUARD) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(dv[cur]));
-        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        sg_arrived<XW>(X);
-        sg_arrived<YW>(Y[cur]);
-        if (k + 1 < R) {   // one statement, so that all of it is issued here and not wherever the scheduler sinks it
-            if constexpr (GUARD)
-                asm volatile("s_load_dwordx16 %0, %3, %4\n\ts_load_dwordx8 %1, %3, %5\n\ts_load_dwordx2 %2, %6, %7"
-                             : "=&s"(Y[nxt].a), "=&s"(Y[nxt].q), "=&s"(dv[nxt])
-                             : "s"(base), "i"(((k + 1) * RS + XW) * 4), "i"(((k + 1) * RS + XW + 16) * 4), "s"(nzb),
-                               "i"(8 * (k + 1)));
-            else
-                asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dwordx8 %1, %2, %4"
-                             : "=&s"(Y[nxt].a), "=&s"(Y[nxt].q)
-                             : "s"(base), "i"(((k + 1) * RS + XW) * 4), "i"(((k + 1) * RS + XW + 16) * 4));
-        }
-        f32x2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};   // two chains are enough: the other wave of the SIMD fills the FMA latency
-#pragma unroll
-        for (int p = 0; p < XP; ++p) {
-            const f32x2 g = sg_pair<XW>(X, p);
-            if (p & 1) a1 = __builtin_elementwise_fma(g, v2[p], a1);
-            else a0 = __builtin_elementwise_fma(g, v2[p], a0);
-        }
-        asm volatile("" : "+v"(a0), "+v"(a1));   // X is consumed: its registers may be refilled
-        if (k + 1 < R) sg_issue<XW, true>(X, base, (k + 1) * RS);
-#pragma unroll
-        for (int p = XP; p < P; ++p) {
-            const f32x2 g = sg_pair<YW>(Y[cur], p - XP);
-            if (p & 1) a1 = __builtin_elementwise_fma(g, v2[p], a1);
-            else a0 = __builtin_elementwise_fma(g, v2[p], a0);
-        }
-        const f32x2 a = a0 + a1;
-        const float vk = v2[k / 2][k & 1];
-        const float x = b[k] - (a[0] + a[1]);
-        float dl;
-        if constexpr (GUARD) {
-            const float sel = !(x < -vk) ? x : -vk;   // np.maximum(x, -v[k]), NaN included
-            asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(dl) : "s"(dv[cur][1]), "v"(sel));
-        } else {   // max(x, -v[k]) in one instruction (fmaxf adds a canonicalising max for the negated operand); finite operands only
-            asm("v_max_f32 %0, %1, -%2" : "=v"(dl) : "v"(x), "v"(vk));
-        }
-        v2[k / 2][k & 1] = vk + dl;
-        nd = fmaf(dl, dl, nd);
-        asm volatile("" : "+v"(nd));  // finish this row's bookkeeping here (otherwise it is sunk to the end of the sweep)
-    }
-    return nd;
-}
 
 // One Gauss-Seidel sweep (nnls.py:158-170) over the column held in v2 = {(v[0],v[1]), (v[2],v[3]), ...}.
 //   x     = (UtM[k] - UtU[k,:].v - sp) / UtU[k,k]
@@ -273,7 +144,8 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
     bool plain = false;   // wave-uniform
     auto sweep = [&](int voff, const auto& mid) -> float {
         if constexpr (XY) {
-            return plain ? hals_sweep_column_xy<RP, false>(v2, b, a.Gs, a.dinv, mid) : hals_sweep_column_xy<RP, true>(v2, b, a.Gs, a.dinv, mid);
+            return plain ? hals_sweep_column_xy<RP, false>(v2, hals_b_regs<RP>{b}, a.Gs, a.dinv, mid)
+                         : hals_sweep_column_xy<RP, true>(v2, hals_b_regs<RP>{b}, a.Gs, a.dinv, mid);
         } else {
             return hals_sweep_column<RP, KEEPB>(v2, b, rb, voff, ldm4, a.Gp, a.sp, mid);
         }
@@ -367,13 +239,14 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
         bool merged = false;    // SPEC: this sweep's block sum and the collect of sweep s-1 share one barrier
         double tot_m = 0.0;
         if constexpr (RES && SPEC) {
-            if (a.mode == 0 && s >= 2 && !(HALS_DBG & 6)) {
+            if (a.mode == 0 && s >= 2 && !(HALS_DBG & 14)) {
                 ok = hals_sum_collect1<256>(a.sy, nd, bs, s - 1, nblocks, tot_m, red2[s & 1][0], red2[s & 1][1], &lds_flag, pf);
                 merged = true;
             }
         }
         if (!merged) {
-            if constexpr (RES) bs = hals_block_sum1<256>(nd, red2[s & 1][0]);   // valid in every thread; one barrier
+            if constexpr (RES && (HALS_DBG & 8) != 0) bs = nd;   // timing only: no wave sum, no barrier
+            else if constexpr (RES) bs = hals_block_sum1<256>(nd, red2[s & 1][0]);   // valid in every thread; one barrier
             else bs = nnf_block_sum_f64(nd, red);
         }
         if (a.mode == 1) {
@@ -389,9 +262,9 @@ __global__ __launch_bounds__(256, (RP > 104 ? 1 : 2)) void nnf_hals_kernel(hals_
             done = s;
             continue;
         }
-        if (!(HALS_DBG & 4)) hals_publish(a.sy, s, nblocks, bs);
+        if (!(HALS_DBG & 12)) hals_publish(a.sy, s, nblocks, bs);
         const int c = SPEC ? s - 1 : s;         // sweep whose global sum is examined now
-        if (c >= 1 && !(HALS_DBG & 6)) {
+        if (c >= 1 && !(HALS_DBG & 14)) {
             double tot;
             if (merged) tot = tot_m;
             else if constexpr (RES) ok = hals_collect1(a.sy, c, nblocks, tot, red2[s & 1][1], &lds_flag, pf);

@@ -27,7 +27,8 @@ struct hals_shape {
     bool snapshots;                // snapshots were asked for
     // NNF_HALS_FORCE pins the layout (tests run every kernel on the same fixtures); its first letter counts (0: not set):
     //   l lane only;  q no wave, no mfma, quad beyond 32768 columns;  w no mfma, a solve wave cannot hold is refused;
-    //   m mfma ahead of wave and quad where it covers the padded rank
+    //   m mfma ahead of wave and quad where it covers the padded rank;
+    //   c lane only, and the resident solve of ranks 33 .. 52 in its 576-thread form (hals_plan::comm) at any number of columns
     char force;
 };
 
@@ -39,6 +40,7 @@ struct hals_plan {
     size_t lds = 0;                // generic: dynamic LDS bytes
     bool hadamard = false, copy = false, prep = true;   // launches in front of the sweep
     bool gs = false;               // lane, mfma: the row-scaled Gram next to the padded one
+    bool comm = false;             // lane-resident: the 576-thread form (k_hals_comm.hip: 512 columns per workgroup, one per CU)
     size_t gram_floats = 0, mfma_floats = 0, snap_floats = 0;   // workspace
 };
 
@@ -50,6 +52,7 @@ struct hals_occupancy {
     int (*lane)(int RP, bool resident);
     int (*mfma)(int RP);
     int (*generic)(int mode, hals_layout layout, int r, size_t lds_bytes, int cap);   // cap: at most so many (0: no cap)
+    int (*lane_comm)(int RP);      // the 576-thread form of the resident lane solve
 };
 
 static inline int pick_rp(int r) {
@@ -116,6 +119,9 @@ static inline size_t nnf_hals_mfma_resid_floats(int RP, int64_t ncols) {
 constexpr size_t HALS_GENERIC_LDS_MAX = (size_t)150 * 1024;   // columns in LDS up to here
 constexpr size_t HALS_GENERIC_SHM_FIXED = 16 + 3 * 2 * 8 + 64;
 
+// ---- k_hals_comm.hip: granules (one per 256 columns) its communication wave collects, 8 pairs per lane ----
+constexpr int HALS_COMM_MAX_GRANULES = 512;
+
 static inline int64_t hals_cap(int cus, int per_cu) {   // workgroups that stay resident at per_cu per CU
     const int64_t c = (int64_t)per_cu * cus;
     return c < NNF_HALS_MAX_BLOCKS ? c : NNF_HALS_MAX_BLOCKS;
@@ -143,13 +149,13 @@ static inline hals_plan hals_make_plan(int cus, const hals_occupancy& occ, const
     p.RP = pick_rp(r);
     // many columns at ranks 64..100: the push form on the matrix cores; below rank 64 a k-block has too few MFMAs to cover its
     // own gather -> update -> scatter chain (measured: 9.7-10.6 against 9.4-9.6 us per sweep at rank 50)
-    const bool mfma = !generic && sweeps && force != 'l' && force != 'q' && force != 'w' && nnf_hals_mfma_supported(p.RP) &&
+    const bool mfma = !generic && sweeps && force != 'l' && force != 'c' && force != 'q' && force != 'w' && nnf_hals_mfma_supported(p.RP) &&
                       (force == 'm' || (p.RP >= 64 && n > 32768));
     const bool pin_mfma = force == 'm' && mfma;
 
     // few columns, a persistent solve from its first sweep: one wave per column, 1 or 2 columns per compute wave
     const bool wave_shape = !generic && q.mode == 0 && q.sweep0 == 0;
-    if (wave_shape && force != 'l' && force != 'q' && !pin_mfma) {
+    if (wave_shape && force != 'l' && force != 'c' && force != 'q' && !pin_mfma) {
         for (int cpw = 1; cpw <= 2; ++cpw) {
             int nw = 0;
             const int need = nnf_hals_wave_grid(n, cpw, &nw);
@@ -171,7 +177,7 @@ static inline hals_plan hals_make_plan(int cus, const hals_occupancy& occ, const
     // few columns (<= 32768: at most two waves per SIMD): four lanes per column, 16 columns per workgroup.  Its buffer
     // offsets reach row r + 15 of V, UtM and the start values in 32 bits: start values beyond that are copied into V first.
     auto quad_32bit = [&](int64_t ld) { return (int64_t)(r + 16) * ld * 4 < (int64_t)0x7fff0000; };
-    if (!generic && force != 'l' && !pin_mfma && (n <= 32768 || force == 'q') && quad_32bit(q.ldv > q.ldm ? q.ldv : q.ldm)) {
+    if (!generic && force != 'l' && force != 'c' && !pin_mfma && (n <= 32768 || force == 'q') && quad_32bit(q.ldv > q.ldm ? q.ldv : q.ldm)) {
         const int ch = (r + 3) / 4, pc = occ.quad(ch);
         const int64_t need = nnf_cdiv(n, 16);
         if (pc > 0 && need <= hals_cap(cus, pc)) {
@@ -240,6 +246,15 @@ static inline hals_plan hals_make_plan(int cus, const hals_occupancy& occ, const
     if (lane_pc < 1) return hals_refuse(p, NNF_ERR_LAUNCH);
     if (lane_fits) {
         p.layout = HL_LANE_RES, p.nblocks = (int)need, p.per_cu = lane_pc;
+        // A solve of the row-split ranks whose 256-thread workgroups outnumber the CUs has two waves on some SIMDs whatever the
+        // layout: 8 compute waves per CU are no slower, and a ninth wave takes the stopping exchange off them (k_hals_comm.hip;
+        // its communication wave sums at most HALS_COMM_MAX_GRANULES granules, one per 256 columns as here).
+        // NNF_HALS_FORCE: `lane` keeps the 256-thread workgroups, `c` takes the new form at any number of columns.
+        if (q.mode == 0 && p.gs && need <= HALS_COMM_MAX_GRANULES && force != 'l' && (force == 'c' || need > cus)) {
+            const int pc = occ.lane_comm ? occ.lane_comm(p.RP) : 0;
+            const int64_t need2 = nnf_cdiv(n, 512);
+            if (pc > 0 && need2 <= hals_cap(cus, pc)) p.comm = true, p.nblocks = (int)need2, p.per_cu = pc;
+        }
         return p;
     }
     // more columns than stay resident: the streaming form strides over column sets (no snapshots)
@@ -253,9 +268,9 @@ static inline hals_plan hals_make_plan(int cus, const hals_occupancy& occ, const
 // the NNF_HALS_DEBUG line of a call (tests/test_gpu_hals_plans.py keys on it)
 static inline void hals_report(FILE* f, const hals_shape& q, const hals_plan& p, const char* more = "") {
     fprintf(f, "[nnf hals] r=%d ncols=%lld mode=%d sweeps=%d sweep0=%d flags=%u -> %s grid=%d per_cu=%d cpw=%d nw=%d ch=%d "
-            "RP=%d gs=%d lds=%zu hadamard=%d copy=%d prep=%d err=%d%s\n", q.r, (long long)q.ncols, q.mode, q.nsweeps, q.sweep0,
+            "RP=%d gs=%d lds=%zu hadamard=%d copy=%d prep=%d err=%d comm=%d%s\n", q.r, (long long)q.ncols, q.mode, q.nsweeps, q.sweep0,
             q.flags, hals_layout_name[p.layout], p.nblocks, p.per_cu, p.cpw, p.nw, p.ch, p.RP, p.gs, p.lds, p.hadamard, p.copy,
-            p.prep, p.err, more);
+            p.prep, p.err, p.comm, more);
 }
 
 // Columns a persistent launch keeps resident at rank r (nnf_hals_resident_columns): the resident lane kernel, 256 columns per

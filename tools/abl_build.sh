@@ -9,6 +9,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/nn_fac_amd/csrc
 mkdir -p $R/tools/abl
 /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-value -Wno-unused-result -mllvm -pragma-unroll-threshold=4000000 "$@" -c $C/$SRC -o /tmp/abl_$TAG.o
-OBJS=$(make -s -C $C -pn 2>/dev/null | grep '^OBJS' | head -1 | sed 's/^OBJS *= *//' | tr ' ' '\n' | grep -v "^$" | sed "s#^\$(BUILD)#$C/build#;s#^build/#$C/build/#" | grep -v "/$REPL\$" | tr '\n' ' ')
+# every object of the product's build (the Makefile links exactly what it compiles into build/) but the one replaced
+OBJS=$(ls $C/build/*.o | grep -v "/$REPL\$" | tr '\n' ' ')
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/tools/abl/libnnfac_$TAG.so $OBJS /tmp/abl_$TAG.o -ldl 2>&1 | tail -3
 echo built tools/abl/libnnfac_$TAG.so

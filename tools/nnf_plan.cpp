@@ -131,7 +131,8 @@ static int pc_mfma(int) { return hals_figure("pc_mfma"); }
 static int pc_generic(int, hals_layout l, int, size_t, int) {
     return hals_figure(l == HL_GENERIC_LDS ? "pc_generic_lds" : l == HL_GENERIC_BIG ? "pc_generic_big" : "pc_generic_gcol");
 }
-static const hals_occupancy hals_line_occupancy = {pc_wave, pc_quad, pc_lane, pc_mfma, pc_generic};
+static int pc_lane_comm(int) { return hals_figure("pc_lane_comm"); }
+static const hals_occupancy hals_line_occupancy = {pc_wave, pc_quad, pc_lane, pc_mfma, pc_generic, pc_lane_comm};
 
 static int answer_hals(const char* name, const char* line) {
     int C = 0, used = 0;
