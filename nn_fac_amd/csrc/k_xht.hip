@@ -12,6 +12,83 @@ NNF_BUILD_FLAGS(k_xht, "XHT_ABL=" NNF_STR(XHT_ABL))
 //   workgroup = 256 rows of X (wave w: rows 64w..64w+63 as four 16-row N tiles), k runs over the n columns.
 //   B operand lane (ii = l&15, g = l>>4) of tile nt, k-group t: float4 X[i0w+16nt+ii][64q+16t+4g .. +3].
 // =========================================================================================================
+// One 64-deep chunk of the contraction: the MFMAs of chunk q on its LDS image `img`, the leftover rank rows on the VALU pipe
+// between them, X of chunk q + 1 reloaded in place behind the k-group that frees its registers and the image of chunk q + 1
+// stored into `img_next` behind the last k-group.  RAGGED: the chunk may reach past column n -- the components at and beyond n
+// are masked (never multiply a staged zero by out-of-row data: the allocated row padding may hold NaN).  Only the last chunk of
+// a row can be that; the body of the chunk loop is the unmasked form: no compare, select or branch between its MFMAs.
+template <int MT, int REM, bool VEC, int NT, bool RAGGED>
+__device__ __forceinline__ void nnf_xht_chunk(const f32x4* __restrict__ img, f32x4* __restrict__ img_next, int q, int64_t n,
+                                              const float* __restrict__ V, int64_t ldv, int r, int a_vec_ok, rsrc_t rs, int voff,
+                                              int ldx4, int lane, int g, f32x4 (&acc)[MT][NT], f32x4 (&xb)[4][NT],
+                                              float (&ev)[REM > 0 ? REM : 1][NT], f32x4 (&areg)[MT + (REM > 0 ? 1 : 0)]) {
+    constexpr int MTA = MT + (REM > 0 ? 1 : 0);
+    stageA_load<MTA>(V, ldv, r, n, 64 * (int64_t)(q + 1), a_vec_ok, areg);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        f32x4 af[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) af[mt] = img[(mt * 4 + t) * 64 + lane];
+        f32x4 uv[REM > 0 ? REM : 1];   // V[16MT+rr][64q+16t+4g+c], c = 0..3
+        if constexpr (REM > 0 && XHT_ABL != 3) {
+#pragma unroll
+            for (int rr = 0; rr < REM; ++rr) uv[rr] = img[(MT * 4 + t) * 64 + 16 * g + rr];
+        }
+        f32x4 xs[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) xs[nt] = xb[t][nt];
+        if constexpr (RAGGED && XHT_ABL != 5) {
+            const int64_t nrem = n - (64 * (int64_t)q + 16 * t + 4 * g);
+            if (nrem < 4) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (c >= nrem) xs[nt][c] = 0.f;
+            }
+        }
+        // component by component: the rank tiles on MFMA, then the leftover rows' FMAs of the same component (every chain of
+        // ev still runs t, then c)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+#if XHT_ABL == 2
+                    if (mt == 0) acc[0][nt][c] += af[0][c] * xs[nt][c];
+#else
+                    acc[mt][nt] = MFMA16(af[mt][c], xs[nt][c], acc[mt][nt]);
+#endif
+                }
+            if constexpr (REM > 0 && XHT_ABL != 3) {
+#pragma unroll
+                for (int rr = 0; rr < REM; ++rr)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) ev[rr][nt] = fmaf(uv[rr][c], xs[nt][c], ev[rr][nt]);
+            }
+        }
+        // finish the chains HERE: left alone, the scheduler sinks them (and the X registers they read) to the barrier
+        if constexpr (REM > 0 && XHT_ABL != 3) {
+#pragma unroll
+            for (int rr = 0; rr < REM; ++rr)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) asm volatile("" : "+v"(ev[rr][nt]));
+        }
+#if XHT_ABL != 1
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) xb[t][nt] = nnf_bload4<VEC>(rs, voff, nt * 16 * ldx4 + 256 * (q + 1) + 64 * t);
+#endif
+        // keep every k-group's reloads and leftover-row FMAs inside the group (as in k_xty.hip; without the fence the four-tile
+        // forms without leftover rows come out slower, DESIGN.md section 7 "X H^T chunk loop")
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#if XHT_ABL != 4
+    stageA_store<MTA>(img_next, areg);
+    __syncthreads();
+#endif
+}
+
 // NT = 16-row tiles per wave (a workgroup covers 64*NT rows starting at row0).
 template <int MT, int REM, bool VEC, int NT>
 __device__ __forceinline__ void nnf_xht_body(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
@@ -31,6 +108,8 @@ __device__ __forceinline__ void nnf_xht_body(const float* __restrict__ X, int64_
     const int voff = (int)(((int64_t)ii * ldx + 4 * g) * 4);
     const int ldx4 = (int)(ldx * 4);
     const int nchunk = q1 >= 0 ? q1 : (int)((n + 63) >> 6);
+    // chunks [q0, nwhole) lie wholly inside n; the one behind them, where the range holds it, is the ragged end of the row
+    const int nwhole = (n >> 6) < nchunk ? (int)(n >> 6) : nchunk;
 
     f32x4 acc[MT][NT];
 #pragma unroll
@@ -50,64 +129,31 @@ __device__ __forceinline__ void nnf_xht_body(const float* __restrict__ X, int64_
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) xb[t][nt] = nnf_bload4<VEC>(rs, voff, nt * 16 * ldx4 + 256 * q0 + 64 * t);
-    stageA_store<MTA>(ldsA[q0 & 1], areg);
+    stageA_store<MTA>(ldsA[0], areg);
     __syncthreads();
 
-    for (int q = q0; q < nchunk; ++q) {
-        const f32x4* img = ldsA[q & 1];
-        stageA_load<MTA>(V, ldv, r, n, 64 * (int64_t)(q + 1), a_vec_ok, areg);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x4 af[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) af[mt] = img[(mt * 4 + t) * 64 + lane];
-            // ragged k tail: never multiply a staged zero by out-of-row data
-#if XHT_ABL != 5
-            const int64_t nrem = n - (64 * (int64_t)q + 16 * t + 4 * g);
-            if (nrem < 4) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (c >= nrem) xb[t][nt][c] = 0.f;
-            }
-#endif
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-#if XHT_ABL == 2
-                        if (mt == 0) acc[0][nt][c] += af[0][c] * xb[t][nt][c];
-#else
-                        acc[mt][nt] = MFMA16(af[mt][c], xb[t][nt][c], acc[mt][nt]);
-#endif
-                    }
-            if constexpr (REM > 0 && XHT_ABL != 3) {
-#pragma unroll
-                for (int rr = 0; rr < REM; ++rr) {
-                    const f32x4 uv = img[(MT * 4 + t) * 64 + 16 * g + rr];   // V[16MT+rr][64q+16t+4g+c], c = 0..3
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        float e = ev[rr][nt];
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) e = fmaf(uv[c], xb[t][nt][c], e);
-                        ev[rr][nt] = e;
-                    }
-                }
-            }
-#if XHT_ABL != 1
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                xb[t][nt] = nnf_bload4<VEC>(rs, voff, nt * 16 * ldx4 + 256 * (q + 1) + 64 * t);
-#endif
+#define NNF_XHT_CHUNK(RAGGED, FROM, TO, Q) \
+    nnf_xht_chunk<MT, REM, VEC, NT, RAGGED>(ldsA[FROM], ldsA[TO], Q, n, V, ldv, r, a_vec_ok, rs, voff, ldx4, lane, g, acc, xb, ev, areg)
+    // the first chunk of the range sits in image 0
+    int q = q0, from = 0;
+    if constexpr (NT > 1) {
+        // two chunks per trip: each half names its LDS image as a constant
+        for (; q + 2 <= nwhole; q += 2) {
+            NNF_XHT_CHUNK(false, 0, 1, q);
+            NNF_XHT_CHUNK(false, 1, 0, q + 1);
         }
-#if XHT_ABL != 4
-        stageA_store<MTA>(const_cast<f32x4*>(ldsA[(q + 1) & 1]), areg);
-        __syncthreads();
-#endif
+        if (q < nwhole) {   // odd count of whole chunks
+            NNF_XHT_CHUNK(false, 0, 1, q);
+            ++q;
+            from = 1;
+        }
+    } else {
+        // the one-tile body of the k-split shares (a few chunks each, one at config B): one chunk per trip as before -- sixteen
+        // MFMAs per rank tile do not cover the loads of a trip whichever way it is unrolled
+        for (; q < nwhole; ++q, from ^= 1) NNF_XHT_CHUNK(false, from, from ^ 1, q);
     }
+    if (q < nchunk) NNF_XHT_CHUNK(true, from, from ^ 1, q);
+#undef NNF_XHT_CHUNK
 
     // epilogue: tile (mt, nt): out[16mt + 4g + reg][i0w + 16nt + ii]
 #pragma unroll
