@@ -570,6 +570,40 @@ int nnf_csr_kl_f32(nnf_ctx* ctx, const int64_t* rowptr, const int32_t* colidx, c
                    int64_t nnz, const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, const float* Own_n,
                    int64_t ldo_n, const float* Fn, int64_t ldn, int r, float* num, int64_t ldnum, double* cost_f64, void* stream);
 
+/* ---- sparse data: NTF on a COO tensor, over the stored entries only (nn_fac_amd/sparse_ntf.py) -----------------------------
+ * A tensor of order N = 3, 4 or 5 (every extent and nnz < 2^31) is held as N sorted copies of its canonical coordinate list
+ * (lexicographic order, no coordinate twice, stored zeros allowed), one per mode.  The copy of mode n is sorted by i_n with a
+ * stable sort, so that a slice keeps its entries in lexicographic order of the other modes; it is the CSR layout above with
+ * ng = N - 1 indices per entry:
+ *   ptr  int64 [extent + 1]   the role of rowptr: slice i of mode n owns the entries [ptr[i], ptr[i + 1]),
+ *   idx  int32 [ng][nnz]      planar: plane m holds the index of the m-th OTHER mode (increasing mode order) of every entry,
+ *   vals float [nnz],
+ * and the chunk table (rowchunk, chunk_row, nchunks, ch) of the CSR entries built from ptr.  The ng gathered factors are passed
+ * node-major as a HOST array of ng device pointers Fn[m] (extents[m] x ldn, one common pitch ldn >= r, a multiple of 4 floats,
+ * every base 16-byte aligned) in the order of the planes of idx.  Per stored entry x at p the kernels form
+ *   h = Fn[0][idx[0][p], :] .* Fn[1][idx[1][p], :] .* ...      (fp32, in that order)
+ * and leave each chunk's sums in the context workspace exactly as the CSR entries do; the same second kernel adds a slice's
+ * chunks in chunk order in fp64.  No atomics and no waiting between workgroups: two calls are bitwise equal.  The kernels hold
+ * every index they read from ptr, idx and the chunk table against the extents, nnz and nchunks (a table that does not belong to
+ * the tensor gives wrong sums and never an access outside the arrays; an entry with an index outside its factor is dropped).
+ * NNF_ERR_UNSUPPORTED: r > NNF_MAX_RANK, nnz or an extent >= 2^31.  NNF_ERR_ARG, nothing launched: null pointers, ng outside
+ * 2 .. 4, ldn not a multiple of 4 or < r, a misaligned node-major operand, short output pitches, nchunks outside [nnz / ch, nnz]. */
+/* The MTTKRP of mode n:  out[k,i] = sum_{p in slice i} vals[p] h_p[k]   (r x extent, pitch ldo), acc = fmaf(x, h, acc) in entry
+ * order inside a chunk. */
+int nnf_sptensor_mttkrp_f32(nnf_ctx* ctx, const int64_t* ptr, const int32_t* idx, const float* vals, int64_t extent, int64_t nnz,
+                            const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, int ng,
+                            const float* const* Fn, const int64_t* extents, int64_t ldn, int r, float* out, int64_t ldo, void* stream);
+/* The beta = 1 sums of mode n, as nnf_csr_kl_f32 with h in the place of the gathered row:  p = <Own_n[i, :], h> (fp32: four
+ * products per lane in index order, then a fixed tree),  q = x / p,
+ *   num[k,i] = sum q h[k]     (r x extent, pitch ldnum; may be NULL: cost only),
+ *   cost_f64[0] = sum (x log(x / p) - x) in fp64     (may be NULL: numerator only);
+ * a stored x = 0 adds 0 to both.  Own_n: the factor of mode n, extent x ldo_n, node-major.  The three forms (both, num only, cost
+ * only) give the same bits for what they share. */
+int nnf_sptensor_kl_f32(nnf_ctx* ctx, const int64_t* ptr, const int32_t* idx, const float* vals, int64_t extent, int64_t nnz,
+                        const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, int ng, const float* const* Fn,
+                        const int64_t* extents, int64_t ldn, const float* Own_n, int64_t ldo_n, int r, float* num, int64_t ldnum,
+                        double* cost_f64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,65 @@ def to_dev_csr(x, device, transpose=False):
             torch.from_numpy(a.data.astype(np.float32)).to(device), (int(a.shape[0]), int(a.shape[1])))
 
 
+class SparseCOO:
+    """A sparse tensor as coordinate lists (the input of nn_fac_amd.sparse_ntf next to a torch sparse-COO tensor): `indices` an
+    N x nnz integer array or tensor, `values` a float array or tensor of nnz entries, `shape` the N extents.  Entries may be
+    unsorted and a coordinate may be stored more than once (the values are summed)."""
+
+    def __init__(self, indices, values, shape):
+        self.indices, self.values, self.shape = indices, values, tuple(int(s) for s in shape)
+        if len(np.shape(indices)) != 2 or len(np.shape(values)) != 1 or tuple(np.shape(indices)) != (len(self.shape), np.shape(values)[0]):
+            raise ValueError(f"SparseCOO: indices of shape {(len(self.shape), 'nnz')} and values of shape ('nnz',) expected, got "
+                             f"{tuple(np.shape(indices))} and {tuple(np.shape(values))}")
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+
+def is_sparse_tensor(x):
+    """A torch sparse-COO tensor or a SparseCOO (the inputs of nn_fac_amd.sparse_ntf)."""
+    if isinstance(x, torch.Tensor):
+        return x.layout == torch.sparse_coo
+    return isinstance(x, SparseCOO)
+
+
+def to_dev_coo(x, device):
+    """The canonical coordinate list of a sparse tensor input on the device: (indices int64 [N, nnz], values float32 [nnz], shape)
+    with the entries in lexicographic order of their coordinates and no coordinate twice -- duplicates are summed in fp32, in
+    input order inside a coordinate, after a stable sort; stored zeros stay.  Never through a dense copy, and never through a
+    linear index (the product of five extents below 2^31 does not fit 64 bits): one stable sort per mode, last mode first."""
+    if isinstance(x, torch.Tensor):
+        if x.dense_dim() != 0:
+            raise EngineError("a sparse tensor with dense dimensions is not a coordinate list of scalars")
+        ind, val, shape = x._indices(), x._values(), tuple(int(s) for s in x.shape)      # (as stored: coalesced or not)
+    else:
+        ind, val, shape = x.indices, x.values, x.shape
+    if not isinstance(ind, torch.Tensor):
+        ind = torch.from_numpy(np.ascontiguousarray(np.asarray(ind), dtype=np.int64))
+    if not isinstance(val, torch.Tensor):
+        val = torch.from_numpy(np.ascontiguousarray(np.asarray(val), dtype=np.float32))
+    ind, val = ind.to(device=device, dtype=torch.int64), val.to(device=device, dtype=torch.float32)
+    nnz = val.numel()
+    order = torch.arange(nnz, dtype=torch.int64, device=device)
+    for m in reversed(range(len(shape))):
+        order = order[torch.argsort(ind[m][order], stable=True)]
+    ind, val = ind[:, order], val[order]
+    if nnz > 1:
+        first = torch.ones(nnz, dtype=torch.bool, device=device)      # the first entry of every coordinate
+        first[1:] = (ind[:, 1:] != ind[:, :-1]).any(dim=0)
+        if not bool(first.all()):
+            seg = torch.cumsum(first, 0) - 1
+            starts = torch.nonzero(first).flatten()
+            nth = torch.arange(nnz, dtype=torch.int64, device=device) - starts[seg]
+            out = val[starts].clone()
+            for k in range(1, int(nth.max()) + 1):      # the k-th duplicate of every coordinate that has one: distinct targets
+                sel = nth == k
+                out[seg[sel]] += val[sel]
+            ind, val = ind[:, starts], out
+    return ind.contiguous(), val.contiguous(), shape
+
+
 def like_input(t, proto):
     """Return device tensor `t` in the type/dtype of the caller's `proto` (ndarray -> ndarray of its dtype)."""
     if isinstance(proto, torch.Tensor):

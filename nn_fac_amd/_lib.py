@@ -90,6 +90,9 @@ SIGNATURES = {
     "nnf_csr_chunk_entries": (_i32, [_p, _i64, C.POINTER(_i64)]),
     "nnf_csr_xf_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p]),
     "nnf_csr_kl_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p, _i64, _p, _p]),
+    "nnf_sptensor_mttkrp_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _i64, _i32, _p, _i64, _p]),
+    "nnf_sptensor_kl_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _i64, _i32, _p, _i64, _p,
+                                   _p]),
 }
 
 _lib = None

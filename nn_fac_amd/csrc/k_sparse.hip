@@ -22,8 +22,7 @@
 //
 // Padding columns (r .. ldn of a node-major operand) are read and never used: the KL form masks them, the product form only
 // lets them reach workspace columns that the second pass does not read.
-#include "nnf_internal.h"
-#include "k_sparse_plan.h"
+#include "k_sparse_common.h"
 
 namespace {
 
@@ -218,32 +217,30 @@ void gather_launch(const sparse_plan& p, hipStream_t st, const int64_t* rowptr, 
 #undef SPARSE_CASE
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+}   // namespace
 
-// the checks both entries share; `nnz`, `nchunks` and `ch` are the caller's word on the device tables (the kernels hold every
-// index they read from them against these extents)
-int csr_args_ok(const nnf_ctx* ctx, const void* rowptr, const void* colidx, const void* vals, int64_t nrows, int64_t ncols, int64_t nnz,
-                const void* rowchunk, const void* chunk_row, int64_t nchunks, int ch, const float* Fn, int64_t ldn, int r) {
+// the checks both entries share (and those of k_sptensor.hip: k_sparse_common.h); `nnz`, `nchunks` and `ch` are the caller's word
+// on the device tables (the kernels hold every index they read from them against these extents)
+int nnf_csr_args_ok(const nnf_ctx* ctx, const void* rowptr, const void* colidx, const void* vals, int64_t nrows, int64_t ncols, int64_t nnz,
+                    const void* rowchunk, const void* chunk_row, int64_t nchunks, int ch, const float* Fn, int64_t ldn, int r) {
     if (!ctx || !rowptr || !rowchunk || nrows < 1 || ncols < 1 || nnz < 0 || nchunks < 0 || !Fn || r < 1 || !sparse_chunk_ok(ch))
         return NNF_ERR_ARG;
     if (nnz > 0 && (!colidx || !vals)) return NNF_ERR_ARG;
     if (nchunks > 0 && !chunk_row) return NNF_ERR_ARG;
     if (nnz > 2147483647 || ncols > 2147483647) return NNF_ERR_UNSUPPORTED;
     if (r > NNF_MAX_RANK) return NNF_ERR_UNSUPPORTED;
-    if (ldn < r || ldn % 4 != 0 || !aligned16(Fn)) return NNF_ERR_ARG;
+    if (ldn < r || ldn % 4 != 0 || !nnf_aligned16(Fn)) return NNF_ERR_ARG;
     if (nchunks > nnz || nchunks * (int64_t)ch < nnz) return NNF_ERR_ARG;      // (no table of `ch`-chunks of nnz entries has that many)
     return NNF_OK;
 }
 
-int rowsum_launch(const sparse_plan& p, hipStream_t st, const float* part, const int64_t* rowchunk, int64_t nrows, int64_t nchunks, int r,
-                  float* out, int64_t ldo) {
+int nnf_csr_rowsum_launch(const sparse_plan& p, hipStream_t st, const float* part, const int64_t* rowchunk, int64_t nrows, int64_t nchunks,
+                          int r, float* out, int64_t ldo) {
     hipLaunchKernelGGL(nnf_csr_rowsum_kernel, dim3((unsigned)p.tgrid), dim3(256), p.lds_bytes, st, part, p.rp, rowchunk, nrows, nchunks, r,
                        out, ldo);
     NNF_CHECK_LAUNCH();
     return NNF_OK;
 }
-
-}   // namespace
 
 extern "C" int nnf_csr_chunk_entries(nnf_ctx* ctx, int64_t nnz, int64_t* out) {
     if (!ctx || !out || nnz < 0) return NNF_ERR_ARG;
@@ -257,7 +254,7 @@ extern "C" int nnf_csr_chunk_entries(nnf_ctx* ctx, int64_t nnz, int64_t* out) {
 extern "C" int nnf_csr_xf_f32(nnf_ctx* ctx, const int64_t* rowptr, const int32_t* colidx, const float* vals, int64_t nrows, int64_t ncols,
                               int64_t nnz, const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, const float* Fn,
                               int64_t ldn, int r, float* out, int64_t ldo, void* stream) {
-    const int bad = csr_args_ok(ctx, rowptr, colidx, vals, nrows, ncols, nnz, rowchunk, chunk_row, nchunks, ch, Fn, ldn, r);
+    const int bad = nnf_csr_args_ok(ctx, rowptr, colidx, vals, nrows, ncols, nnz, rowchunk, chunk_row, nchunks, ch, Fn, ldn, r);
     if (bad != NNF_OK) return bad;
     if (!out || ldo < nrows) return NNF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -273,15 +270,15 @@ extern "C" int nnf_csr_xf_f32(nnf_ctx* ctx, const int64_t* rowptr, const int32_t
                              nullptr);
         NNF_CHECK_LAUNCH();
     }
-    return rowsum_launch(p, st, part, rowchunk, nrows, nchunks, r, out, ldo);
+    return nnf_csr_rowsum_launch(p, st, part, rowchunk, nrows, nchunks, r, out, ldo);
 }
 
 extern "C" int nnf_csr_kl_f32(nnf_ctx* ctx, const int64_t* rowptr, const int32_t* colidx, const float* vals, int64_t nrows, int64_t ncols,
                               int64_t nnz, const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, const float* Own_n,
                               int64_t ldo_n, const float* Fn, int64_t ldn, int r, float* num, int64_t ldnum, double* cost_f64, void* stream) {
-    const int bad = csr_args_ok(ctx, rowptr, colidx, vals, nrows, ncols, nnz, rowchunk, chunk_row, nchunks, ch, Fn, ldn, r);
+    const int bad = nnf_csr_args_ok(ctx, rowptr, colidx, vals, nrows, ncols, nnz, rowchunk, chunk_row, nchunks, ch, Fn, ldn, r);
     if (bad != NNF_OK) return bad;
-    if (!Own_n || ldo_n < r || ldo_n % 4 != 0 || !aligned16(Own_n)) return NNF_ERR_ARG;
+    if (!Own_n || ldo_n < r || ldo_n % 4 != 0 || !nnf_aligned16(Own_n)) return NNF_ERR_ARG;
     if ((!num && !cost_f64) || (num && ldnum < nrows)) return NNF_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     nnf_ws_cursor cur(ctx);
@@ -312,5 +309,5 @@ extern "C" int nnf_csr_kl_f32(nnf_ctx* ctx, const int64_t* rowptr, const int32_t
             return NNF_ERR_LAUNCH;
         }
     }
-    return num ? rowsum_launch(p, st, part, rowchunk, nrows, nchunks, r, num, ldnum) : NNF_OK;
+    return num ? nnf_csr_rowsum_launch(p, st, part, rowchunk, nrows, nchunks, r, num, ldnum) : NNF_OK;
 }

@@ -100,3 +100,32 @@ inline void sparse_report(FILE* f, const char* what, int r, int64_t nrows, int64
                "part_bytes=%zu cost_bytes=%zu ws_bytes=%zu%s\n", what, r, (long long)nrows, (long long)nnz, (long long)nchunks, ch, p.L,
             p.U, p.G, p.rp, (long long)p.grid, (long long)p.tgrid, p.lds_bytes, p.part_bytes, p.cost_bytes, p.ws_bytes, more);
 }
+
+// ---- sparse TENSORS (k_sptensor.hip; nnf_sptensor_mttkrp_f32, nnf_sptensor_kl_f32) ------------------------------------------------
+// One mode's sorted copy of a COO tensor is a CSR matrix whose "row" is a slice of that mode and whose stored entry carries
+// ng = N - 1 indices instead of one column: the chunk table, the spans, the lanes per entry, the workspace rows and the second
+// pass are the CSR kernels' (everything above).  What differs is what a lane holds in flight: ng 16-byte pieces per entry (one of
+// every gathered factor row) instead of one, so the entries in flight per lane are cut to keep the pieces in flight per lane
+// (U ng) at about twice the CSR kernel's U: 2 U / ng rounded down to a power of two, at least 1.
+//     L        1, 2   4, 8   16, 32          pieces in flight per lane (U ng)
+//     ng = 2   1      2      4               2 / 4 / 8
+//     ng = 3   1      1      2               3 / 3 / 6
+//     ng = 4   1      1      2               4 / 4 / 8
+// The registers of every instance (build/k_sptensor.s) stay below the 128 of four waves per SIMD, so the
+// chunk rule's SPARSE_WAVES_PER_CU = 16 holds for these kernels too.
+constexpr int SPTENSOR_NG_MIN = 2;         // gathered factors per entry: tensors of order 3 ..
+constexpr int SPTENSOR_NG_MAX = 4;         // .. 5
+constexpr int sptensor_unroll(int L, int ng) {
+    const int u = sparse_unroll(L) * 2 / (ng < 1 ? 1 : ng);
+    return u >= 4 ? 4 : u >= 2 ? 2 : 1;
+}
+// the CSR plan of the mode's copy (nrows = the extent of the mode) with the entries in flight of `ng` gathered factors
+inline sparse_plan sptensor_make_plan(int r, int ng, int64_t extent, int64_t nchunks, bool want_out, bool want_cost, size_t ws_free) {
+    sparse_plan p = sparse_make_plan(r, extent, nchunks, want_out, want_cost, ws_free);
+    if (ng < SPTENSOR_NG_MIN || ng > SPTENSOR_NG_MAX) {
+        p.status = NNF_ERR_ARG;
+        return p;
+    }
+    if (p.L > 0) p.U = sptensor_unroll(p.L, ng);
+    return p;
+}

@@ -349,7 +349,148 @@ class CsrOps:
         return O
 
 
-class Engine(CsrOps):
+class SparseMode:
+    """One mode's sorted copy of a sparse tensor (include/nnfac_hip.h): `ptr` int64 [extent + 1] with the role of rowptr, `idx`
+    int32 [N - 1, nnz] planar with the other modes (`others`, increasing) one per plane, `vals` float32 [nnz], and the chunk
+    table of csr_chunk_table.  Checked once, as _csr_triple checks a CSR matrix."""
+
+    def __init__(self, mode, ptr, idx, vals, shape, ch, what="sparse_tensor"):
+        self.mode, self.extent, self.nnz = int(mode), int(shape[mode]), vals.numel()
+        self.others = [m for m in range(len(shape)) if m != mode]
+        self.extents = [int(shape[m]) for m in self.others]
+        what = f"{what} mode {mode}"
+        for t, dt, nd, nm in ((ptr, torch.int64, 1, "ptr"), (idx, torch.int32, 2, "idx"), (vals, torch.float32, 1, "vals")):
+            if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd or not t.is_contiguous() or not t.is_cuda \
+                    or t.device != ptr.device:
+                raise EngineError(f"{what} {nm}: expected a contiguous {nd}-D {dt} tensor on the device of ptr")
+        if ptr.numel() != self.extent + 1 or tuple(idx.shape) != (len(self.others), self.nnz):
+            raise EngineError(f"{what}: lengths do not fit, extent {self.extent}, ptr {ptr.numel()}, idx {tuple(idx.shape)}, "
+                              f"vals {self.nnz}")
+        ends = torch.stack([ptr[0], ptr[-1], (ptr[1:] - ptr[:-1]).min()]).tolist()
+        if ends[0] != 0 or ends[1] != self.nnz or ends[2] < 0:
+            raise EngineError(f"{what} ptr: must rise from ptr[0] == 0 to ptr[-1] == nnz ({self.nnz}); got {ends[0]} .. {ends[1]}")
+        if self.nnz:
+            top = torch.tensor(self.extents, dtype=torch.int32, device=idx.device)[:, None]
+            if not bool(((idx >= 0) & (idx < top)).all()):
+                raise EngineError(f"{what} idx: an index outside its mode's extent {self.extents}")
+        self.ptr, self.idx, self.vals, self.ch = ptr, idx, vals, int(ch)
+        self.rowchunk, self.chunk_row = csr_chunk_table(ptr, self.ch)
+        self.nchunks = self.chunk_row.numel()
+
+    def args(self):
+        """The argument run of the sparse-tensor entries up to the gathered factors."""
+        return (_ptr(self.ptr), _ptr(self.idx), _ptr(self.vals), self.extent, self.nnz, _ptr(self.rowchunk), _ptr(self.chunk_row),
+                self.nchunks, self.ch)
+
+
+class SparseTensor:
+    """A device sparse tensor of order 3 .. 5 as the sparse-tensor kernels walk it (Engine.sparse_tensor): one sorted copy per
+    mode (SparseMode), each 4 N bytes per stored entry.  `indices` int64 [N, nnz] and `values` float32 [nnz] on one device,
+    every index inside its extent; a coordinate stored twice is the caller's business (_convert.to_dev_coo sums duplicates).
+    A copy is a stable sort of the list handed in by its mode's index: from the canonical (lexicographic) list every slice keeps
+    its entries in lexicographic order of the other modes."""
+
+    MIN_ORDER, MAX_ORDER = 3, 5
+
+    def __init__(self, eng, indices, values, shape, ch=None):
+        shape = tuple(int(s) for s in shape)
+        N = len(shape)
+        if not self.MIN_ORDER <= N <= self.MAX_ORDER:
+            raise EngineError(f"sparse_tensor: order {N} is outside the {self.MIN_ORDER} .. {self.MAX_ORDER} the kernels are built for")
+        for t, dt, nd, nm in ((indices, torch.int64, 2, "indices"), (values, torch.float32, 1, "values")):
+            if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd or not t.is_cuda or t.device != indices.device:
+                raise EngineError(f"sparse_tensor {nm}: expected a {nd}-D {dt} device tensor on the device of indices")
+        nnz = values.numel()
+        if tuple(indices.shape) != (N, nnz):
+            raise EngineError(f"sparse_tensor: indices of shape {(N, nnz)} expected, got {tuple(indices.shape)}")
+        if min(shape) < 1 or max(shape) >= 2 ** 31 or nnz >= 2 ** 31:
+            raise EngineError(f"sparse_tensor: a tensor of shape {shape} with {nnz} stored entries is outside 1 <= extents and "
+                              f"nnz < 2^31")
+        top = torch.tensor(shape, dtype=torch.int64, device=indices.device)[:, None]
+        if nnz and not bool(((indices >= 0) & (indices < top)).all()):
+            raise EngineError(f"sparse_tensor indices: an index outside the shape {shape}")
+        self.shape, self.order, self.nnz, self.device = shape, N, nnz, indices.device
+        self.ch = int(ch) if ch is not None else eng.csr_chunk_entries(nnz)
+        if not 1 <= self.ch <= 1 << 20:
+            raise EngineError(f"sparse_tensor: a chunk size of {self.ch} is outside 1 .. 2^20")
+        self.modes = []
+        for n in range(N):
+            order = torch.argsort(indices[n], stable=True)
+            ptr = torch.zeros(shape[n] + 1, dtype=torch.int64, device=indices.device)
+            torch.cumsum(torch.bincount(indices[n], minlength=shape[n]), 0, out=ptr[1:])
+            others = [m for m in range(N) if m != n]
+            idx = indices[others][:, order].to(torch.int32).contiguous()
+            self.modes.append(SparseMode(n, ptr, idx, values[order].contiguous(), shape, self.ch))
+
+
+class SparseTensorOps:
+    """The sparse-tensor entries of the engine (Engine inherits them): NTF on sparse data, over the stored entries only.  Their
+    operand refusals are tested in tests/test_gpu_sptensor_kernels.py, one spoilt operand at a time."""
+
+    def sparse_tensor(self, indices, values, shape, ch=None):
+        """A checked device sparse tensor with its N mode copies and their chunk tables (once per tensor; `ch`: another chunk
+        size than the library's)."""
+        return SparseTensor(self, indices, values, shape, ch=ch)
+
+    @staticmethod
+    def _sptensor_ops(S, mode, factors, what):
+        """The copy of `mode` and its N - 1 gathered node-major factors (the other modes in increasing order, one common pitch)
+        -> (copy, r, host array of device pointers, host array of extents, pitch)."""
+        if not isinstance(S, SparseTensor):
+            raise EngineError(f"{what}: the tensor must be a SparseTensor (Engine.sparse_tensor)")
+        if not isinstance(mode, int) or not 0 <= mode < S.order:
+            raise EngineError(f"{what}: mode {mode!r} is not a mode of a tensor of order {S.order}")
+        M = S.modes[mode]
+        factors = list(factors)
+        if len(factors) != S.order - 1:
+            raise EngineError(f"{what}: {S.order - 1} gathered factors (the modes {M.others}) expected, got {len(factors)}")
+        r = None
+        for m, F, ext in zip(M.others, factors, M.extents):
+            if not torch.is_tensor(F):
+                raise EngineError(f"{what} factor of mode {m}: a node-major device tensor expected, got {type(F).__name__}")
+            rm = _node_major(F, ext, f"{what} factor of mode {m}")
+            if F.device != S.device:
+                raise EngineError(f"{what} factor of mode {m} must be on {S.device}, got {F.device}")
+            if r is not None and rm != r:
+                raise EngineError(f"{what}: the gathered factors differ in rank ({r} and {rm})")
+            r = rm
+        if r > MAX_RANK:
+            raise EngineError(f"{what}: rank {r} is above the {MAX_RANK} the sparse-tensor kernels are built for")
+        pitches = {_ld(F) for F in factors if F.shape[0] > 1}      # (the pitch of a single row addresses nothing)
+        if len(pitches) > 1:
+            raise EngineError(f"{what}: the gathered factors must share one pitch (node_major() gives it), got {sorted(pitches)}")
+        ldn = pitches.pop() if pitches else (r + 3) // 4 * 4
+        ptrs = (C.c_void_p * len(factors))(*[F.data_ptr() for F in factors])
+        exts = (C.c_int64 * len(factors))(*M.extents)
+        return M, r, ptrs, exts, ldn
+
+    def sptensor_mttkrp(self, S, mode, factors_node_major, out=None):
+        """The MTTKRP of `mode` over the stored entries of S (nnf_sptensor_mttkrp_f32): out[k, i] = sum_{p in slice i} x_p
+        prod_{m != mode} F_m[i_m(p), k]  (r x extent).  `factors_node_major`: the N - 1 other factors, node-major (node_major()),
+        in increasing mode order."""
+        M, r, ptrs, exts, ldn = self._sptensor_ops(S, mode, factors_node_major, "sptensor_mttkrp")
+        O = _out(out, (r, M.extent), M.vals, "sptensor_mttkrp out")
+        self._call("nnf_sptensor_mttkrp_f32", *M.args(), len(exts), ptrs, exts, ldn, r, *_mat(O))
+        return O
+
+    def sptensor_kl(self, S, mode, Own_n, factors_node_major, num=True, cost_out=None, out=None):
+        """The beta = 1 sums of `mode` over the stored entries of S (nnf_sptensor_kl_f32): with h = prod_{m != mode} F_m[i_m, :],
+        p = <Own_n[i, :], h> and q = x / p per stored x, the numerator num[k, i] = sum q h[k] (r x extent; `num=False`: not asked
+        for) and, into the 1-element float64 `cost_out`, sum (x log(x / p) - x).  Returns the numerator or None."""
+        M, r, ptrs, exts, ldn = self._sptensor_ops(S, mode, factors_node_major, "sptensor_kl")
+        if not torch.is_tensor(Own_n) or _node_major(Own_n, M.extent, "sptensor_kl Own_n") != r or Own_n.device != S.device:
+            raise EngineError(f"sptensor_kl Own_n: {M.extent} x {r} on {S.device} expected, got {tuple(getattr(Own_n, 'shape', ()))} on "
+                              f"{getattr(Own_n, 'device', None)}")
+        if not num and cost_out is None:
+            raise EngineError("sptensor_kl: nothing asked for")
+        if cost_out is not None:
+            _f64(cost_out, 1, S.device, "sptensor_kl cost_out")
+        O = _out(out, (r, M.extent), M.vals, "sptensor_kl out") if num else None
+        self._call("nnf_sptensor_kl_f32", *M.args(), len(exts), ptrs, exts, ldn, *_mat(Own_n), r, *_optmat(O), _opt(cost_out))
+        return O
+
+
+class Engine(CsrOps, SparseTensorOps):
     """One context (workspace + device properties) per device."""
 
     def __init__(self, device, workspace_bytes=0):

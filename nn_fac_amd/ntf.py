@@ -29,7 +29,7 @@ import torch
 from .utils import errors as err
 from .utils import initialize_factors as init_factors
 from . import engine as _engine
-from ._convert import device_of, to_dev, to_dev_t, like_input
+from ._convert import device_of, to_dev, to_dev_t, like_input, is_sparse_tensor
 from .update_rules.nnls import tic, toc, timed_budget
 from . import dist as _dist
 from . import _outer_loop as _loop
@@ -43,6 +43,9 @@ def ntf(tensor, rank, init="random", factors_0=[], n_iter_max=100, tol=1e-8,
         sparsity_coefficients=[], fixed_modes=[], normalize=[],
         verbose=False, return_costs=False):
     """Nonnegative PARAFAC of `tensor` (reference docstring: ntf.py:23-179)."""
+    if is_sparse_tensor(tensor):      # sparse_ntf.py: what that path refuses is said before the start values are drawn
+        from . import sparse_ntf
+        sparse_ntf.check_request(rank, update_rule, beta, len(tensor.shape), init=init)
     factors = []
     nb_modes = len(tensor.shape)
     if init.lower() == "custom":
@@ -380,7 +383,14 @@ def compute_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8,
                 update_rule="hals", beta=2,
                 sparsity_coefficients=[], fixed_modes=[], normalize=[],
                 verbose=False, return_costs=False, alpha=0.5, delta=0.01, sweep_log=None):
-    """Outer loop of ntf.py:288-344.  Returns the list of factors (dim x R each) [, costs, toc]."""
+    """Outer loop of ntf.py:288-344.  Returns the list of factors (dim x R each) [, costs, toc].
+    A sparse `tensor_in` (a torch sparse-COO tensor, a sparse_ntf.SparseCOO) runs in nn_fac_amd.sparse_ntf, over its stored entries."""
+    if is_sparse_tensor(tensor_in):
+        from . import sparse_ntf
+        return sparse_ntf.compute_sparse_ntf(tensor_in, rank, factors_in, n_iter_max=n_iter_max, tol=tol, update_rule=update_rule,
+                                             beta=beta, sparsity_coefficients=sparsity_coefficients, fixed_modes=fixed_modes,
+                                             normalize=normalize, verbose=verbose, return_costs=return_costs, alpha=alpha,
+                                             delta=delta, sweep_log=sweep_log)
     dev = device_of(tensor_in, *factors_in)
     eng = _engine.get_engine(dev)
     T = to_dev(tensor_in, dev)
@@ -409,7 +419,12 @@ def one_ntf_step(unfolded_tensors, rank, in_factors, norm_tensor, update_rule, b
                  sparsity_coefficients, fixed_modes, normalize,
                  alpha=0.5, delta=0.01):
     """One pass over the modes (ntf.py:422-477).  `unfolded_tensors` is the reference's list of unfoldings; the tensor is
-    rebuilt from the mode-0 unfolding (a plain reshape).  Returns (factors, cost)."""
+    rebuilt from the mode-0 unfolding (a plain reshape).  Returns (factors, cost).  A sparse tensor (sparse_ntf.py) is passed
+    as itself, where the unfoldings are."""
+    if is_sparse_tensor(unfolded_tensors):
+        from . import sparse_ntf
+        return sparse_ntf.one_sparse_ntf_step(unfolded_tensors, rank, in_factors, norm_tensor, update_rule, beta,
+                                              sparsity_coefficients, fixed_modes, normalize, alpha=alpha, delta=delta)
     dev = device_of(*unfolded_tensors, *in_factors)
     eng = _engine.get_engine(dev)
     dims = [int(u.shape[0]) for u in unfolded_tensors]

@@ -73,6 +73,12 @@
 //                                     line of that call (csr_xf / csr_kl), then carved= (the bytes a cursor has handed out after the launcher's
 //                                     carves) and chunks=<row>:<first>:<end>,... (every chunk in chunk order, spans from
 //                                     sparse_chunk_span as the kernel takes them; "-" for none), or "status=<code>".
+//                        The sparse-tensor kernels' plan (k_sparse_plan.h: the CSR plan of one mode's sorted copy), key=value only:
+//                          sptensor <CUs> r= ng= lens=<len0,len1,...> [ch=] [out=] [cost=] [ws=]     as `sparse`, with lens the stored
+//                                     entries of every slice of the mode and ng = N - 1 the gathered factors per entry (2 .. 4).
+//                                     Answer: the "[nnf plan] sptensor_..." line of that call (sptensor_mttkrp: out=1 cost=0;
+//                                     sptensor_kl otherwise) with U = sptensor_unroll(L, ng), then ng=, carved= and chunks=, or
+//                                     "status=<code>" (the argument checks of the entries included).
 //   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
 //                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
 //
@@ -184,7 +190,7 @@ static int answer_simplex(const char* line) {
     return 0;
 }
 
-static int answer_sparse(const char* line) {
+static int answer_sparse(const char* line, bool tensor) {
     int C = 0, used = 0;
     if (sscanf(line, "%*s %d%n", &C, &used) != 1 || C < 1) return 2;
     const char* rest = line + used;
@@ -202,8 +208,9 @@ static int answer_sparse(const char* line) {
     const long long r = key_of(rest, "r", 0), ws = key_of(rest, "ws", 1024ll << 20);
     const int ch = (int)key_of(rest, "ch", sparse_chunk_entries(C, nnz));
     const bool out = key_of(rest, "out", 1) != 0, cost = key_of(rest, "cost", 0) != 0;
-    // (the argument checks of csr_args_ok, k_sparse.hip)
-    if (nrows < 1 || r < 1 || !sparse_chunk_ok(ch) || (!out && !cost)) {
+    const int ng = (int)key_of(rest, "ng", 0);
+    // (the argument checks of nnf_csr_args_ok, k_sparse.hip, and of sptensor_args_ok, k_sptensor.hip)
+    if (nrows < 1 || r < 1 || !sparse_chunk_ok(ch) || (!out && !cost) || (tensor && (ng < SPTENSOR_NG_MIN || ng > SPTENSOR_NG_MAX))) {
         printf("status=%d\n", NNF_ERR_ARG);
         return 0;
     }
@@ -216,7 +223,9 @@ static int answer_sparse(const char* line) {
         chunk_row.insert(chunk_row.end(), (size_t)k, (int)i);
     }
     const int64_t nchunks = rowchunk.back();
-    const sparse_plan p = sparse_make_plan((int)(r > 1000000 ? 1000000 : r), nrows, nchunks, out, cost, (size_t)ws);
+    const int rr = (int)(r > 1000000 ? 1000000 : r);
+    const sparse_plan p = tensor ? sptensor_make_plan(rr, ng, nrows, nchunks, out, cost, (size_t)ws)
+                                 : sparse_make_plan(rr, nrows, nchunks, out, cost, (size_t)ws);
     if (p.status != NNF_OK) {
         printf("status=%d\n", p.status);
         return 0;
@@ -233,7 +242,9 @@ static int answer_sparse(const char* line) {
         chunks += one;
     }
     std::string more = " carved=" + std::to_string(cur.off) + " chunks=" + (nchunks ? chunks : std::string("-"));
-    sparse_report(stdout, out && !cost ? "csr_xf" : "csr_kl", (int)r, nrows, nnz, nchunks, ch, p, more.c_str());
+    if (tensor) more = " ng=" + std::to_string(ng) + more;
+    const char* what = tensor ? (out && !cost ? "sptensor_mttkrp" : "sptensor_kl") : (out && !cost ? "csr_xf" : "csr_kl");
+    sparse_report(stdout, what, (int)r, nrows, nnz, nchunks, ch, p, more.c_str());
     return 0;
 }
 
@@ -265,8 +276,8 @@ int main(int argc, char** argv) {
             answer_reduce(line);
             continue;
         }
-        if (sscanf(line, "%31s", name) == 1 && strcmp(name, "sparse") == 0) {
-            if (answer_sparse(line) != 0) {
+        if (sscanf(line, "%31s", name) == 1 && (strcmp(name, "sparse") == 0 || strcmp(name, "sptensor") == 0)) {
+            if (answer_sparse(line, name[1] == 'p' && name[2] == 't') != 0) {
                 fprintf(stderr, "nnf_plan: bad case line: %s", line);
                 return 2;
             }
