@@ -604,6 +604,32 @@ int nnf_sptensor_kl_f32(nnf_ctx* ctx, const int64_t* ptr, const int32_t* idx, co
                         const int64_t* extents, int64_t ldn, const float* Own_n, int64_t ldo_n, int r, float* num, int64_t ldnum,
                         double* cost_f64, void* stream);
 
+/* ---- sparse data with MISSING entries: the MU sums of any beta >= 0 over the stored entries only ------------------------------
+ * (nn_fac_amd/sparse_nmf.py, sparse_ntf.py with unstored="missing": an unstored entry is unknown, not zero.)  The layouts, the
+ * chunk table, the workspace rows, the second pass and the refusals are those of nnf_csr_kl_f32 / nnf_sptensor_kl_f32 above.
+ * Per stored entry x with h the gathered row (a tensor: the Hadamard product of the ng gathered rows, fp32 in mode order) and
+ * p = <Own_n[i, :], h> (fp32: four products per lane in index order, then a fixed tree; formed once per entry),
+ *   num[k,i] = sum x p^(beta - 2) h[k],   den[k,i] = sum p^(beta - 1) h[k]     (r x nrows, pitches ldnum / ldden; fp32 FMAs in entry
+ *                                                                              order; given together or both NULL: cost only),
+ *   cost_f64[0] = sum d_beta(x | p) in fp64 from the fp32 p     (may be NULL: sums only; the beta-divergence per entry of
+ *                                                               beta_divergence.py:45-52, 1/2 (x - p)^2 at beta = 2).
+ * This is mu_betadivmin (mu.py:82-97) with every sum cut down to the stored entries: F <- max(F (num / den)^gamma, eps) is
+ * nnf_mu_apply_f32 on the two outputs.  beta = 0, 1, 2, 3 use multiplications and divisions only, any other beta a
+ * single-precision power p^e = exp2(e log2 p).  A stored x = 0 is an OBSERVED zero: nothing to num, its term to den (h at
+ * beta = 1), d_beta(0 | p) to the cost -- as nnf_betadiv_f32 has it for a zero entry, p at beta = 1 and +inf at beta = 0 (no
+ * 0 log 0 := 0 here: the entry is data), p^beta / beta otherwise.  A slice without stored entries gets num = den = 0: the caller
+ * keeps its factor row (0 / 0 otherwise).  Each chunk leaves two node-major rows in the context workspace (8 nchunks
+ * roundup4(r) bytes); the three forms (both, sums only, cost only) give the same bits for what they share.  NNF_ERR_ARG, nothing
+ * launched: what the KL entries refuse, one of num / den without the other, nothing asked for, beta < 0 or not finite. */
+int nnf_csr_obs_f32(nnf_ctx* ctx, const int64_t* rowptr, const int32_t* colidx, const float* vals, int64_t nrows, int64_t ncols,
+                    int64_t nnz, const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, const float* Own_n,
+                    int64_t ldo_n, const float* Fn, int64_t ldn, int r, double beta, float* num, int64_t ldnum, float* den,
+                    int64_t ldden, double* cost_f64, void* stream);
+int nnf_sptensor_obs_f32(nnf_ctx* ctx, const int64_t* ptr, const int32_t* idx, const float* vals, int64_t extent, int64_t nnz,
+                         const int64_t* rowchunk, const int32_t* chunk_row, int64_t nchunks, int ch, int ng, const float* const* Fn,
+                         const int64_t* extents, int64_t ldn, const float* Own_n, int64_t ldo_n, int r, double beta, float* num,
+                         int64_t ldnum, float* den, int64_t ldden, double* cost_f64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

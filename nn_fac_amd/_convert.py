@@ -134,6 +134,28 @@ def to_dev_coo(x, device):
     return ind.contiguous(), val.contiguous(), shape
 
 
+def observed_entries(array, mask):
+    """The sparse input that holds exactly the entries of the dense `array` (NumPy or torch, order >= 2) where the boolean `mask`
+    (same shape) is set, ZEROS INCLUDED, in row-major order: a torch sparse-CSR tensor for a matrix, a SparseCOO for order >= 3,
+    on the device of a torch `array`.  The input of unstored="missing" runs (sparse_nmf.py, sparse_ntf.py), where a stored zero
+    is an observed zero: scipy.sparse.csr_matrix(dense) drops zeros and would turn them into missing entries."""
+    a = array if isinstance(array, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(array)))
+    if isinstance(mask, torch.Tensor):
+        w = mask.to(a.device)
+    else:
+        w = torch.from_numpy(np.ascontiguousarray(np.asarray(mask))).to(a.device)
+    if w.dtype != torch.bool or tuple(w.shape) != tuple(a.shape) or a.dim() < 2:
+        raise ValueError(f"observed_entries: a boolean mask of the array's shape {tuple(a.shape)} (order >= 2) expected, got "
+                         f"{w.dtype} {tuple(w.shape)}")
+    indices = torch.nonzero(w).t().contiguous()      # N x nnz, lexicographic
+    values = a[w]
+    if a.dim() > 2:
+        return SparseCOO(indices, values, a.shape)
+    crow = torch.zeros(a.shape[0] + 1, dtype=torch.int64, device=a.device)
+    torch.cumsum(w.sum(dim=1), 0, out=crow[1:])
+    return torch.sparse_csr_tensor(crow, indices[1], values, size=tuple(a.shape))
+
+
 def like_input(t, proto):
     """Return device tensor `t` in the type/dtype of the caller's `proto` (ndarray -> ndarray of its dtype)."""
     if isinstance(proto, torch.Tensor):

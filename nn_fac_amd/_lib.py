@@ -93,6 +93,10 @@ SIGNATURES = {
     "nnf_sptensor_mttkrp_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _i64, _i32, _p, _i64, _p]),
     "nnf_sptensor_kl_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _i64, _i32, _p, _i64, _p,
                                    _p]),
+    "nnf_csr_obs_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _f64, _p, _i64, _p,
+                               _i64, _p, _p]),
+    "nnf_sptensor_obs_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _i64, _i32, _f64, _p,
+                                    _i64, _p, _i64, _p, _p]),
 }
 
 _lib = None

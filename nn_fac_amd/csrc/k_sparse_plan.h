@@ -129,3 +129,26 @@ inline sparse_plan sptensor_make_plan(int r, int ng, int64_t extent, int64_t nch
     if (p.L > 0) p.U = sptensor_unroll(p.L, ng);
     return p;
 }
+
+// ---- OBSERVED entries only (k_sparse_obs.hip; nnf_csr_obs_f32, nnf_sptensor_obs_f32) ----------------------------------------------
+// The MU sums of a factorization that fits the stored entries and nothing else: numerator AND denominator are sums over a slice's
+// stored entries, so one gather kernel leaves two node-major workspace rows per chunk (one array each) and the second pass runs
+// once per array.  A CSR matrix is the ng = 1 case of a mode's copy (colidx = index plane 0): chunk table, spans, lanes per entry,
+// entries in flight and workspace rows are those of the plans above -- sparse_make_plan at ng = 1, sptensor_make_plan at
+// ng = 2 .. 4 -- with part_bytes doubled and carved as two arrays (each starts on the cursor's 256-byte boundary).
+constexpr int SPARSE_OBS_NG_MIN = 1;
+inline sparse_plan sparse_obs_make_plan(int r, int ng, int64_t nrows, int64_t nchunks, bool want_sums, bool want_cost, size_t ws_free) {
+    sparse_plan p = ng == SPARSE_OBS_NG_MIN ? sparse_make_plan(r, nrows, nchunks, want_sums, want_cost, ~size_t(0) >> 1)
+                                            : sptensor_make_plan(r, ng, nrows, nchunks, want_sums, want_cost, ~size_t(0) >> 1);
+    if (p.status != NNF_OK) return p;
+    const size_t one = p.part_bytes;      // one array: nchunks node-major rows
+    p.part_bytes = 2 * one;
+    nnf_ws_cursor cur(nullptr, ws_free);
+    const bool fits = (one == 0 || (cur.reserve(one) && cur.reserve(one))) && (p.cost_bytes == 0 || cur.reserve(p.cost_bytes));
+    nnf_ws_cursor all(nullptr, ~size_t(0) >> 1);
+    if (one != 0) all.reserve(one), all.reserve(one);
+    if (p.cost_bytes != 0) all.reserve(p.cost_bytes);
+    p.ws_bytes = all.off;
+    p.status = fits ? NNF_OK : NNF_ERR_WORKSPACE;
+    return p;
+}

@@ -278,6 +278,17 @@ def _node_major(F, nodes, what):
     return F.shape[1]
 
 
+def _obs_beta(beta, what):
+    """beta of the observed-entries sums as a float: finite and >= 0."""
+    try:
+        b = float(beta)
+    except (TypeError, ValueError):
+        raise EngineError(f"{what}: beta must be a number, got {beta!r}") from None
+    if not (0.0 <= b < float("inf")):
+        raise EngineError(f"{what}: beta must be finite and >= 0, got {beta!r}")
+    return b
+
+
 def node_major(Ft):
     """The node-major copy (nodes x r, pitch r rounded up to 4 floats) of a component-major factor Ft (r x nodes): data movement."""
     r, nodes = Ft.shape
@@ -347,6 +358,25 @@ class CsrOps:
         O = _out(out, (r, A.nrows), Fn, "csr_kl out") if num else None
         self._call("nnf_csr_kl_f32", *A.args(), *_mat(Own_n), *_mat(Fn), r, *_optmat(O), _opt(cost_out))
         return O
+
+    def csr_obs(self, A, Own_n, Fn, beta, sums=True, cost_out=None, out_num=None, out_den=None):
+        """The MU sums of any beta >= 0 over the stored entries of A, read as the OBSERVED ones (nnf_csr_obs_f32): with
+        p = <Own_n[i, :], Fn[j, :]> per stored x at (i, j), num[k, i] = sum x p^(beta - 2) Fn[j, k] and den[k, i] = sum
+        p^(beta - 1) Fn[j, k] (both r x nrows; `sums=False`: not asked for) and, into the 1-element float64 `cost_out`, sum
+        d_beta(x | p).  A stored 0 is an observed zero; a row without stored entries gets num = den = 0.  Returns (num, den) or
+        None.  Refusals: tests/test_gpu_observed_kernels.py, one spoilt operand at a time."""
+        r = self._csr_rank(A, Fn, "csr_obs")
+        if _node_major(Own_n, A.nrows, "csr_obs Own_n") != r or Own_n.device != A.device:
+            raise EngineError(f"csr_obs Own_n: {A.nrows} x {r} on {A.device} expected, got {tuple(Own_n.shape)} on {Own_n.device}")
+        beta = _obs_beta(beta, "csr_obs")
+        if not sums and cost_out is None:
+            raise EngineError("csr_obs: nothing asked for")
+        if cost_out is not None:
+            _f64(cost_out, 1, A.device, "csr_obs cost_out")
+        N = _out(out_num, (r, A.nrows), Fn, "csr_obs out_num") if sums else None
+        D = _out(out_den, (r, A.nrows), Fn, "csr_obs out_den") if sums else None
+        self._call("nnf_csr_obs_f32", *A.args(), *_mat(Own_n), *_mat(Fn), r, beta, *_optmat(N), *_optmat(D), _opt(cost_out))
+        return (N, D) if sums else None
 
 
 class SparseMode:
@@ -488,6 +518,27 @@ class SparseTensorOps:
         O = _out(out, (r, M.extent), M.vals, "sptensor_kl out") if num else None
         self._call("nnf_sptensor_kl_f32", *M.args(), len(exts), ptrs, exts, ldn, *_mat(Own_n), r, *_optmat(O), _opt(cost_out))
         return O
+
+    def sptensor_obs(self, S, mode, Own_n, factors_node_major, beta, sums=True, cost_out=None, out_num=None, out_den=None):
+        """The MU sums of `mode` at any beta >= 0 over the stored entries of S, read as the OBSERVED ones
+        (nnf_sptensor_obs_f32): with h = prod_{m != mode} F_m[i_m, :] and p = <Own_n[i, :], h> per stored x, num[k, i] = sum
+        x p^(beta - 2) h[k] and den[k, i] = sum p^(beta - 1) h[k] (both r x extent; `sums=False`: not asked for) and, into the
+        1-element float64 `cost_out`, sum d_beta(x | p).  Returns (num, den) or None.  Refusals:
+        tests/test_gpu_observed_kernels.py, one spoilt operand at a time."""
+        M, r, ptrs, exts, ldn = self._sptensor_ops(S, mode, factors_node_major, "sptensor_obs")
+        if not torch.is_tensor(Own_n) or _node_major(Own_n, M.extent, "sptensor_obs Own_n") != r or Own_n.device != S.device:
+            raise EngineError(f"sptensor_obs Own_n: {M.extent} x {r} on {S.device} expected, got "
+                              f"{tuple(getattr(Own_n, 'shape', ()))} on {getattr(Own_n, 'device', None)}")
+        beta = _obs_beta(beta, "sptensor_obs")
+        if not sums and cost_out is None:
+            raise EngineError("sptensor_obs: nothing asked for")
+        if cost_out is not None:
+            _f64(cost_out, 1, S.device, "sptensor_obs cost_out")
+        N = _out(out_num, (r, M.extent), M.vals, "sptensor_obs out_num") if sums else None
+        D = _out(out_den, (r, M.extent), M.vals, "sptensor_obs out_den") if sums else None
+        self._call("nnf_sptensor_obs_f32", *M.args(), len(exts), ptrs, exts, ldn, *_mat(Own_n), r, beta, *_optmat(N), *_optmat(D),
+                   _opt(cost_out))
+        return (N, D) if sums else None
 
 
 class Engine(CsrOps, SparseTensorOps):

@@ -41,11 +41,15 @@ from ._outer_loop import _IdentityUnreliable, _IdentityNearStop, _GuessMissed  #
 def ntf(tensor, rank, init="random", factors_0=[], n_iter_max=100, tol=1e-8,
         update_rule="hals", beta=2,
         sparsity_coefficients=[], fixed_modes=[], normalize=[],
-        verbose=False, return_costs=False):
-    """Nonnegative PARAFAC of `tensor` (reference docstring: ntf.py:23-179)."""
+        verbose=False, return_costs=False, unstored="zero"):
+    """Nonnegative PARAFAC of `tensor` (reference docstring: ntf.py:23-179).  ``unstored`` (extension, sparse tensors): "zero" reads
+    an unstored entry as a zero, "missing" as unknown -- the fit is over the stored entries only (sparse_ntf.py)."""
     if is_sparse_tensor(tensor):      # sparse_ntf.py: what that path refuses is said before the start values are drawn
         from . import sparse_ntf
-        sparse_ntf.check_request(rank, update_rule, beta, len(tensor.shape), init=init)
+        sparse_ntf.check_request(rank, update_rule, beta, len(tensor.shape), init=init, unstored=unstored)
+    elif unstored != "zero":
+        from .sparse_nmf import check_unstored
+        check_unstored(unstored, False, "NTF")
     factors = []
     nb_modes = len(tensor.shape)
     if init.lower() == "custom":
@@ -62,7 +66,7 @@ def ntf(tensor, rank, init="random", factors_0=[], n_iter_max=100, tol=1e-8,
     return compute_ntf(tensor, rank, factors, n_iter_max=n_iter_max, tol=tol,
                        update_rule=update_rule, beta=beta,
                        sparsity_coefficients=sparsity_coefficients, fixed_modes=fixed_modes, normalize=normalize,
-                       verbose=verbose, return_costs=return_costs)
+                       verbose=verbose, return_costs=return_costs, unstored=unstored)
 
 
 class _NtfState(TensorState, _loop.AsyncStop):
@@ -382,15 +386,19 @@ def run_ntf_steps(st, rank, Ft, n_iter, update_rule, beta, sparsity_coefficients
 def compute_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8,
                 update_rule="hals", beta=2,
                 sparsity_coefficients=[], fixed_modes=[], normalize=[],
-                verbose=False, return_costs=False, alpha=0.5, delta=0.01, sweep_log=None):
+                verbose=False, return_costs=False, alpha=0.5, delta=0.01, sweep_log=None, unstored="zero"):
     """Outer loop of ntf.py:288-344.  Returns the list of factors (dim x R each) [, costs, toc].
-    A sparse `tensor_in` (a torch sparse-COO tensor, a sparse_ntf.SparseCOO) runs in nn_fac_amd.sparse_ntf, over its stored entries."""
+    A sparse `tensor_in` (a torch sparse-COO tensor, a sparse_ntf.SparseCOO) runs in nn_fac_amd.sparse_ntf, over its stored entries;
+    ``unstored`` says what an unstored entry is, "zero" or "missing" (see there)."""
     if is_sparse_tensor(tensor_in):
         from . import sparse_ntf
         return sparse_ntf.compute_sparse_ntf(tensor_in, rank, factors_in, n_iter_max=n_iter_max, tol=tol, update_rule=update_rule,
                                              beta=beta, sparsity_coefficients=sparsity_coefficients, fixed_modes=fixed_modes,
                                              normalize=normalize, verbose=verbose, return_costs=return_costs, alpha=alpha,
-                                             delta=delta, sweep_log=sweep_log)
+                                             delta=delta, sweep_log=sweep_log, unstored=unstored)
+    if unstored != "zero":
+        from .sparse_nmf import check_unstored
+        check_unstored(unstored, False, "NTF")
     dev = device_of(tensor_in, *factors_in)
     eng = _engine.get_engine(dev)
     T = to_dev(tensor_in, dev)
@@ -417,14 +425,18 @@ def compute_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8,
 
 def one_ntf_step(unfolded_tensors, rank, in_factors, norm_tensor, update_rule, beta,
                  sparsity_coefficients, fixed_modes, normalize,
-                 alpha=0.5, delta=0.01):
+                 alpha=0.5, delta=0.01, unstored="zero"):
     """One pass over the modes (ntf.py:422-477).  `unfolded_tensors` is the reference's list of unfoldings; the tensor is
     rebuilt from the mode-0 unfolding (a plain reshape).  Returns (factors, cost).  A sparse tensor (sparse_ntf.py) is passed
     as itself, where the unfoldings are."""
     if is_sparse_tensor(unfolded_tensors):
         from . import sparse_ntf
         return sparse_ntf.one_sparse_ntf_step(unfolded_tensors, rank, in_factors, norm_tensor, update_rule, beta,
-                                              sparsity_coefficients, fixed_modes, normalize, alpha=alpha, delta=delta)
+                                              sparsity_coefficients, fixed_modes, normalize, alpha=alpha, delta=delta,
+                                              unstored=unstored)
+    if unstored != "zero":
+        from .sparse_nmf import check_unstored
+        check_unstored(unstored, False, "NTF")
     dev = device_of(*unfolded_tensors, *in_factors)
     eng = _engine.get_engine(dev)
     dims = [int(u.shape[0]) for u in unfolded_tensors]

@@ -27,11 +27,27 @@ Any other beta raises NotImplementedError before the device is touched: the MU d
 entry, stored or not.  Also refused, before anything is launched: `group=` (sharded runs), init="nndsvd" (it needs an SVD of the
 data) and ranks above 128.
 
+All of the above reads an unstored entry as a ZERO (`unstored="zero"`, the default).  `unstored="missing"` reads it as UNKNOWN:
+the factorization fits the stored entries only (a stored 0 is an observed zero) and predicts the rest.  Then numerator,
+denominator and cost of mu_betadivmin (mu.py:82-97) are all sums over stored entries, for every beta >= 0:
+
+    update_rule="mu", any beta >= 0   per factor: node-major copies -> nnf_csr_obs_f32 (num = sum x p^(beta-2) h, den = sum
+                                      p^(beta-1) h from one p per entry) -> mu_apply(F, num, den, None, beta); a row or column
+                                      without a stored entry keeps its start value through the run (nothing is known about it;
+                                      num / den = 0 / 0 there): the list of those is taken once per run from the row pointers.
+                                      Cost: sum_stored d_beta(x | p) from nnf_csr_obs_f32 (cost only) after both updates.
+
+No Grams, no small_gemm, nothing of the data's dense size.  update_rule="hals" with missing entries needs one Gram per row -- a
+different algorithm -- and raises NotImplementedError.  `observed_entries(array, mask)` builds the sparse input from a dense
+array and a boolean mask, zeros included (scipy.sparse.csr_matrix(dense) would drop them, turning observed zeros into missing
+ones).
+
 Setup, once per run (SparseData): the CSR of X and of X^T (host-side `X.T.tocsr()` for SciPy input, a stable sort by column on
 the device for a torch tensor), the chunk tables of both (Engine.csr_matrix) and ||X||^2.  The outer loop, its stopping test,
 `return_costs`, `toc` and `sweep_log` are those of compute_nmf, on `_outer_loop.Pipeline`.
 """
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -39,7 +55,7 @@ import torch
 from . import _outer_loop as _loop
 from . import dist as _dist
 from . import engine as _engine
-from ._convert import device_of, to_dev, to_dev_t, to_dev_csr, like_input
+from ._convert import device_of, to_dev, to_dev_t, to_dev_csr, like_input, observed_entries      # noqa: F401 (observed_entries: public here)
 from ._status import NMF_COST, NMF_WORDS
 from .update_rules.nnls import tic, toc
 from .utils import errors as err
@@ -47,17 +63,37 @@ from .utils import errors as err
 PIPELINE_DEPTH = 1   # outer iterations enqueued ahead of the one whose cost the host is looking at
 
 
-def check_request(rank, update_rule, beta, group=None, init=None):
+UNSTORED = ("zero", "missing")
+
+
+def check_unstored(unstored, sparse, what="NMF"):
+    """The `unstored` keyword of the drivers: "zero" or "missing", the latter with sparse data only."""
+    if unstored not in UNSTORED:
+        raise err.InvalidArgumentValue(f'Invalid value for unstored: {unstored!r} (it is "zero" or "missing")')
+    if unstored == "missing" and not sparse:
+        raise err.InvalidArgumentValue(f'unstored="missing" needs sparse data: a dense array has no unstored entries ({what}; '
+                                       f'observed_entries(array, mask) makes the sparse input of a dense array and a mask)')
+
+
+def check_request(rank, update_rule, beta, group=None, init=None, unstored="zero"):
     """Everything the sparse path refuses, said before anything is uploaded or launched."""
+    check_unstored(unstored, True)
     if update_rule not in ["hals", "mu"]:
         raise err.InvalidArgumentValue(f"Invalid update rule: {update_rule}")
-    if update_rule == "hals" and beta != 2:
+    if unstored == "missing":
+        if update_rule == "hals":
+            raise NotImplementedError('NMF with missing entries (unstored="missing") is built for the multiplicative update: hals '
+                                      'then needs one Gram matrix per row, a different algorithm; use update_rule="mu"')
+        if not (isinstance(beta, numbers.Real) and 0 <= beta < math.inf):
+            raise err.InvalidArgumentValue(f"Invalid value for beta: {beta!r} (a finite beta >= 0 is needed).")
+    elif update_rule == "hals" and beta != 2:
         raise err.InvalidArgumentValue(f"The hals is only valid for the frobenius norm, corresponding to the beta divergence with "
                                        f"beta = 2. Here, beta was set to {beta}.")
-    if update_rule == "mu" and beta not in (1, 2):
+    elif update_rule == "mu" and beta not in (1, 2):
         raise NotImplementedError(
             f"NMF of sparse data is built for beta = 1 and beta = 2: for any other beta the multiplicative update's denominator "
-            f"needs (U V)^(beta - 1) at every entry, stored or not (got beta = {beta!r}); densify the data to use it")
+            f"needs (U V)^(beta - 1) at every entry, stored or not (got beta = {beta!r}); densify the data to use it, or fit the "
+            f'stored entries only with unstored="missing"')
     if group is not None:
         raise NotImplementedError("NMF of sparse data does not run row-sharded: group= is refused")
     if init is not None and init.lower() == "nndsvd":
@@ -75,6 +111,15 @@ class SparseData:
         self.Xt = eng.csr_matrix(*to_dev_csr(data, dev, transpose=True))
         self.shape = self.X.shape
         self.normx2 = self.X.vals.double().pow(2).sum().reshape(1)
+
+    def empty_slices(self):
+        """(rows, columns) without a stored entry as boolean masks [1, m] and [1, n], None where there is none: from the row
+        pointers, once per run (unstored="missing": such a slice keeps its start value)."""
+        out = []
+        for A in (self.X, self.Xt):
+            empty = A.rowptr[1:] == A.rowptr[:-1]
+            out.append(empty[None, :] if bool(empty.any()) else None)
+        return out
 
 
 class _Buffers(_loop.StatusRing):
@@ -166,6 +211,24 @@ def _one_step_dev(eng, S, ws, Ut_in, V_in, update_rule, beta, sparsity_coefficie
     return Ut, V, nstat
 
 
+def _one_step_obs(eng, S, ws, Ut_in, V_in, beta, fixed_modes, empty):
+    """One pass of MU updates on U then V over the stored entries only (unstored="missing"), then the cost, on the device.
+    `empty`: S.empty_slices().  Returns (Ut, V, 0); the cost is left in ws.block."""
+    Ut, V = Ut_in, V_in
+    if 0 not in fixed_modes:
+        num, den = eng.csr_obs(S.X, _engine.node_major(Ut_in), _engine.node_major(V), beta)
+        Ut = eng.mu_apply(Ut_in, num, den, None, beta)
+        if empty[0] is not None:
+            Ut = torch.where(empty[0], Ut_in, Ut)
+    if 1 not in fixed_modes:
+        num, den = eng.csr_obs(S.Xt, _engine.node_major(V_in), _engine.node_major(Ut), beta)
+        V = eng.mu_apply(V_in, num, den, None, beta)
+        if empty[1] is not None:
+            V = torch.where(empty[1], V_in, V)
+    eng.csr_obs(S.X, _engine.node_major(Ut), _engine.node_major(V), beta, sums=False, cost_out=ws.block[NMF_COST:NMF_COST + 1])
+    return Ut, V, 0
+
+
 def _lists(sparsity_coefficients, fixed_modes, normalize):
     if sparsity_coefficients is None:
         sparsity_coefficients = [None, None]
@@ -180,9 +243,10 @@ def _lists(sparsity_coefficients, fixed_modes, normalize):
 
 def compute_sparse_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8, update_rule="hals", beta=2,
                        sparsity_coefficients=[None, None], fixed_modes=[], normalize=[False, False], verbose=False,
-                       return_costs=False, deterministic=False, sweep_log=None, group=None):
+                       return_costs=False, deterministic=False, sweep_log=None, group=None, unstored="zero"):
     """compute_nmf (nmf.py:284-329) for sparse `data`.  Factors come back in the kind of U_in / V_in."""
-    check_request(np.shape(U_in)[1], update_rule, beta, group=group)
+    check_request(np.shape(U_in)[1], update_rule, beta, group=group, unstored=unstored)
+    missing = unstored == "missing"
     sparsity_coefficients, fixed_modes, normalize = _lists(sparsity_coefficients, fixed_modes, normalize)
     dev = device_of(data, U_in, V_in)
     eng = _engine.get_engine(dev)
@@ -192,11 +256,15 @@ def compute_sparse_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8, update_
     ws = _Buffers(Ut.shape[0], dev, PIPELINE_DEPTH)
     retired = _loop.Retired(tol, verbose=verbose, sweep_log=sweep_log)
     main = torch.cuda.current_stream(dev)
+    empty = S.empty_slices() if missing else None
 
     def enqueue(iteration, factors):
         ws.select(iteration % ws.blocks.shape[0])
-        Ut, V, nstat = _one_step_dev(eng, S, ws, factors[0], factors[1], update_rule, beta, sparsity_coefficients, fixed_modes,
-                                     normalize, deterministic)
+        if missing:
+            Ut, V, nstat = _one_step_obs(eng, S, ws, factors[0], factors[1], beta, fixed_modes, empty)
+        else:
+            Ut, V, nstat = _one_step_dev(eng, S, ws, factors[0], factors[1], update_rule, beta, sparsity_coefficients, fixed_modes,
+                                         normalize, deterministic)
         step = _loop.Step(iteration, ws.slot, (Ut, V), nstat)
         ws.host[ws.slot].copy_(ws.block, non_blocking=True)
         step.event = main.record_event()
@@ -208,7 +276,7 @@ def compute_sparse_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8, update_
         return float(host[NMF_COST]), _loop.sweep_counts(host, step.nstat)
 
     # (the wall-clock sweep budget synchronises inside a step: nothing is gained by running ahead then)
-    loop = _loop.Pipeline(enqueue, settle, retired, [main], depth=PIPELINE_DEPTH if deterministic else 0)
+    loop = _loop.Pipeline(enqueue, settle, retired, [main], depth=PIPELINE_DEPTH if deterministic or missing else 0)
     Ut, V = loop.run(n_iter_max, (Ut, V))
     U_out, V_out = like_input(Ut.t(), U_in), like_input(V, V_in)
     if return_costs:
@@ -217,18 +285,21 @@ def compute_sparse_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8, update_
 
 
 def one_sparse_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta, sparsity_coefficients, fixed_modes, normalize,
-                        deterministic):
+                        deterministic, unstored="zero"):
     """one_nmf_step (nmf.py:387-458) for sparse `data`.  Returns (U, V, cost).  The setup (transpose, chunk tables) is redone at
     every call: a loop belongs in compute_nmf."""
-    check_request(np.shape(U_in)[1], update_rule, beta)
+    check_request(np.shape(U_in)[1], update_rule, beta, unstored=unstored)
     sparsity_coefficients, fixed_modes, normalize = _lists(sparsity_coefficients, fixed_modes, normalize)
     dev = device_of(data, U_in, V_in)
     eng = _engine.get_engine(dev)
     S = SparseData(eng, data, dev)
     Ut, V = to_dev_t(U_in, dev), to_dev(V_in, dev)
     ws = _Buffers(Ut.shape[0], dev, 0)
-    Ut2, V2, nstat = _one_step_dev(eng, S, ws, Ut, V, update_rule, beta, sparsity_coefficients, fixed_modes, normalize,
-                                   deterministic)
+    if unstored == "missing":
+        Ut2, V2, nstat = _one_step_obs(eng, S, ws, Ut, V, beta, fixed_modes, S.empty_slices())
+    else:
+        Ut2, V2, nstat = _one_step_dev(eng, S, ws, Ut, V, update_rule, beta, sparsity_coefficients, fixed_modes, normalize,
+                                       deterministic)
     host = ws.block.cpu()
     _loop.check_status(host, nstat)
     return like_input(Ut2.t(), U_in), like_input(V2, V_in), float(host[NMF_COST])

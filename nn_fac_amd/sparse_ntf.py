@@ -34,18 +34,33 @@ then needs P^(beta - 1) at every entry, stored or not), orders above 5 (NotImple
 business: it takes scipy.sparse and torch sparse-CSR data), init="nndsvd" (an SVD of every unfolding), `group=` (sharded runs)
 and ranks above 128 (EngineError).
 
+All of the above reads an unstored entry as a ZERO (`unstored="zero"`, the default).  `unstored="missing"` reads it as UNKNOWN:
+the factorization fits the stored entries only (a stored 0 is an observed zero) and predicts the rest; numerator, denominator
+and cost of mu_betadivmin are then all sums over stored entries, for every beta >= 0:
+
+    update_rule="mu", any beta >= 0   per mode: node-major copies -> nnf_sptensor_obs_f32 (num = sum x p^(beta-2) h, den = sum
+                                      p^(beta-1) h from one p per entry) -> mu_apply(F, num, den, None, beta); a slice without
+                                      a stored entry keeps its start value through the run (num / den = 0 / 0 there): the list
+                                      of those is taken once per run from the modes' pointers.  Cost: sum_stored d_beta(x | p)
+                                      from nnf_sptensor_obs_f32 (cost only) after the last mode, divided by ||T||^2 as above.
+
+No Grams, no small_gemm, nothing of the tensor's dense size.  update_rule="hals" with missing entries needs one Gram per slice
+-- a different algorithm -- and raises NotImplementedError.  `observed_entries(array, mask)` builds the SparseCOO of a dense
+array and a boolean mask, zeros included.
+
 Setup, once per run (SparseTensorData): the canonical coordinate list (_convert.to_dev_coo), its N sorted copies with their chunk
 tables (Engine.sparse_tensor) and ||T||^2.  The outer loop, its stopping test, `return_costs`, `verbose` and `sweep_log` are those
 of compute_ntf, on `_outer_loop.Pipeline`.
 """
 import math
+import numbers
 
 import numpy as np
 import torch
 
 from . import _outer_loop as _loop
 from . import engine as _engine
-from ._convert import SparseCOO, device_of, is_sparse_tensor, to_dev_coo, to_dev_t, like_input      # noqa: F401 (SparseCOO: public here)
+from ._convert import SparseCOO, device_of, is_sparse_tensor, observed_entries, to_dev_coo, to_dev_t, like_input      # noqa: F401 (SparseCOO, observed_entries: public here)
 from .update_rules.nnls import tic, toc, timed_budget
 from .utils import errors as err
 
@@ -53,17 +68,26 @@ PIPELINE_DEPTH = 1   # outer iterations enqueued ahead of the one whose cost the
 MIN_ORDER, MAX_ORDER = _engine.SparseTensor.MIN_ORDER, _engine.SparseTensor.MAX_ORDER
 
 
-def check_request(rank, update_rule, beta, order, group=None, init=None):
+def check_request(rank, update_rule, beta, order, group=None, init=None, unstored="zero"):
     """Everything the sparse path refuses, said before anything is uploaded or launched."""
+    from .sparse_nmf import check_unstored
+    check_unstored(unstored, True, "NTF")
     if update_rule not in ["hals", "mu"]:
         raise err.InvalidArgumentValue(f"Invalid update rule: {update_rule}")
-    if update_rule == "hals" and beta != 2:
+    if unstored == "missing":
+        if update_rule == "hals":
+            raise NotImplementedError('NTF with missing entries (unstored="missing") is built for the multiplicative update: hals '
+                                      'then needs one Gram matrix per slice, a different algorithm; use update_rule="mu"')
+        if not (isinstance(beta, numbers.Real) and 0 <= beta < math.inf):
+            raise err.InvalidArgumentValue(f"Invalid value for beta: {beta!r} (a finite beta >= 0 is needed).")
+    elif update_rule == "hals" and beta != 2:
         raise err.InvalidArgumentValue(f"The hals is only valid for the frobenius norm, corresponding to the beta divergence with "
                                        f"beta = 2. Here, beta was set to {beta}.")
-    if update_rule == "mu" and beta not in (1, 2):
+    elif update_rule == "mu" and beta not in (1, 2):
         raise NotImplementedError(
             f"NTF of sparse data is built for beta = 1 and beta = 2: for any other beta the multiplicative update's denominator "
-            f"needs the model to the power beta - 1 at every entry, stored or not (got beta = {beta!r}); densify the data to use it")
+            f"needs the model to the power beta - 1 at every entry, stored or not (got beta = {beta!r}); densify the data to use it, "
+            f'or fit the stored entries only with unstored="missing"')
     if order < MIN_ORDER:
         raise NotImplementedError(f"NTF needs a tensor of order >= 3, got order {order}: a sparse matrix is nmf's business (it takes "
                                   f"scipy.sparse matrices and torch sparse-CSR tensors)")
@@ -92,6 +116,15 @@ class SparseTensorData:
         self.S = eng.sparse_tensor(indices, values, shape)
         self.shape, self.nway = self.S.shape, self.S.order
         self.normx2 = values.double().pow(2).sum().reshape(1)
+
+    def empty_slices(self):
+        """Per mode, the slices without a stored entry as a boolean mask [1, extent], None where there is none: from the modes'
+        pointers, once per run (unstored="missing": such a slice keeps its start value)."""
+        out = []
+        for M in self.S.modes:
+            empty = M.ptr[1:] == M.ptr[:-1]
+            out.append(empty[None, :] if bool(empty.any()) else None)
+        return out
 
 
 class _Buffers(_loop.StatusRing):
@@ -209,6 +242,24 @@ def _one_step_dev(eng, D, ws, Ft_in, update_rule, beta, sparsity_coefficients, f
     return Ft, nstat
 
 
+def _one_step_obs(eng, D, ws, Ft_in, beta, fixed_modes, empty):
+    """One pass of MU updates over the modes on the stored entries only (unstored="missing"), then the cost, on the device.
+    `empty`: D.empty_slices().  Returns (factors, 0); the cost is left in ws.block."""
+    Ft = list(Ft_in)
+    S, N = D.S, D.nway
+    for mode in [m for m in range(N) if m not in fixed_modes]:
+        gathered = [_engine.node_major(f) for f in _others(Ft, mode)]
+        num, den = eng.sptensor_obs(S, mode, _engine.node_major(Ft[mode]), gathered, beta)
+        new = eng.mu_apply(Ft[mode], num, den, None, beta)
+        Ft[mode] = new if empty[mode] is None else torch.where(empty[mode], Ft[mode], new)
+    cost = ws.block[ws.cost_at:ws.cost_at + 1]
+    mode = N - 1
+    eng.sptensor_obs(S, mode, _engine.node_major(Ft[mode]), [_engine.node_major(f) for f in _others(Ft, mode)], beta, sums=False,
+                     cost_out=cost)
+    cost.div_(D.normx2)                                   # (ntf.py:475)
+    return Ft, 0
+
+
 def _lists(nb_modes, sparsity_coefficients, fixed_modes, normalize):
     """The defaults of compute_ntf (ntf.py:292-301)."""
     if sparsity_coefficients is None or len(sparsity_coefficients) != nb_modes:
@@ -230,10 +281,12 @@ def _check_factors(shape, factors):
 
 def compute_sparse_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8, update_rule="hals", beta=2,
                        sparsity_coefficients=[], fixed_modes=[], normalize=[], verbose=False, return_costs=False, alpha=0.5,
-                       delta=0.01, sweep_log=None, group=None):
+                       delta=0.01, sweep_log=None, group=None, unstored="zero"):
     """compute_ntf (ntf.py:288-344) for a sparse `tensor_in`.  Factors come back in the kind of `factors_in`."""
     shape = tuple(int(s) for s in tensor_in.shape)
-    check_request(np.shape(factors_in[0])[1] if len(factors_in) else rank, update_rule, beta, len(shape), group=group)
+    check_request(np.shape(factors_in[0])[1] if len(factors_in) else rank, update_rule, beta, len(shape), group=group,
+                  unstored=unstored)
+    missing = unstored == "missing"
     _check_factors(shape, factors_in)
     sparsity_coefficients, fixed_modes, normalize = _lists(len(shape), sparsity_coefficients, fixed_modes, normalize)
     dev = _device_of(tensor_in, factors_in)
@@ -244,10 +297,15 @@ def compute_sparse_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8, up
     ws = _Buffers(eng, D.nway, dev, PIPELINE_DEPTH)
     retired = _loop.Retired(tol, verbose=verbose, sweep_log=sweep_log)
     main = torch.cuda.current_stream(dev)
+    empty = D.empty_slices() if missing else None
 
     def enqueue(iteration, factors):
         ws.select(iteration % ws.blocks.shape[0])
-        Ft, nstat = _one_step_dev(eng, D, ws, factors, update_rule, beta, sparsity_coefficients, fixed_modes, normalize, alpha, delta)
+        if missing:
+            Ft, nstat = _one_step_obs(eng, D, ws, factors, beta, fixed_modes, empty)
+        else:
+            Ft, nstat = _one_step_dev(eng, D, ws, factors, update_rule, beta, sparsity_coefficients, fixed_modes, normalize, alpha,
+                                      delta)
         step = _loop.Step(iteration, ws.slot, Ft, nstat)
         ws.host[ws.slot].copy_(ws.block, non_blocking=True)
         step.event = main.record_event()
@@ -259,7 +317,7 @@ def compute_sparse_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8, up
         return float(host[ws.cost_at]), _loop.sweep_counts(host, step.nstat)
 
     # (the wall-clock sweep budget synchronises inside a step: nothing is gained by running ahead then)
-    loop = _loop.Pipeline(enqueue, settle, retired, [main], depth=PIPELINE_DEPTH if deterministic else 0)
+    loop = _loop.Pipeline(enqueue, settle, retired, [main], depth=PIPELINE_DEPTH if deterministic or missing else 0)
     Ft = loop.run(n_iter_max, Ft)
     factors = [like_input(f.t(), factors_in[i]) for i, f in enumerate(Ft)]
     if return_costs:
@@ -268,18 +326,21 @@ def compute_sparse_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8, up
 
 
 def one_sparse_ntf_step(tensor_in, rank, in_factors, norm_tensor, update_rule, beta, sparsity_coefficients, fixed_modes, normalize,
-                        alpha=0.5, delta=0.01):
+                        alpha=0.5, delta=0.01, unstored="zero"):
     """one_ntf_step (ntf.py:422-477) for a sparse tensor, passed where the reference takes the unfoldings.  Returns (factors,
     cost).  The setup (sorted copies, chunk tables) is redone at every call: a loop belongs in compute_ntf."""
     shape = tuple(int(s) for s in tensor_in.shape)
-    check_request(np.shape(in_factors[0])[1] if len(in_factors) else rank, update_rule, beta, len(shape))
+    check_request(np.shape(in_factors[0])[1] if len(in_factors) else rank, update_rule, beta, len(shape), unstored=unstored)
     _check_factors(shape, in_factors)
     dev = _device_of(tensor_in, in_factors)
     eng = _engine.get_engine(dev)
     D = SparseTensorData(eng, tensor_in, dev)
     Ft = [to_dev_t(f, dev) for f in in_factors]
     ws = _Buffers(eng, D.nway, dev, 0)
-    Ft, nstat = _one_step_dev(eng, D, ws, Ft, update_rule, beta, list(sparsity_coefficients), fixed_modes, normalize, alpha, delta)
+    if unstored == "missing":
+        Ft, nstat = _one_step_obs(eng, D, ws, Ft, beta, fixed_modes or [], D.empty_slices())
+    else:
+        Ft, nstat = _one_step_dev(eng, D, ws, Ft, update_rule, beta, list(sparsity_coefficients), fixed_modes, normalize, alpha, delta)
     host = ws.block.cpu()
     _loop.check_status(host, nstat)
     return [like_input(f.t(), in_factors[i]) for i, f in enumerate(Ft)], float(host[ws.cost_at])

@@ -79,6 +79,11 @@
 //                                     Answer: the "[nnf plan] sptensor_..." line of that call (sptensor_mttkrp: out=1 cost=0;
 //                                     sptensor_kl otherwise) with U = sptensor_unroll(L, ng), then ng=, carved= and chunks=, or
 //                                     "status=<code>" (the argument checks of the entries included).
+//                        The observed-entries kernels' plan (k_sparse_plan.h: sparse_obs_make_plan), key=value only:
+//                          obs <CUs> r= ng= lens=<len0,len1,...> [ch=] [out=] [cost=] [ws=]     as `sptensor`, with ng = 1 for a CSR
+//                                     matrix (1 .. 4) and out: the two sums (numerator and denominator) are asked for.  Answer:
+//                                     the "[nnf plan] csr_obs ..." (ng = 1) or "[nnf plan] sptensor_obs ..." line of that call
+//                                     (part_bytes: both workspace arrays), then ng=, carved= and chunks=, or "status=<code>".
 //   nnf_plan shm         the dynamic LDS the fused MU launchers ask for at ranks 65 .. 128, one line per (MT, form):
 //                        "<MT> <REM> <KL|GEN> <bytes>"   (r = 16 MT + REM, the largest rank of the split)
 //
@@ -190,7 +195,7 @@ static int answer_simplex(const char* line) {
     return 0;
 }
 
-static int answer_sparse(const char* line, bool tensor) {
+static int answer_sparse(const char* line, bool tensor, bool obs = false) {
     int C = 0, used = 0;
     if (sscanf(line, "%*s %d%n", &C, &used) != 1 || C < 1) return 2;
     const char* rest = line + used;
@@ -210,7 +215,8 @@ static int answer_sparse(const char* line, bool tensor) {
     const bool out = key_of(rest, "out", 1) != 0, cost = key_of(rest, "cost", 0) != 0;
     const int ng = (int)key_of(rest, "ng", 0);
     // (the argument checks of nnf_csr_args_ok, k_sparse.hip, and of sptensor_args_ok, k_sptensor.hip)
-    if (nrows < 1 || r < 1 || !sparse_chunk_ok(ch) || (!out && !cost) || (tensor && (ng < SPTENSOR_NG_MIN || ng > SPTENSOR_NG_MAX))) {
+    if (nrows < 1 || r < 1 || !sparse_chunk_ok(ch) || (!out && !cost) || (tensor && (ng < SPTENSOR_NG_MIN || ng > SPTENSOR_NG_MAX)) ||
+        (obs && (ng < SPARSE_OBS_NG_MIN || ng > SPTENSOR_NG_MAX))) {
         printf("status=%d\n", NNF_ERR_ARG);
         return 0;
     }
@@ -224,14 +230,16 @@ static int answer_sparse(const char* line, bool tensor) {
     }
     const int64_t nchunks = rowchunk.back();
     const int rr = (int)(r > 1000000 ? 1000000 : r);
-    const sparse_plan p = tensor ? sptensor_make_plan(rr, ng, nrows, nchunks, out, cost, (size_t)ws)
-                                 : sparse_make_plan(rr, nrows, nchunks, out, cost, (size_t)ws);
+    const sparse_plan p = obs      ? sparse_obs_make_plan(rr, ng, nrows, nchunks, out, cost, (size_t)ws)
+                          : tensor ? sptensor_make_plan(rr, ng, nrows, nchunks, out, cost, (size_t)ws)
+                                   : sparse_make_plan(rr, nrows, nchunks, out, cost, (size_t)ws);
     if (p.status != NNF_OK) {
         printf("status=%d\n", p.status);
         return 0;
     }
     nnf_ws_cursor cur(nullptr, (size_t)ws);      // the launcher's carves, in its order
-    if (nchunks > 0 && out) cur.reserve(p.part_bytes);
+    if (nchunks > 0 && out && obs) cur.reserve(p.part_bytes / 2), cur.reserve(p.part_bytes / 2);      // (numerator, denominator)
+    else if (nchunks > 0 && out) cur.reserve(p.part_bytes);
     if (nchunks > 0 && cost) cur.reserve(p.cost_bytes);
     std::string chunks;
     for (int64_t c = 0; c < nchunks; ++c) {
@@ -242,8 +250,8 @@ static int answer_sparse(const char* line, bool tensor) {
         chunks += one;
     }
     std::string more = " carved=" + std::to_string(cur.off) + " chunks=" + (nchunks ? chunks : std::string("-"));
-    if (tensor) more = " ng=" + std::to_string(ng) + more;
-    const char* what = tensor ? (out && !cost ? "sptensor_mttkrp" : "sptensor_kl") : (out && !cost ? "csr_xf" : "csr_kl");
+    if (tensor || obs) more = " ng=" + std::to_string(ng) + more;
+    const char* what = obs ? (ng == 1 ? "csr_obs" : "sptensor_obs") : tensor ? (out && !cost ? "sptensor_mttkrp" : "sptensor_kl") : (out && !cost ? "csr_xf" : "csr_kl");
     sparse_report(stdout, what, (int)r, nrows, nnz, nchunks, ch, p, more.c_str());
     return 0;
 }
@@ -278,6 +286,13 @@ int main(int argc, char** argv) {
         }
         if (sscanf(line, "%31s", name) == 1 && (strcmp(name, "sparse") == 0 || strcmp(name, "sptensor") == 0)) {
             if (answer_sparse(line, name[1] == 'p' && name[2] == 't') != 0) {
+                fprintf(stderr, "nnf_plan: bad case line: %s", line);
+                return 2;
+            }
+            continue;
+        }
+        if (sscanf(line, "%31s", name) == 1 && strcmp(name, "obs") == 0) {
+            if (answer_sparse(line, false, true) != 0) {
                 fprintf(stderr, "nnf_plan: bad case line: %s", line);
                 return 2;
             }

@@ -6,6 +6,11 @@ and stays as it is).  One JSON line per measurement on stdout.
                                                         with --dense also the dense driver's step on the densified matrix
     python tools/sparse_bench.py --set large            10^6 x 4000, ranks 50 and 100, 0.1 / 1 / 5 %
     python tools/sparse_bench.py --chunks 128,256,...   the V-side product (rows of X^T: the skewed side) of one case per chunk size
+    python tools/sparse_bench.py --set small --observed  the observed-entries leg instead (unstored="missing"): csr_obs (numerator and
+                                                        denominator in one pass) at beta = 1, 2 and 0.5 next to csr_xf and csr_kl
+                                                        (numerator only) on the same entries, with `fused_over_two_passes` =
+                                                        t(csr_obs) / (t(csr_kl) + t(csr_xf)) -- what two separate passes would cost --
+                                                        and the ms/step of a missing-entries MU run next to the stored-zero KL step
     python tools/sparse_bench.py --memory               nmf(scipy_csr, 50, ...) for HALS and MU beta = 1 on 10^6 x 4000 at 1 %: the peak of
                                                         torch's allocator against the 16 GB of a dense copy
 
@@ -83,6 +88,44 @@ def kernels(eng, S, r, reps, case):
                  gbytes_per_s=(nbytes + extra) / med / 1e6, **row_stats(A), **case)
 
 
+def observed(eng, S, r, reps, nsteps, case):
+    """The observed-entries leg: csr_obs (sums form) against the two passes it fuses, then the steps."""
+    dev = S.X.device
+    m, n = S.shape
+    Ut, V = torch.rand(r, m, device=dev) + 0.05, torch.rand(r, n, device=dev) + 0.05
+    Un, Vn = _engine.node_major(Ut), _engine.node_major(V)
+    ldn = Un.stride(0)
+    for name, A, own, F in (("u_side", S.X, Un, Vn), ("v_side", S.Xt, Vn, Un)):
+        base = {}
+        for kern, fn in (("csr_xf", lambda: eng.csr_xf(A, F)), ("csr_kl_num", lambda: eng.csr_kl(A, own, F))):
+            base[kern], lo, hi = timed(fn, reps)
+            emit(kind="observed", kernel=kern, side=name, ms_median=base[kern], ms_min=lo, ms_max=hi, **row_stats(A), **case)
+        nbytes = (8 + 4 * ldn) * A.nnz + (2 * 4 * r + 4 * ldn) * A.nrows
+        for beta in (1, 2, 0.5):
+            med, lo, hi = timed(lambda: eng.csr_obs(A, own, F, beta), reps)
+            emit(kind="observed", kernel="csr_obs", side=name, beta=beta, ms_median=med, ms_min=lo, ms_max=hi, bytes=nbytes,
+                 gbytes_per_s=nbytes / med / 1e6, two_passes_ms=base["csr_kl_num"] + base["csr_xf"],
+                 fused_over_two_passes=med / (base["csr_kl_num"] + base["csr_xf"]), **row_stats(A), **case)
+    ws = sparse_nmf._Buffers(r, dev, 0)
+    empty = S.empty_slices()
+
+    def run(step):
+        Ut, V = torch.rand(r, m, device=dev) + 0.05, torch.rand(r, n, device=dev) + 0.05
+        for _ in range(2):
+            Ut, V = step(Ut, V)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(nsteps):
+            Ut, V = step(Ut, V)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / nsteps
+    ms = run(lambda Ut, V: sparse_nmf._one_step_dev(eng, S, ws, Ut, V, "mu", 1, [None, None], [], [False, False], True)[:2])
+    emit(kind="step", driver="sparse", unstored="zero", rule="mu", beta=1, ms_per_step=ms, steps=nsteps, **case)
+    for beta in (1, 2, 0.5):
+        ms = run(lambda Ut, V: sparse_nmf._one_step_obs(eng, S, ws, Ut, V, beta, [], empty)[:2])
+        emit(kind="step", driver="sparse", unstored="missing", rule="mu", beta=beta, ms_per_step=ms, steps=nsteps, **case)
+
+
 def steps(eng, S, r, nsteps, case, dense=None):
     dev = S.X.device
     m, n = S.shape
@@ -122,6 +165,7 @@ def main():
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--chunks", default=None)
     ap.add_argument("--memory", action="store_true")
+    ap.add_argument("--observed", action="store_true")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--steps", type=int, default=5)
     a = ap.parse_args()
@@ -142,6 +186,9 @@ def main():
                 dense = T.to_dense() if (a.dense and a.set == "small") else None
                 for r in ranks:
                     case = dict(m=m, n=n, r=r, density=d, pattern=pat, nnz=S.X.nnz)
+                    if a.observed:
+                        observed(eng, S, r, a.reps, a.steps, case)
+                        continue
                     kernels(eng, S, r, a.reps, case)
                     steps(eng, S, r, a.steps, case, dense=dense)
                 del S, T, dense

@@ -6,6 +6,10 @@
                                                         ranks 16, 50 and 100, 10^7 stored entries, uniform and power-law indices
     python tools/sptensor_bench.py --nnz 1000000 --orders 3 --ranks 50 --patterns uniform      a smaller run
 
+    python tools/sptensor_bench.py --observed ...       also sptensor_obs (numerator and denominator in one pass, unstored="missing")
+                                                        at beta = 1, 2 and 0.5, with `fused_over_two_passes` = its time over
+                                                        t(sptensor_kl, numerator only) + t(sptensor_mttkrp) of the same mode
+
 Per tensor and rank: sptensor_mttkrp and sptensor_kl (numerator and cost) of every mode, and csr_xf on the matrix of the first two
 extents with the same number of stored entries drawn the same way.  Kernel times are device events around one engine call (gather
 kernel + the sum-and-transpose pass), the median of `--reps` calls after two warm-up calls.  Bytes: (4 N + ng 4 ldn) per stored
@@ -78,6 +82,7 @@ def main():
     ap.add_argument("--ranks", default="16,50,100")
     ap.add_argument("--patterns", default="uniform,powerlaw")
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--observed", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("sptensor_bench: no ROCm device (there is nothing to time without one)")
@@ -108,6 +113,17 @@ def main():
                 for mode, M in enumerate(S.modes):
                     others = [f for m, f in enumerate(F) if m != mode]
                     entry = 4 * order + (order - 1) * 4 * ldn
+                    if a.observed:
+                        mt, _, _ = timed(lambda: eng.sptensor_mttkrp(S, mode, others), a.reps)
+                        kl, _, _ = timed(lambda: eng.sptensor_kl(S, mode, F[mode], others), a.reps)
+                        emit(kind="observed", kernel="sptensor_mttkrp", mode=mode, ms_median=mt, nnz=M.nnz, **case)
+                        emit(kind="observed", kernel="sptensor_kl_num", mode=mode, ms_median=kl, nnz=M.nnz, **case)
+                        for beta in (1, 2, 0.5):
+                            med, lo, hi = timed(lambda: eng.sptensor_obs(S, mode, F[mode], others, beta), a.reps)
+                            emit(kind="observed", kernel="sptensor_obs", mode=mode, beta=beta, ms_median=med, ms_min=lo, ms_max=hi,
+                                 nnz=M.nnz, two_passes_ms=kl + mt, fused_over_two_passes=med / (kl + mt),
+                                 **slice_stats(M.ptr, M.nchunks, M.ch), **case)
+                        continue
                     for kern, fn, extra in (("sptensor_mttkrp", lambda: eng.sptensor_mttkrp(S, mode, others), 0),
                                             ("sptensor_kl", lambda: eng.sptensor_kl(S, mode, F[mode], others, cost_out=cost),
                                              4 * ldn * M.extent)):
