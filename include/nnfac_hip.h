@@ -630,6 +630,33 @@ int nnf_sptensor_obs_f32(nnf_ctx* ctx, const int64_t* ptr, const int32_t* idx, c
                          const int64_t* extents, int64_t ldn, const float* Own_n, int64_t ldo_n, int r, double beta, float* num,
                          int64_t ldnum, float* den, int64_t ldden, double* cost_f64, void* stream);
 
+/* ---- weighted NMF on dense data: a weight per entry next to X (nn_fac_amd/weighted_nmf.py) -----------------------------------
+ * Wg (m x n, pitch ldw >= n, independent of ldx) holds finite weights >= 0; the fit minimises sum_ij Wg[i,j] d_beta(X[i,j] |
+ * (U V)[i,j]).  A 0/1 mask is the special case; Wg == 1 everywhere is plain mu_betadivmin.  With P = U V (never written):
+ *   left :  num[k,i] = sum_j Wg[i,j] X[i,j] P[i,j]^(beta-2) V[k,j]     den[k,i] = sum_j Wg[i,j] P[i,j]^(beta-1) V[k,j]     (r x m)
+ *   right:  num[k,j] = sum_i Wg[i,j] X[i,j] P[i,j]^(beta-2) U[i,k]     den[k,j] = sum_i Wg[i,j] P[i,j]^(beta-1) U[i,k]     (r x n)
+ *   cost :  *out_f64 = sum_ij Wg[i,j] d_beta(X[i,j] | P[i,j])          (not normalised; 1/2 (x - p)^2 at beta = 2, as nnf_betadiv_f32)
+ * The update itself is nnf_mu_apply_f32(F, num, den, NULL, beta).  The fused two-MFMA kernels of nnf_mu_left_f32 /
+ * nnf_mu_right_f32 in their two-accumulator form, at every beta (beta = 1 and beta = 2 have no shortcut under weights: r1 = w x /
+ * p, r2 = w and r1 = w x, r2 = w p per entry; any other beta the log2 / exp2 pair times w), with the general-beta launch plans; the
+ * 32-bit offset bounds of the plans hold for max(ldx, ldw); 16-byte loads when X and Wg are both 16-byte aligned with pitches in
+ * fours.  Where Wg[i,j] == 0 the entry adds exactly 0 to num, den and the cost WHATEVER X[i,j] holds, NaN and +-Inf included (a
+ * select, not a product: Wg = !isnan(X) is a valid mask).  Under a positive weight a NaN or Inf of X goes through as in the
+ * unweighted kernels, and x = 0 is an observed zero (nothing to num, its term to den, d_beta(0 | p) to the cost).  A row of U (a
+ * column of V) whose weights are all zero gets num = den = 0 exactly: the caller keeps that factor row (0 / 0 otherwise).  The
+ * right update adds its row splits in a fixed order (two calls are bitwise equal).  Any beta >= 0.  Nothing is launched and the
+ * outputs are untouched on: r > NNF_MAX_RANK (NNF_ERR_UNSUPPORTED); a null pointer, a pitch below the row length, beta < 0 or
+ * NaN (NNF_ERR_ARG); a workspace that cannot hold one pair of r x n slabs (right update: NNF_ERR_WORKSPACE). */
+int nnf_mu_left_w_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg, int64_t ldw,
+                      const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* num, int64_t ldnum,
+                      float* den, int64_t ldden, void* stream);
+int nnf_mu_right_w_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg, int64_t ldw,
+                       const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* num, int64_t ldnum,
+                       float* den, int64_t ldden, void* stream);
+int nnf_betadiv_w_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg, int64_t ldw,
+                      const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, double* out_f64,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,9 @@ SIGNATURES = {
                                _i64, _p, _p]),
     "nnf_sptensor_obs_f32": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _i64, _i32, _f64, _p,
                                     _i64, _p, _i64, _p, _p]),
+    "nnf_mu_left_w_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _f64, _p, _i64, _p, _i64, _p]),
+    "nnf_mu_right_w_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _f64, _p, _i64, _p, _i64, _p]),
+    "nnf_betadiv_w_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _f64, _p, _p]),
 }
 
 _lib = None

@@ -39,14 +39,17 @@ __global__ __launch_bounds__(256) void nnf_cost_prepv_kernel(const float* __rest
 // PIN (ranks above 128, walked in chunks of <= 128): the model of the EARLIER rank chunks, m x n with row stride ldr in Pin, is
 // added to this chunk's product before the element-wise part -- read one block ahead like X (Pin may be R1: a lane reads its
 // own elements of a block before it writes them).
-template <int OP, bool VEC, int NV, bool PIN = false>   // NV = float4 pieces of a V image per thread: 4 up to r = 64, 8 up to r = 128
-__global__ __launch_bounds__(256, PIN ? 2 : 3) void nnf_cost_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
+// WT (nnf_betadiv_w_f32): a weight per entry, streamed like X through a resource and pitch of its own; the term of an entry is
+// its weight times the divergence, and exactly 0 where the weight is 0, whatever X holds there (a select: 0 * NaN is NaN).
+template <int OP, bool VEC, int NV, bool PIN = false, bool WT = false>   // NV = float4 pieces of a V image per thread: 4 up to r = 64, 8 up to r = 128
+__global__ __launch_bounds__(256, PIN || WT ? 2 : 3) void nnf_cost_kernel(const float* __restrict__ X, int64_t m, int64_t n, int64_t ldx,
                                                           const float* __restrict__ Ut, int64_t ldu,
                                                           const f32x4* __restrict__ Vf, int r,
                                                           float beta, double* __restrict__ partial,
                                                           const float* __restrict__ Ub, int64_t ldub, int64_t nbu,
                                                           float* __restrict__ R1, float* __restrict__ R2, int64_t ldr,
-                                                          int u_vec_ok, int vdb, const float* Pin = nullptr) {
+                                                          int u_vec_ok, int vdb, const float* Pin = nullptr,
+                                                          const float* __restrict__ Wg = nullptr, int64_t ldw = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int KS = (r + 3) >> 2;                               // k-steps of 4
     float* ldsU = reinterpret_cast<float*>(smem);              // [wave 4][rt 2][KS][64]
@@ -181,8 +184,23 @@ __global__ __launch_bounds__(256, PIN ? 2 : 3) void nnf_cost_kernel(const float*
         ldp4 = (int)(ldr * 4);
         voffp = (int)(((int64_t)4 * g * ldr + 4 * jj) * 4);
     }
+    f32x4 wb[WT ? 2 : 1][WT ? 4 : 1];   // the same elements of Wg
+    rsrc_t rsw = rs;
+    int ldw4 = 0, voffw = 0;
+    if constexpr (WT) {
+        rsw = nnf_make_rsrc(Wg + (rows > 0 ? i0w : 0) * ldw, rows > 0 ? (uint32_t)(((rows - 1) * ldw + n) * 4) : 0u);
+        ldw4 = (int)(ldw * 4);
+        voffw = (int)(((int64_t)4 * g * ldw + 4 * jj) * 4);
+    }
     auto xload = [&](int blk) {
         const int vo = (blk < nblk) ? voff : (int)0x7ffffff0;
+        if constexpr (WT) {
+            const int vw = (blk < nblk) ? voffw : (int)0x7ffffff0;
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) wb[rt][reg] = nnf_bload4<VEC>(rsw, vw, (16 * rt + reg) * ldw4 + 256 * blk);
+        }
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -301,6 +319,19 @@ __global__ __launch_bounds__(256, PIN ? 2 : 3) void nnf_cost_kernel(const float*
                         }
                     }
                 }
+        } else if constexpr (WT) {
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const bool rowok = 16 * rt + 4 * g + reg < rows;   // rows past the end of the matrix
+#pragma unroll
+                    for (int cc = 0; cc < 4; ++cc) {
+                        const float wv = wb[rt][reg][cc];
+                        const float term = wv * nnf_cost_term<OP>(xb[rt][reg][cc], acc[rt][cc][reg], beta);
+                        loc += (rowok && cc < jrem && wv != 0.f) ? term : 0.f;
+                    }
+                }
         } else
         if (rows == 32 && 64 * (int64_t)(blk + 1) <= n) {   // interior block (wave-uniform): no edge masks
 #pragma unroll
@@ -343,6 +374,7 @@ struct cost_request {
     float* R1 = nullptr; float* R2 = nullptr; int64_t ldr = 0;   // ratio passes: the outputs, m x n with row stride ldr; NNF_PROD: R1
     const float* Pin = nullptr;            // the model of the earlier rank chunks (row stride ldr), added to this pass's product
     size_t ws_cap = 0;                     // != 0: the workspace ends here (its tail holds that model)
+    const float* Wg = nullptr; int64_t ldw = 0;   // weighted cost (r <= NNF_MAX_RANK): m x n weights, streamed next to X
 };
 
 template <int OP>
@@ -359,10 +391,10 @@ static int launch_cost(nnf_ctx* ctx, const cost_request& q, hipStream_t st) {
     const nnf_cost_plan pl = nnf_plan_cost(ctx->num_cus, m, n, r, q.Ub != nullptr, forced, q.Pin != nullptr, OP == NNF_PROD, cur.remaining());
     if (pl.status != NNF_OK) return pl.status;
     // (a later rank chunk of a rank above 128, launch_cost_any_rank, reads the model next to X: one load width for both)
-    const bool vec = x_vec_ok(X, ldx) && (q.Pin == nullptr || x_vec_ok(q.Pin, q.ldr));
+    const bool vec = x_vec_ok(X, ldx) && (q.Pin == nullptr || x_vec_ok(q.Pin, q.ldr)) && (q.Wg == nullptr || x_vec_ok(q.Wg, q.ldw));
     if (nnf_plan_debug()) {
         static const char* const ops[] = {"frob", "kl", "is", "gen", "ratio_kl", "ratio_gen", "prod"};
-        nnf_report_cost(stderr, m, n, r, ops[OP], vec, q.Pin != nullptr, q.Ub ? q.nbu : 0, pl);
+        nnf_report_cost(stderr, m, n, r, ops[OP], vec, q.Pin != nullptr, q.Ub ? q.nbu : 0, pl, q.Wg ? " weighted=1" : "");
     }
     const int grid = pl.grid, csplit = pl.csplit, KS = pl.KS, vdb = pl.vdb, u_vec_ok = x_vec_ok(q.Ut, q.ldu) ? 1 : 0;
     const size_t shm = pl.shm;
@@ -376,17 +408,24 @@ static int launch_cost(nnf_ctx* ctx, const cost_request& q, hipStream_t st) {
         hipLaunchKernelGGL(nnf_cost_prepv_kernel, dim3((int)pg), dim3(256), 0, st, q.V, q.ldv, r, n, KS, Vf, vf_total);
         NNF_CHECK_LAUNCH();
     }
-    const auto launch = [&](auto vv, auto nn, auto pin) {
-        const auto kernel = nnf_cost_kernel<OP, decltype(vv)::value, decltype(nn)::value, decltype(pin)::value>;
+    const auto launch = [&](auto vv, auto nn, auto pin, auto wt) {
+        const auto kernel = nnf_cost_kernel<OP, decltype(vv)::value, decltype(nn)::value, decltype(pin)::value, decltype(wt)::value>;
         if (shm > 48 * 1024)
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
         hipLaunchKernelGGL(kernel, dim3(grid, csplit), dim3(256), shm, st, X, m, n, ldx, q.Ut, q.ldu, Vf, r, q.beta, partial, q.Ub, q.ldub,
-                           q.nbu, q.R1, q.R2, q.ldr, u_vec_ok, vdb, q.Pin);
+                           q.nbu, q.R1, q.R2, q.ldr, u_vec_ok, vdb, q.Pin, q.Wg, q.ldw);
     };
     const auto pick = [&](auto vv) {   // per load width: one instance that reads a model back, one that writes it, two for the rest
-        if (q.Pin != nullptr) launch(vv, nnf_int<8>{}, std::true_type{});
-        else if (OP == NNF_PROD || pl.NN != 4) launch(vv, nnf_int<8>{}, std::false_type{});
-        else launch(vv, nnf_int<4>{}, std::false_type{});
+        if constexpr (OP <= NNF_COST_GEN) {   // the weighted cost: the same two widths of the V image
+            if (q.Wg != nullptr) {
+                if (pl.NN != 4) launch(vv, nnf_int<8>{}, std::false_type{}, std::true_type{});
+                else launch(vv, nnf_int<4>{}, std::false_type{}, std::true_type{});
+                return;
+            }
+        }
+        if (q.Pin != nullptr) launch(vv, nnf_int<8>{}, std::true_type{}, std::false_type{});
+        else if (OP == NNF_PROD || pl.NN != 4) launch(vv, nnf_int<8>{}, std::false_type{}, std::false_type{});
+        else launch(vv, nnf_int<4>{}, std::false_type{}, std::false_type{});
     };
     nnf_probe(ctx, NNF_PROBE_COST, 0, st);
     if (vec) pick(std::true_type{});
@@ -509,5 +548,20 @@ extern "C" int nnf_cp3_betadiv_f32(nnf_ctx* ctx, const float* T, int64_t I, int6
     if (!nnf_cost_offsets_ok(K, K)) return NNF_ERR_UNSUPPORTED;
     const cost_request q = {.X = T, .m = I * J, .n = K, .ldx = K, .Ut = Ft0, .ldu = ld0, .V = Ft2, .ldv = ld2, .r = R, .out = out_f64,
                             .Ub = Ft1, .ldub = ld1, .nbu = J};
+    return launch_betadiv(ctx, q, beta, (hipStream_t)stream);
+}
+
+// Weighted beta-divergence  sum_ij Wg[i][j] d_beta(X[i][j] | (U V)[i][j])  (not normalised, as nmf.py:455): the cost of weighted
+// NMF (nnf_mu_left_w_f32 / nnf_mu_right_w_f32).  An entry of weight zero adds exactly 0 whatever X holds there.  beta = 2 counts
+// 1/2 (x - p)^2 per entry like nnf_betadiv_f32.  Same launch plans as the unweighted pass; r <= NNF_MAX_RANK.
+extern "C" int nnf_betadiv_w_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg, int64_t ldw,
+                                 const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, double* out_f64,
+                                 void* stream) {
+    const cost_request q = {.X = X, .m = m, .n = n, .ldx = ldx, .Ut = Ut, .ldu = ldu, .V = V, .ldv = ldv, .r = r, .out = out_f64,
+                            .Wg = Wg, .ldw = ldw};
+    const int rc = cost_args_ok(ctx, q, out_f64 != nullptr);
+    if (rc != NNF_OK && rc != NNF_ERR_UNSUPPORTED) return rc;
+    if (!Wg || ldw < n || !(beta >= 0.0)) return NNF_ERR_ARG;
+    if (rc != NNF_OK || r > NNF_MAX_RANK || !nnf_cost_offsets_ok(ldw, n)) return NNF_ERR_UNSUPPORTED;
     return launch_betadiv(ctx, q, beta, (hipStream_t)stream);
 }

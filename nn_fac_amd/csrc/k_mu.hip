@@ -23,10 +23,11 @@
 // One source, seven translation units (Makefile: -DMU_PART=0..6) so that the ~90 instantiations of the two fused kernels
 // compile side by side: 0 = right update + the small helpers, 1 = left update (beta = 1 and general beta), 2 = the left
 // kernel's cost-carrying forms (KL cost, NTF cost + partial product); ranks 65 .. 128 (MT = 5 .. 8): 3 = right KL, 4 = right
-// general beta, 5 = left KL, 6 = left general beta.  The small kernels and launch templates above the entry points are
-// `static`: every unit sees them, only the units that use them emit them.
+// general beta, 5 = left KL, 6 = left general beta.  The weighted forms (BM_WGEN: per-entry weights next to X, any beta, raw
+// numerator and denominator out): 7 = right, 8 = left up to rank 64; 9 = right, 10 = left at ranks 65 .. 128.  The small kernels
+// and launch templates above the entry points are `static`: every unit sees them, only the units that use them emit them.
 #ifndef MU_PART
-#error "k_mu.hip is compiled per part: -DMU_PART=0..6"
+#error "k_mu.hip is compiled per part: -DMU_PART=0..10"
 #endif
 NNF_BUILD_FLAGS(NNF_CAT(k_mu, MU_PART), "MU_WG_PER_CU=" NNF_STR(MU_WG_PER_CU) " MU_STEP_FENCE()=" NNF_STR(MU_STEP_FENCE()))
 
@@ -156,11 +157,13 @@ template <int MT, int REM, int BM, bool VEC>
 static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx,
                            const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* V_out,
                            int64_t ldvo, hipStream_t st, float* num_out = nullptr, int64_t ldnum = 0,
-                           float* den_out = nullptr, int64_t ldden = 0, double* den_vec_out = nullptr) {
-    const mu_right_plan pl = mu_plan_right(cur, ctx->num_cus, m, n, ldx, ldu, r, MT, BM);
+                           float* den_out = nullptr, int64_t ldden = 0, double* den_vec_out = nullptr,
+                           const float* Wg = nullptr, int64_t ldw = 0) {
+    const mu_right_plan pl = BM == BM_WGEN ? mu_plan_right_w(cur, ctx->num_cus, m, n, ldx, ldw, ldu, r, MT)
+                                           : mu_plan_right(cur, ctx->num_cus, m, n, ldx, ldu, r, MT, BM);
     if (pl.split.status != NNF_OK) return pl.split.status;
     if (nnf_plan_debug()) mu_report_right(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, BM, pl);
-    const int ncb = pl.ncb, nsplit = (int)pl.split.nsplit, nacc = (BM == BM_GEN) ? 2 : 1;
+    const int ncb = pl.ncb, nsplit = (int)pl.split.nsplit, nacc = mu_two_acc(BM) ? 2 : 1;
     const int64_t ldp = nnf_rup(n, 4), slab_elems = (int64_t)r * ldp;
     double* dvec = (double*)cur.take((size_t)r * 8);
     double* part = pl.pieces > 1 ? (double*)cur.take((size_t)r * pl.pieces * 8) : nullptr;
@@ -168,7 +171,7 @@ static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int
     float* sden = nacc == 2 ? (float*)cur.take((size_t)nsplit * slab_elems * 4) : nullptr;
     if (!dvec || (pl.pieces > 1 && !part) || !snum || (nacc == 2 && !sden)) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan took the same)
     const int a_vec_ok = x_vec_ok(Ut, ldu) ? 1 : 0;
-    const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, BM == BM_GEN));
+    const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, mu_two_acc(BM)));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_mu_right_kernel<MT, REM, BM, VEC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     if (BM == BM_KL) {  // den[k] = colsum(U)[k] = rowsum(Ut)[k]   (mu.py:86-87 on the transposed problem)
@@ -177,7 +180,7 @@ static int launch_mu_right(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int
     }
     nnf_probe(ctx, NNF_PROBE_MU_RIGHT, 0, st);
     hipLaunchKernelGGL((nnf_mu_right_kernel<MT, REM, BM, VEC>), dim3(nnf_split_grid(nsplit, ncb)), dim3(256), shm, st, X, m, n, ldx,
-                       Ut, ldu, V, ldv, r, (float)beta, snum, sden, ldp, ncb, nsplit, pl.split.rows_per_split, a_vec_ok);
+                       Ut, ldu, V, ldv, r, (float)beta, snum, sden, ldp, ncb, nsplit, pl.split.rows_per_split, a_vec_ok, Wg, ldw);
     NNF_CHECK_LAUNCH();
     nnf_probe(ctx, NNF_PROBE_MU_RIGHT, 1, st);
     if (num_out) {   // accumulate only (row-sharded runs): this block's numerator / denominator, slab-reduced in fixed order
@@ -200,7 +203,8 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
                           int64_t lduo, hipStream_t st, int raw_num = 0, mu_left_extra ex = mu_left_extra{nullptr, 0, 1, nullptr},
                           double* cost_out = nullptr) {
     constexpr bool with_cost = BM == BM_FROB || BM == BM_KLC;
-    const mu_left_plan pl = mu_plan_left(cur, ctx->num_cus, m, n, ldx, ldv, r, nnf_rank_tiles{MT, REM}, BM);
+    const mu_left_plan pl = BM == BM_WGEN ? mu_plan_left_w(cur, ctx->num_cus, m, n, ldx, ex.ldw, ldv, r, MT)
+                                          : mu_plan_left(cur, ctx->num_cus, m, n, ldx, ldv, r, nnf_rank_tiles{MT, REM}, BM);
     if (pl.status != NNF_OK) return pl.status;
     if (nnf_plan_debug()) mu_report_left(stderr, m, n, r, nnf_rank_tiles{MT, REM}, VEC, BM, pl);
     double* dvec = (double*)cur.take((size_t)r * 8);
@@ -208,7 +212,7 @@ static int launch_mu_left(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int6
     if (with_cost) ex.partial = (double*)cur.take((size_t)pl.grid * 8);
     if (!dvec || (pl.pieces > 1 && !part) || (with_cost && (!ex.partial || !cost_out))) return NNF_ERR_WORKSPACE;   // (cannot happen: the plan took the same)
     const int a_vec_ok = x_vec_ok(V, ldv) ? 1 : 0;
-    const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, BM == BM_GEN));
+    const size_t shm = mu_shm(MT, REM, r, mu_frags_in_regs(MT, mu_two_acc(BM)));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nnf_mu_left_kernel<MT, REM, BM, VEC>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     if (BM == BM_KL || BM == BM_KLC) {  // den[k] = rowsum(V)[k]   (mu.py:86-87)
@@ -612,3 +616,81 @@ extern "C" int nnf_mu_left_kl_cost_f32(nnf_ctx* ctx, const float* X, int64_t m, 
     MU_CALL(launch_mu_left, BM_KLC, true, r, vec, ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, 1.0, Ut_out, lduo, st, 0, ex, cost_f64);
 }
 #endif   // MU_PART == 2
+
+// =========================================================================================================
+// Weighted forms (BM_WGEN): with a weight Wg[i][j] >= 0 per entry and P = U V,
+//   left :  num[k,i] = sum_j Wg X P^(beta-2) V[k,j],   den[k,i] = sum_j Wg P^(beta-1) V[k,j]
+//   right:  num[k,j] = sum_i Wg X P^(beta-2) U[i,k],   den[k,j] = sum_i Wg P^(beta-1) U[i,k]
+// for any beta >= 0 -- beta = 1 and beta = 2 have no shortcut under weights (rowsum(V) and the Gram form both assume that every
+// entry counts alike), so every beta carries both accumulators and takes the BM_GEN launch plans.  An entry of weight zero is
+// out of both sums whatever X holds there (NaN, Inf); both updates hand out the raw sums and nnf_mu_apply_f32 finishes.
+// One instantiation per (rank tiles, load width) serves every beta; 16-byte loads need X AND Wg aligned.
+// =========================================================================================================
+#define MU_CALL_W(FN, R, VECF, MT0, ...)                                                                             \
+    do {                                                                                                             \
+        switch (((R) + 15) / 16 - (MT0)) {                                                                           \
+            case 0: return (VECF) ? FN<(MT0) + 0, 0, BM_WGEN, true>(__VA_ARGS__) : FN<(MT0) + 0, 0, BM_WGEN, false>(__VA_ARGS__); \
+            case 1: return (VECF) ? FN<(MT0) + 1, 0, BM_WGEN, true>(__VA_ARGS__) : FN<(MT0) + 1, 0, BM_WGEN, false>(__VA_ARGS__); \
+            case 2: return (VECF) ? FN<(MT0) + 2, 0, BM_WGEN, true>(__VA_ARGS__) : FN<(MT0) + 2, 0, BM_WGEN, false>(__VA_ARGS__); \
+            case 3: return (VECF) ? FN<(MT0) + 3, 0, BM_WGEN, true>(__VA_ARGS__) : FN<(MT0) + 3, 0, BM_WGEN, false>(__VA_ARGS__); \
+            default: return NNF_ERR_UNSUPPORTED;                                                                     \
+        }                                                                                                            \
+    } while (0)
+int nnf_mu_right_w_big(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg,
+                       int64_t ldw, const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* num,
+                       int64_t ldnum, float* den, int64_t ldden, hipStream_t st);
+int nnf_mu_left_w_big(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg,
+                      int64_t ldw, const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* num,
+                      int64_t ldnum, float* den, int64_t ldden, hipStream_t st);
+static inline bool mu_w_vec_ok(const float* X, int64_t ldx, const float* Wg, int64_t ldw) { return x_vec_ok(X, ldx) && x_vec_ok(Wg, ldw); }
+// what the weighted entries check before anything is launched (cols: the long side of the outputs)
+static int mu_w_args_ok(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg, int64_t ldw,
+                        const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, const float* num,
+                        int64_t ldnum, const float* den, int64_t ldden, int64_t cols) {
+    const int rc = mu_args_ok(ctx, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, num);
+    if (rc != NNF_OK) return rc;
+    if (!Wg || !den || ldw < n || ldnum < cols || ldden < cols) return NNF_ERR_ARG;
+    return NNF_OK;
+}
+#if MU_PART == 9
+int nnf_mu_right_w_big(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg,
+                       int64_t ldw, const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* num,
+                       int64_t ldnum, float* den, int64_t ldden, hipStream_t st) {
+    MU_CALL_W(launch_mu_right, r, mu_w_vec_ok(X, ldx, Wg, ldw), 5, ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, nullptr, 0, st, num,
+              ldnum, den, ldden, nullptr, Wg, ldw);
+}
+#endif
+#if MU_PART == 10
+int nnf_mu_left_w_big(nnf_ctx* ctx, nnf_ws_cursor& cur, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg,
+                      int64_t ldw, const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* num,
+                      int64_t ldnum, float* den, int64_t ldden, hipStream_t st) {
+    const mu_left_extra ex{nullptr, 0, 1, nullptr, Wg, ldw, den, ldden};
+    MU_CALL_W(launch_mu_left, r, mu_w_vec_ok(X, ldx, Wg, ldw), 5, ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, num, ldnum, st, 1, ex);
+}
+#endif
+#if MU_PART == 7
+extern "C" int nnf_mu_right_w_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg, int64_t ldw,
+                                  const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* num,
+                                  int64_t ldnum, float* den, int64_t ldden, void* stream) {
+    const int rc = mu_w_args_ok(ctx, X, m, n, ldx, Wg, ldw, Ut, ldu, V, ldv, r, beta, num, ldnum, den, ldden, n);
+    if (rc != NNF_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    nnf_ws_cursor cur(ctx);
+    if (r > 64) return nnf_mu_right_w_big(ctx, cur, X, m, n, ldx, Wg, ldw, Ut, ldu, V, ldv, r, beta, num, ldnum, den, ldden, st);
+    MU_CALL_W(launch_mu_right, r, mu_w_vec_ok(X, ldx, Wg, ldw), 1, ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, nullptr, 0, st, num,
+              ldnum, den, ldden, nullptr, Wg, ldw);
+}
+#endif
+#if MU_PART == 8
+extern "C" int nnf_mu_left_w_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t ldx, const float* Wg, int64_t ldw,
+                                 const float* Ut, int64_t ldu, const float* V, int64_t ldv, int r, double beta, float* num,
+                                 int64_t ldnum, float* den, int64_t ldden, void* stream) {
+    const int rc = mu_w_args_ok(ctx, X, m, n, ldx, Wg, ldw, Ut, ldu, V, ldv, r, beta, num, ldnum, den, ldden, m);
+    if (rc != NNF_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    nnf_ws_cursor cur(ctx);
+    if (r > 64) return nnf_mu_left_w_big(ctx, cur, X, m, n, ldx, Wg, ldw, Ut, ldu, V, ldv, r, beta, num, ldnum, den, ldden, st);
+    const mu_left_extra ex{nullptr, 0, 1, nullptr, Wg, ldw, den, ldden};
+    MU_CALL_W(launch_mu_left, r, mu_w_vec_ok(X, ldx, Wg, ldw), 1, ctx, cur, X, m, n, ldx, Ut, ldu, V, ldv, r, beta, num, ldnum, st, 1, ex);
+}
+#endif

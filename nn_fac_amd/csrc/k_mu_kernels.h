@@ -10,6 +10,10 @@ struct mu_left_extra {
     const float* Fb;      // != nullptr: U[k][i] = Ut[k][i / nb] * Fb[k][i % nb]  (row (a, b) of a 3-way tensor seen as (A*B) x K)
     int64_t ldb, nb;
     double* partial;      // BM_FROB: one fp64 partial of sum (X - UV)^2 per workgroup
+    const float* Wg = nullptr;   // BM_WGEN: the m x n weights, streamed next to X with their own pitch
+    int64_t ldw = 0;
+    float* den_out = nullptr;    // BM_WGEN: the raw denominator (r x m, pitch lddo) next to the raw numerator in Ut_out
+    int64_t lddo = 0;
 };
 
 // F_K image of a 64-wide chunk of a row-major r x K matrix A (the rank index is the MFMA k index):
@@ -74,6 +78,25 @@ __device__ __forceinline__ void mu_elem(float x, float p, float beta, float& r1,
     }
 }
 
+// Weighted forms (BM_WGEN): num += w x p^(beta-2) f, den += w p^(beta-1) f with w the entry's weight.  BSEL says which of the
+// three element-wise bodies runs (1: beta = 1, 2: beta = 2, 0: the log2 / exp2 pair); the kernels pick it with one wave-uniform
+// switch per block, so that one instantiation serves every beta.  The caller puts the result behind the zero-weight select.
+template <int BSEL>
+__device__ __forceinline__ void mu_elem_w(float x, float p, float w, float beta, float& r1, float& r2) {
+    if constexpr (BSEL == 1) {
+        r1 = w * x * __builtin_amdgcn_rcpf(p);
+        r2 = w;
+    } else if constexpr (BSEL == 2) {
+        r1 = w * x;
+        r2 = w * p;
+    } else {
+        mu_elem<BM_GEN>(x, p, beta, r1, r2);
+        r1 *= w;
+        r2 *= w;
+    }
+}
+__device__ __forceinline__ int mu_bsel(float beta) { return beta == 1.f ? 1 : (beta == 2.f ? 2 : 0); }
+
 // =========================================================================================================
 // right update: slabs of num (and den) [ks][r][ldp], split over the rows of X like xty.
 // =========================================================================================================
@@ -95,15 +118,16 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
                                                               const float* __restrict__ V, int64_t ldv, int r, float beta,
                                                               float* __restrict__ snum, float* __restrict__ sden,
                                                               int64_t ldp, int ncb, int nsplit, int64_t rows_per_split,
-                                                              int a_vec_ok) {
+                                                              int a_vec_ok, const float* __restrict__ Wg, int64_t ldw) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr bool TWO = mu_two_acc(BM), WT = BM == BM_WGEN;         // denominator accumulators; weights streamed next to X
     static_assert(REM == 0 || BM == BM_KL, "leftover ranks on the VALU pipe: KL form only");
     static_assert(REM == 0 || MT <= 4, "leftover ranks on the VALU pipe: up to three full tiles");
     constexpr int NC = mu_right_nc(MT);                              // 16-column tiles per wave: columns jl + cc, cc < NC
     constexpr int MTA = MT + (REM > 0 ? 1 : 0);                      // tiles of the F_A image
     constexpr int NR = REM > 0 ? REM : 1;
     const int KS = REM > 0 ? 4 * MT : ((r + 3) >> 2);
-    constexpr bool REGF = mu_frags_in_regs(MT, BM == BM_GEN);                           // resident fragments in registers / in LDS
+    constexpr bool REGF = mu_frags_in_regs(MT, TWO);                                    // resident fragments in registers / in LDS
     const bool tail4 = REM > 0 || KS > 4 * (MT - 1) + 2;
     f32x4* ldsVf = reinterpret_cast<f32x4*>(smem);                 // !REGF: [4][KS][64]: V[4s+g][jw+4jj..+3]
     f32x4* ldsA = ldsVf + (REGF ? 0 : (size_t)4 * KS * 64);          // [2][MTA*256]  F_A image of the Ut chunk
@@ -120,6 +144,11 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
     const rsrc_t rs = nnf_make_rsrc(X + i_begin * ldx, (uint32_t)(((i_end - i_begin - 1) * ldx + n) * 4));
     const int voff = (jl < n) ? (int)(((int64_t)4 * g * ldx + jl) * 4) : (int)0x7ffffff0;
     const int ldx4 = (int)(ldx * 4);
+    // the weights: a resource, lane offset and pitch of their own (same rows and columns as X)
+    const rsrc_t rsw = WT ? nnf_make_rsrc(Wg + i_begin * ldw, (uint32_t)(((i_end - i_begin - 1) * ldw + n) * 4)) : rs;
+    const int voffw = (WT && jl < n) ? (int)(((int64_t)4 * g * ldw + jl) * 4) : (int)0x7ffffff0;
+    const int ldw4 = (int)(ldw * 4);
+    const int bsel = mu_bsel(beta);
 
     auto v_row4 = [&](int k) {   // V[k][jl .. jl+NC-1], zero beyond r x n
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -157,13 +186,13 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
             ldsVf[e] = v;
         }
     }
-    f32x4 num[MT][4], den[BM == BM_GEN ? MT : 1][4];
+    f32x4 num[MT][4], den[TWO ? MT : 1][4];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int cc = 0; cc < NC; ++cc) {
             num[mt][cc] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (BM == BM_GEN) den[mt][cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (TWO) den[mt][cc] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     f32x4 ev[NR];     // REM: numerator rows 16MT+rr, columns jl..jl+3, partial over this lane's rows
 #pragma unroll
@@ -173,6 +202,13 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int c = 0; c < 4; ++c) xb[t][c] = nnf_bloadn<VEC, NC>(rs, voff, (16 * t + c) * ldx4);
+    f32x4 wb[WT ? 2 : 1][WT ? 4 : 1];   // BM_WGEN: the same ring of the weights
+    if constexpr (WT) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) wb[t][c] = nnf_bloadn<VEC, NC>(rsw, voffw, (16 * t + c) * ldw4);
+    }
     const mu_stage stg = mu_stage_make(Ut, ldu, r, i_end);
     {
         f32x4 sa[MTA], sk[MT];
@@ -185,7 +221,26 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
 
     // element-wise phase of one 16-row group: R = op(X, P), masked past the split's last row (0/0 otherwise)
     auto elementwise = [&](const f32x4 (&x)[4], const f32x4 (&accP)[4], int rowrem, f32x4 (&R1)[4],
-                           f32x4 (&R2)[BM == BM_GEN ? 4 : 1]) {
+                           f32x4 (&R2)[TWO ? 4 : 1], int tw) {
+        if constexpr (WT) {
+            // a zero weight takes the entry out of both sums whatever X holds there (a select: 0 * NaN would be NaN)
+            auto body = [&](auto bs) {
+#pragma unroll
+                for (int cc = 0; cc < NC; ++cc)
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) {
+                        float r1, r2;
+                        const float wv = wb[tw][reg][cc];
+                        mu_elem_w<decltype(bs)::value>(x[reg][cc], accP[cc][reg], wv, beta, r1, r2);
+                        const bool ok = reg < rowrem && wv != 0.f;
+                        R1[cc][reg] = ok ? r1 : 0.f;
+                        R2[cc][reg] = ok ? r2 : 0.f;
+                    }
+            };
+            if (bsel == 1) body(nnf_int<1>{});
+            else if (bsel == 2) body(nnf_int<2>{});
+            else body(nnf_int<0>{});
+        } else {
 #pragma unroll
         for (int cc = 0; cc < NC; ++cc)
 #pragma unroll
@@ -194,8 +249,9 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
                 mu_elem<BM>(x[reg][cc], accP[cc][reg], beta, r1, r2);
                 const bool ok = reg < rowrem;
                 R1[cc][reg] = ok ? r1 : 0.f;
-                if constexpr (BM == BM_GEN) R2[cc][reg] = ok ? r2 : 0.f;
+                if constexpr (TWO) R2[cc][reg] = ok ? r2 : 0.f;
             }
+        }
     };
 
     if constexpr (REGF) {
@@ -249,8 +305,8 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
                 });
                 nnf_static_for<0, MT>([&](auto mt) { nnf_lds_read4<(mt * 4 + t) * 1024>(af[mt], ab); });
                 const int rowrem = rows_left - 16 * t - 4 * g;
-                f32x4 R1[4], R2[BM == BM_GEN ? 4 : 1];
-                elementwise(xb[t & 1], accP, rowrem, R1, R2);
+                f32x4 R1[4], R2[TWO ? 4 : 1];
+                elementwise(xb[t & 1], accP, rowrem, R1, R2, WT ? (t & 1) : 0);
                 if constexpr (REM > 0) {
 #pragma unroll
                     for (int rr = 0; rr < REM; ++rr)
@@ -274,16 +330,21 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
 #pragma unroll
                         for (int cc = 0; cc < NC; ++cc) {
                             num[mt][cc] = MFMA16(af[mt][reg], R1[cc][reg], num[mt][cc]);
-                            if constexpr (BM == BM_GEN) den[mt][cc] = MFMA16(af[mt][reg], R2[cc][reg], den[mt][cc]);
+                            if constexpr (TWO) den[mt][cc] = MFMA16(af[mt][reg], R2[cc][reg], den[mt][cc]);
                         }
                     if constexpr (t < 3) {
-                        nnf_lds_read4_after<((t + 1) * MT + mt) * 1024>(ak[mt], kb, (BM == BM_GEN ? den : num)[mt][NC - 1]);
+                        nnf_lds_read4_after<((t + 1) * MT + mt) * 1024>(ak[mt], kb, (TWO ? den : num)[mt][NC - 1]);
                         if constexpr (mt == UVT)
                             nnf_static_for<0, REM>([&](auto rr) { nnf_lds_read4<(MT * 4 + t + 1) * 1024 + rr * 16>(uv[rr], ub); });
                     }
                 });
 #pragma unroll
                 for (int c = 0; c < 4; ++c) xb[t & 1][c] = nnf_bloadn<VEC, NC>(rs, voff, soff_q + (16 * (t + 2) + c) * ldx4);
+                if constexpr (WT) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        wb[t & 1][c] = nnf_bloadn<VEC, NC>(rsw, voffw, q * 64 * ldw4 + (16 * (t + 2) + c) * ldw4);
+                }
                 // next chunk's images: A loaded at the top of the chunk and written here in group 1, K loaded in group 2 and
                 // written after group 3 -- the fences between the groups keep the two staging sets from being live together
                 if constexpr (t == 1) stageA_store<MTA>(ldsA + (size_t)((q + 1) & 1) * MTA * 256, sa);
@@ -323,8 +384,8 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
             }
             const int64_t left64 = (i_end - i_begin) - 64 * (int64_t)q;
             const int rowrem = (left64 > 64 ? 64 : (int)left64) - 16 * t - 4 * g;
-            f32x4 R1[4], R2[BM == BM_GEN ? 4 : 1];
-            elementwise(xb[t & 1], accP, rowrem, R1, R2);
+            f32x4 R1[4], R2[TWO ? 4 : 1];
+            elementwise(xb[t & 1], accP, rowrem, R1, R2, WT ? (t & 1) : 0);
             // MFMA #2: num[rk][j] += Ut[rk][i] * R[i][j], k = the block's 16 rows
             f32x4 af[MT];
 #pragma unroll
@@ -336,10 +397,15 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
 #pragma unroll
                     for (int cc = 0; cc < 4; ++cc) {
                         num[mt][cc] = MFMA16(af[mt][reg], R1[cc][reg], num[mt][cc]);
-                        if constexpr (BM == BM_GEN) den[mt][cc] = MFMA16(af[mt][reg], R2[cc][reg], den[mt][cc]);
+                        if constexpr (TWO) den[mt][cc] = MFMA16(af[mt][reg], R2[cc][reg], den[mt][cc]);
                     }
 #pragma unroll
             for (int c = 0; c < 4; ++c) xb[t & 1][c] = nnf_bloadn<VEC, NC>(rs, voff, soff_q + (16 * (t + 2) + c) * ldx4);
+            if constexpr (WT) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    wb[t & 1][c] = nnf_bloadn<VEC, NC>(rsw, voffw, q * 64 * ldw4 + (16 * (t + 2) + c) * ldw4);
+            }
             if (t == 1) stageA_store<MTA>(ldsA + (size_t)((q + 1) & 1) * MTA * 256, sa);
             if (t == 2) stageK_bload<MT>(stg, i_end, i_begin + 64 * (int64_t)(q + 1), sk);
             MU_STEP_FENCE();
@@ -350,7 +416,7 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
     }
     if (jl < ldp) {
         float* sn = snum + (int64_t)ks * r * ldp;
-        float* sd = (BM == BM_GEN) ? sden + (int64_t)ks * r * ldp : nullptr;
+        float* sd = TWO ? sden + (int64_t)ks * r * ldp : nullptr;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -360,12 +426,12 @@ __global__ __launch_bounds__(256, (BM == BM_KL && MT <= 4 ? MU_WG_PER_CU : 1)) v
                     if constexpr (NC == 4) {
                         *reinterpret_cast<f32x4*>(sn + (int64_t)rk * ldp + jl) =
                             f32x4{num[mt][0][reg], num[mt][1][reg], num[mt][2][reg], num[mt][3][reg]};
-                        if constexpr (BM == BM_GEN)
+                        if constexpr (TWO)
                             *reinterpret_cast<f32x4*>(sd + (int64_t)rk * ldp + jl) =
                                 f32x4{den[mt][0][reg], den[mt][1][reg], den[mt][2][reg], den[mt][3][reg]};
                     } else {   // (jl is even and ldp a multiple of 4: the pair is 8-byte aligned and inside the slab row)
                         *reinterpret_cast<f32x2*>(sn + (int64_t)rk * ldp + jl) = f32x2{num[mt][0][reg], num[mt][1][reg]};
-                        if constexpr (BM == BM_GEN)
+                        if constexpr (TWO)
                             *reinterpret_cast<f32x2*>(sd + (int64_t)rk * ldp + jl) = f32x2{den[mt][0][reg], den[mt][1][reg]};
                     }
                 }
@@ -402,11 +468,12 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
                                                  const double* __restrict__ den_vec, float gamma,
                                                  float* __restrict__ Ut_out, int64_t lduo, int a_vec_ok, int64_t row0,
                                                  char* smem, const mu_left_extra& ex) {
-    static_assert(REM == 0 || BM != BM_GEN, "leftover ranks on the VALU pipe: not for the general-beta form");
+    constexpr bool TWO = mu_two_acc(BM), WT = BM == BM_WGEN;         // denominator accumulators; weights streamed next to X
+    static_assert(REM == 0 || !TWO, "leftover ranks on the VALU pipe: not for the general-beta forms");
     constexpr int MTA = MT + (REM > 0 ? 1 : 0);                      // tiles of the F_A image
     constexpr int NR = REM > 0 ? REM : 1;
     const int KS = REM > 0 ? 4 * MT : ((r + 3) >> 2);
-    constexpr bool REGF = mu_frags_in_regs(MT, BM == BM_GEN);                          // resident fragments in registers / in LDS
+    constexpr bool REGF = mu_frags_in_regs(MT, TWO);                                   // resident fragments in registers / in LDS
     const bool tail4 = REM > 0 || KS > 4 * (MT - 1) + 2;
     float csum = 0.f;                                                // BM_FROB: this lane's share of sum (X - UV)^2
     f32x4* ldsUf = reinterpret_cast<f32x4*>(smem);                 // !REGF: [4][KS][64]: comps nt: Ut[4s+g][i0w+16nt+ii]
@@ -422,6 +489,11 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
     const int voff = (int)(((int64_t)ii * ldx + 4 * g) * 4);
     const int ldx4 = (int)(ldx * 4);
     const int nchunk = (int)((n + 63) >> 6);
+    // the weights: a resource, lane offset and pitch of their own (same rows and columns as X)
+    const rsrc_t rsw = WT ? nnf_make_rsrc(ex.Wg + (rows > 0 ? i0w : 0) * ex.ldw, rows > 0 ? (uint32_t)(((rows - 1) * ex.ldw + n) * 4) : 0u) : rs;
+    const int voffw = (int)(((int64_t)ii * ex.ldw + 4 * g) * 4);
+    const int ldw4 = (int)(ex.ldw * 4);
+    const int bsel = mu_bsel(beta);
 
     // resident U fragments of this wave's 64 rows, in registers (like the V fragments of the right kernel):
     // ufr[s][nt] = Ut[4s+g][i0w + 16nt + ii], s < KS (zero beyond r x m);  REM: urem[rr][nt] = Ut[16MT+rr][i0w + 16nt + ii]
@@ -494,13 +566,13 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
             ldsUf[e] = v;
         }
     }
-    f32x4 num[MT][4], den[BM == BM_GEN ? MT : 1][4];
+    f32x4 num[MT][4], den[TWO ? MT : 1][4];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             num[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (BM == BM_GEN) den[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (TWO) den[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     f32x4 ev[NR];    // REM: numerator rows 16MT+rr of this lane's NT rows of U, partial over this lane's columns
 #pragma unroll
@@ -510,6 +582,13 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) xb[t][nt] = nnf_bload4<VEC>(rs, voff, nt * 16 * ldx4 + 64 * t);
+    f32x4 wb[WT ? 2 : 1][WT ? 4 : 1];   // BM_WGEN: the same ring of the weights
+    if constexpr (WT) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) wb[t][nt] = nnf_bload4<VEC>(rsw, voffw, nt * 16 * ldw4 + 64 * t);
+    }
     const mu_stage stg = mu_stage_make(V, ldv, r, n);
     {
         f32x4 sa[MTA], sk[MT];
@@ -522,7 +601,29 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
 
     // element-wise phase of one 16-column group: R = op(X, P) (+ this group's share of the cost), masked outside the matrix
     auto elementwise = [&](const f32x4 (&x)[4], const f32x4 (&accP)[4], int colrem, f32x4 (&R1)[4],
-                           f32x4 (&R2)[BM == BM_GEN ? 4 : 1]) {
+                           f32x4 (&R2)[TWO ? 4 : 1], int tw) {
+        if constexpr (WT) {
+            // a zero weight takes the entry out of both sums whatever X holds there (a select: 0 * NaN would be NaN)
+            auto body = [&](auto bs) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const bool rowok = (16 * nt + ii) < rows;
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) {
+                        float r1, r2;
+                        const float wv = wb[tw][nt][reg];
+                        mu_elem_w<decltype(bs)::value>(x[nt][reg], accP[nt][reg], wv, beta, r1, r2);
+                        const bool ok = rowok && (reg < colrem) && wv != 0.f;
+                        R1[nt][reg] = ok ? r1 : 0.f;
+                        R2[nt][reg] = ok ? r2 : 0.f;
+                    }
+                }
+            };
+            if (bsel == 1) body(nnf_int<1>{});
+            else if (bsel == 2) body(nnf_int<2>{});
+            else body(nnf_int<0>{});
+            return;
+        }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const bool rowok = (16 * nt + ii) < rows;
@@ -599,8 +700,8 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
                 });
                 nnf_static_for<0, MT>([&](auto mt) { nnf_lds_read4<(mt * 4 + t) * 1024>(af[mt], ab); });
                 const int colrem = cols_left - 16 * t - 4 * g;
-                f32x4 R1[4], R2[BM == BM_GEN ? 4 : 1];
-                elementwise(xb[t & 1], accP, colrem, R1, R2);
+                f32x4 R1[4], R2[TWO ? 4 : 1];
+                elementwise(xb[t & 1], accP, colrem, R1, R2, WT ? (t & 1) : 0);
                 if constexpr (REM > 0) {
 #pragma unroll
                     for (int rr = 0; rr < REM; ++rr)
@@ -620,10 +721,10 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
 #pragma unroll
                         for (int nt = 0; nt < NT; ++nt) {
                             num[mt][nt] = MFMA16(af[mt][reg], R1[nt][reg], num[mt][nt]);
-                            if constexpr (BM == BM_GEN) den[mt][nt] = MFMA16(af[mt][reg], R2[nt][reg], den[mt][nt]);
+                            if constexpr (TWO) den[mt][nt] = MFMA16(af[mt][reg], R2[nt][reg], den[mt][nt]);
                         }
                     if constexpr (t < 3) {
-                        nnf_lds_read4_after<((t + 1) * MT + mt) * 1024>(ak[mt], kb, (BM == BM_GEN ? den : num)[mt][NT - 1]);
+                        nnf_lds_read4_after<((t + 1) * MT + mt) * 1024>(ak[mt], kb, (TWO ? den : num)[mt][NT - 1]);
                         if constexpr (mt == UVT)
                             nnf_static_for<0, REM>([&](auto rr) { nnf_lds_read4<(MT * 4 + t + 1) * 1024 + rr * 16>(vv[rr], ub); });
                     }
@@ -631,6 +732,11 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
                     xb[t & 1][nt] = nnf_bload4<VEC>(rs, voff, nt * 16 * ldx4 + 256 * q + 64 * (t + 2));
+                if constexpr (WT) {
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        wb[t & 1][nt] = nnf_bload4<VEC>(rsw, voffw, nt * 16 * ldw4 + 256 * q + 64 * (t + 2));
+                }
                 if constexpr (t == 1) stageA_store<MTA>(ldsA + (size_t)((q + 1) & 1) * MTA * 256, sa);
                 if constexpr (t == 2) stageK_bload<MT>(stg, n, 64 * (int64_t)(q + 1), sk);
                 MU_STEP_FENCE();
@@ -664,8 +770,8 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
             }
             const int64_t left64 = n - 64 * (int64_t)q;
             const int colrem = (left64 > 64 ? 64 : (int)left64) - 16 * t - 4 * g;
-            f32x4 R1[4], R2[BM == BM_GEN ? 4 : 1];
-            elementwise(xb[t & 1], accP, colrem, R1, R2);
+            f32x4 R1[4], R2[TWO ? 4 : 1];
+            elementwise(xb[t & 1], accP, colrem, R1, R2, WT ? (t & 1) : 0);
             // MFMA #2: num[rk][i] += V[rk][j] * R[j][i], k = the block's 16 columns
             f32x4 af[MT];
 #pragma unroll
@@ -677,11 +783,16 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
                         num[mt][nt] = MFMA16(af[mt][reg], R1[nt][reg], num[mt][nt]);
-                        if constexpr (BM == BM_GEN) den[mt][nt] = MFMA16(af[mt][reg], R2[nt][reg], den[mt][nt]);
+                        if constexpr (TWO) den[mt][nt] = MFMA16(af[mt][reg], R2[nt][reg], den[mt][nt]);
                     }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
                 xb[t & 1][nt] = nnf_bload4<VEC>(rs, voff, nt * 16 * ldx4 + 256 * q + 64 * (t + 2));
+            if constexpr (WT) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    wb[t & 1][nt] = nnf_bload4<VEC>(rsw, voffw, nt * 16 * ldw4 + 256 * q + 64 * (t + 2));
+            }
             if (t == 1) stageA_store<MTA>(ldsA + (size_t)((q + 1) & 1) * MTA * 256, sa);
             if (t == 2) stageK_bload<MT>(stg, n, 64 * (int64_t)(q + 1), sk);
             MU_STEP_FENCE();
@@ -695,7 +806,7 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
     // from addresses clamped into the factor (no branch around a load), and pinned: with a load inside the `i < m` /
     // `rk < r` branches hipcc waited for each one alone (s_waitcnt vmcnt(0) twice per element: ~100 dependent round trips at
     // the end of a kernel whose workgroups all finish together -- nothing left to hide them behind).
-    const bool raw = (BM == BM_FROB) || gamma < 0.f;   // raw numerator (nnf_mu_left_num_f32; wave-uniform flag)
+    const bool raw = (BM == BM_FROB) || WT || gamma < 0.f;   // raw numerator (nnf_mu_left_num_f32; wave-uniform flag); weighted: + raw denominator
     float uo[MT][NT][4], dn[MT][4], uor[NR][NT], dnr[NR];
     if (!raw) {
 #pragma unroll
@@ -703,7 +814,7 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 const int rk = 16 * mt + 4 * g + reg, rkc = rk < r ? rk : r - 1;
-                if constexpr (BM != BM_GEN) dn[mt][reg] = (float)den_vec[rkc];
+                if constexpr (!TWO) dn[mt][reg] = (float)den_vec[rkc];
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     const int64_t i = i0w + 16 * nt + ii, ic = i < m ? i : m - 1;
@@ -726,7 +837,7 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
-                if constexpr (BM != BM_GEN) asm volatile("" : "+v"(dn[mt][reg]));
+                if constexpr (!TWO) asm volatile("" : "+v"(dn[mt][reg]));
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) asm volatile("" : "+v"(uo[mt][nt][reg]));
             }
@@ -742,6 +853,7 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
     auto finish = [&](int rk, int64_t i, float nu, float de, float old) {
         if (raw) {
             Ut_out[(int64_t)rk * lduo + i] = nu;
+            if constexpr (WT) ex.den_out[(int64_t)rk * ex.lddo + i] = de;
             return;
         }
         float ratio = nu / de;
@@ -760,7 +872,7 @@ __device__ __forceinline__ void nnf_mu_left_body(const float* __restrict__ X, in
                     const int rk = 16 * mt + 4 * g + reg;
                     if (rk < r) {
                         float d;
-                        if constexpr (BM == BM_GEN) d = den[mt][nt][reg]; else d = dn[mt][reg];
+                        if constexpr (TWO) d = den[mt][nt][reg]; else d = dn[mt][reg];
                         finish(rk, i, num[mt][nt][reg], d, uo[mt][nt][reg]);
                     }
                 }

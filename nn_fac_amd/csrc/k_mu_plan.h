@@ -3,8 +3,13 @@
 #pragma once
 #include "k_stream_plan.h"
 
-enum { BM_KL = 1, BM_FROB = 2, BM_KLC = 3, BM_GEN = 9 };   // BM_KLC: the KL update + the KL divergence of its INPUT factors   // BM_FROB: R = X (plain X V^T) + the squared residual, see nnf_cp3_partial_cost_f32
-constexpr const char* mu_bm_name(int BM) { return BM == BM_KL ? "KL" : BM == BM_KLC ? "KLC" : BM == BM_FROB ? "FROB" : "GEN"; }
+enum { BM_KL = 1, BM_FROB = 2, BM_KLC = 3, BM_GEN = 9, BM_WGEN = 10 };   // BM_KLC: the KL update + the KL divergence of its INPUT factors   // BM_FROB: R = X (plain X V^T) + the squared residual, see nnf_cp3_partial_cost_f32
+// BM_WGEN: per-entry weights next to X, any beta (k_mu.hip, "weighted forms"): numerator AND denominator accumulators like BM_GEN
+constexpr const char* mu_bm_name(int BM) {
+    return BM == BM_KL ? "KL" : BM == BM_KLC ? "KLC" : BM == BM_FROB ? "FROB" : BM == BM_WGEN ? "WGEN" : "GEN";
+}
+// the forms that carry a denominator accumulator next to the numerator's: they share every residency figure and launch plan
+constexpr bool mu_two_acc(int BM) { return BM == BM_GEN || BM == BM_WGEN; }
 
 // Where the loop-invariant ("resident") factor fragments of MFMA #1 live: in registers for the KL forms, and for every form
 // above rank 64 (MT > 4 rank tiles, where the chunk images alone take 16 KiB of LDS per tile); otherwise (general beta,
@@ -19,12 +24,12 @@ constexpr size_t mu_shm(int MT, int REM, int r, bool regf) {
 // resident workgroups per CU of the left kernel: three for the small Frobenius forms (<= 168 VGPRs), one for general beta
 // and for ranks above 80 (MT > 5: 16 KiB of chunk images per rank tile)
 constexpr int mu_left_wgpc(int MT, int REM, int BM) {
-    return BM == BM_GEN || MT > 5 ? 1 : ((MT + (REM > 0) <= 2 && REM <= 2 && BM == BM_FROB) ? 3 : 2);
+    return mu_two_acc(BM) || MT > 5 ? 1 : ((MT + (REM > 0) <= 2 && REM <= 2 && BM == BM_FROB) ? 3 : 2);
 }
 // above rank 64 the left kernel has its 128-row form only for general beta (numerator + denominator + fragments in registers)
 // and at MT = 5 (there that form stays within 256 registers and 80 KiB of LDS: two workgroups share a CU, which measured
 // faster than the better balanced mix of 192- and 128-row workgroups at one per CU: 719 against 792 us at 100000 x 2000, r = 65)
-constexpr bool mu_left_rows128(int MT, int BM) { return MT > 4 && (BM == BM_GEN || MT == 5); }
+constexpr bool mu_left_rows128(int MT, int BM) { return MT > 4 && (mu_two_acc(BM) || MT == 5); }
 // 16-column tiles per wave of the right kernel: 256 columns per workgroup, 128 at MT > 4 (k_mu_kernels.h)
 constexpr int mu_right_nc(int MT) { return MT > 4 ? 2 : 4; }
 // resident 4-wave workgroups per CU the right update's split count aims at
@@ -66,8 +71,13 @@ inline mu_right_plan mu_plan_right(nnf_ws_cursor cur, int cus, int64_t m, int64_
     p.split.status = NNF_ERR_WORKSPACE;
     if (!cur.reserve((size_t)r * 8) || (p.pieces > 1 && !cur.reserve((size_t)r * p.pieces * 8))) return p;
     p.split = nnf_plan_split(m, ldx, p.ncb, mu_right_wgpc(MT, BM) * (int64_t)cus, 0, (int64_t)r * nnf_rup(n, 4) * 4,
-                             BM == BM_GEN ? 2 : 1, cur.remaining());
+                             mu_two_acc(BM) ? 2 : 1, cur.remaining());
     return p;
+}
+// weighted form: a second stream with its own pitch runs next to X through the same 32-bit offsets -- the offset bound and the
+// row halving of the split hold for the larger of the two pitches
+inline mu_right_plan mu_plan_right_w(nnf_ws_cursor cur, int cus, int64_t m, int64_t n, int64_t ldx, int64_t ldw, int64_t ldu, int r, int MT) {
+    return mu_plan_right(cur, cus, m, n, ldx > ldw ? ldx : ldw, ldu, r, MT, BM_WGEN);
 }
 inline void mu_report_right(FILE* f, int64_t m, int64_t n, int r, nnf_rank_tiles t, bool vec, int BM, const mu_right_plan& p,
                             const char* more = "") {
@@ -119,6 +129,10 @@ inline mu_left_plan mu_plan_left(nnf_ws_cursor cur, int cus, int64_t m, int64_t 
                       ((BM != BM_FROB && BM != BM_KLC) || cur.reserve((size_t)p.grid * 8));
     p.status = fits ? NNF_OK : NNF_ERR_WORKSPACE;
     return p;
+}
+// weighted form: the offset bound holds for the larger of the two pitches (see mu_plan_right_w)
+inline mu_left_plan mu_plan_left_w(nnf_ws_cursor cur, int cus, int64_t m, int64_t n, int64_t ldx, int64_t ldw, int64_t ldv, int r, int MT) {
+    return mu_plan_left(cur, cus, m, n, ldx > ldw ? ldx : ldw, ldv, r, nnf_rank_tiles{MT, 0}, BM_WGEN);
 }
 inline void mu_report_left(FILE* f, int64_t m, int64_t n, int r, nnf_rank_tiles t, bool vec, int BM, const mu_left_plan& p,
                            const char* more = "") {

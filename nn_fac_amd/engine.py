@@ -541,7 +541,48 @@ class SparseTensorOps:
         return (N, D) if sums else None
 
 
-class Engine(CsrOps, SparseTensorOps):
+class WeightedOps:
+    """The weighted entries of the engine (Engine inherits them): the MU sums and the beta-divergence of dense data with a weight
+    per entry (nn_fac_amd/weighted_nmf.py).  Their operand refusals are tested in tests/test_gpu_weighted_kernels.py, one spoilt
+    operand at a time, as tests/test_gpu_engine_args.py does for the methods Engine defines itself."""
+
+    @staticmethod
+    def _xwuv(X, Wg, Ut, V, beta, what):
+        """X, Wg (m x n, pitches of their own), Ut (r x m), V (r x n), beta >= 0 -> (m, n, r, beta)."""
+        m, n, r = _xuv(X, Ut, V, what)
+        if _shaped(Wg, (m, n), what + " Wg").device != X.device:
+            raise EngineError(f"{what} Wg must be on {X.device}, got {Wg.device}")
+        if r > MAX_RANK:
+            raise EngineError(f"{what}: rank {r} is above the {MAX_RANK} the weighted kernels are built for")
+        return m, n, r, _obs_beta(beta, what)
+
+    def mu_left_w(self, X, Wg, Ut, V, beta, out_num=None, out_den=None):
+        """num[k, i] = sum_j Wg X P^(beta-2) V[k, j], den[k, i] = sum_j Wg P^(beta-1) V[k, j] with P = Ut^T V (both r x m; nnf_mu_left_w_f32).
+        An entry of weight 0 is out of both sums whatever X holds there.  Returns (num, den); mu_apply(Ut, num, den, None, beta) is
+        the update."""
+        m, n, r, beta = self._xwuv(X, Wg, Ut, V, beta, "mu_left_w")
+        N = _out(out_num, (r, m), Ut, "mu_left_w out_num")
+        D = _out(out_den, (r, m), Ut, "mu_left_w out_den")
+        self._call("nnf_mu_left_w_f32", _ptr(X), m, n, _ld(X), *_mat(Wg), *_mat(Ut), *_mat(V), r, beta, *_mat(N), *_mat(D))
+        return N, D
+
+    def mu_right_w(self, X, Wg, Ut, V, beta, out_num=None, out_den=None):
+        """num[k, j] = sum_i Wg X P^(beta-2) Ut[k, i], den[k, j] = sum_i Wg P^(beta-1) Ut[k, i] (both r x n; nnf_mu_right_w_f32)."""
+        m, n, r, beta = self._xwuv(X, Wg, Ut, V, beta, "mu_right_w")
+        N = _out(out_num, (r, n), V, "mu_right_w out_num")
+        D = _out(out_den, (r, n), V, "mu_right_w out_den")
+        self._call("nnf_mu_right_w_f32", _ptr(X), m, n, _ld(X), *_mat(Wg), *_mat(Ut), *_mat(V), r, beta, *_mat(N), *_mat(D))
+        return N, D
+
+    def betadiv_w(self, X, Wg, Ut, V, beta, out=None):
+        """sum_ij Wg[i, j] d_beta(X[i, j] | (Ut^T V)[i, j]) into a 1-element float64 device tensor (nnf_betadiv_w_f32)."""
+        m, n, r, beta = self._xwuv(X, Wg, Ut, V, beta, "betadiv_w")
+        o = _out64(out, 1, X.device, "betadiv_w out")
+        self._call("nnf_betadiv_w_f32", _ptr(X), m, n, _ld(X), *_mat(Wg), *_mat(Ut), *_mat(V), r, beta, _ptr(o))
+        return o
+
+
+class Engine(CsrOps, SparseTensorOps, WeightedOps):
     """One context (workspace + device properties) per device."""
 
     def __init__(self, device, workspace_bytes=0):

@@ -36,9 +36,11 @@ from ._outer_loop import _SolveTimedOut, _IdentityUnreliable, _IdentityNearStop,
 def nmf(data, rank, init="random", U_0=None, V_0=None, n_iter_max=100, tol=1e-8,
         update_rule="hals", beta=2,
         sparsity_coefficients=[None, None], fixed_modes=[], normalize=[False, False],
-        verbose=False, return_costs=False, deterministic=False, seed=0, unstored="zero"):
+        verbose=False, return_costs=False, deterministic=False, seed=0, unstored="zero", weights=None):
     """Nonnegative matrix factorisation  data ~= U V  (reference docstring: nmf.py:23-174).  ``unstored`` (extension, sparse data):
-    "zero" reads an unstored entry as a zero, "missing" as unknown -- the fit is over the stored entries only (sparse_nmf.py)."""
+    "zero" reads an unstored entry as a zero, "missing" as unknown -- the fit is over the stored entries only (sparse_nmf.py).
+    ``weights`` (extension, dense data, update_rule="mu"): an array of the data's shape, floats >= 0 or a boolean mask -- the fit
+    minimises sum w d_beta(x | (U V)); an entry of weight zero is missing, whatever the data holds there (weighted_nmf.py)."""
     if min(data.shape) < rank:
         min_data = min(data.shape)
         rank = min_data
@@ -47,6 +49,9 @@ def nmf(data, rank, init="random", U_0=None, V_0=None, n_iter_max=100, tol=1e-8,
     if deterministic:
         np.random.seed(seed)
 
+    if weights is not None:  # weighted_nmf.py: what that path refuses is said before the start values are drawn
+        from . import weighted_nmf
+        weighted_nmf.check_request(data, weights, rank, update_rule, beta, init=init)
     if is_sparse(data):      # sparse_nmf.py: what that path refuses is said before the start values are drawn
         from . import sparse_nmf
         sparse_nmf.check_request(rank, update_rule, beta, init=init, unstored=unstored)
@@ -63,20 +68,28 @@ def nmf(data, rank, init="random", U_0=None, V_0=None, n_iter_max=100, tol=1e-8,
     return compute_nmf(data, rank, U_0, V_0, n_iter_max=n_iter_max, tol=tol,
                        update_rule=update_rule, beta=beta,
                        sparsity_coefficients=sparsity_coefficients, fixed_modes=fixed_modes, normalize=normalize,
-                       verbose=verbose, return_costs=return_costs, deterministic=deterministic, unstored=unstored)
+                       verbose=verbose, return_costs=return_costs, deterministic=deterministic, unstored=unstored,
+                       weights=weights)
 
 
 def compute_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8,
                 update_rule="hals", beta=2,
                 sparsity_coefficients=[None, None], fixed_modes=[], normalize=[False, False],
-                verbose=False, return_costs=False, deterministic=False, sweep_log=None, group=None, unstored="zero"):
+                verbose=False, return_costs=False, deterministic=False, sweep_log=None, group=None, unstored="zero",
+                weights=None):
     """Outer loop of nmf.py:284-329.  ``sweep_log`` (extension): list receiving the inner sweep counts.
     ``group`` (extension): a torch.distributed process group -- `data` and `U_in` are then THIS RANK'S row block of a
     row-sharded problem (contiguous blocks, nn_fac_amd.dist.shard_rows), `V_in` is replicated; the Gram / cross terms, the
     stopping scalars and the cost are all-reduced over the group (RCCL over xGMI) and every rank returns its
     block of U, the whole V and the global costs (start values: nn_fac_amd.dist.sharded_random_init).
     Sparse `data` (a scipy.sparse matrix, a torch sparse-CSR tensor) runs in nn_fac_amd.sparse_nmf, over its stored entries;
-    ``unstored`` says what an unstored entry is, "zero" or "missing" (see there)."""
+    ``unstored`` says what an unstored entry is, "zero" or "missing" (see there).  ``weights`` (dense data, update_rule="mu"): a
+    weight per entry, floats >= 0 or a boolean mask; the run is nn_fac_amd.weighted_nmf's."""
+    if weights is not None:
+        from . import weighted_nmf
+        return weighted_nmf.compute_weighted_nmf(data, rank, U_in, V_in, weights, n_iter_max=n_iter_max, tol=tol,
+                                                 update_rule=update_rule, beta=beta, fixed_modes=fixed_modes, verbose=verbose,
+                                                 return_costs=return_costs, sweep_log=sweep_log, group=group)
     if is_sparse(data):
         from . import sparse_nmf
         return sparse_nmf.compute_sparse_nmf(data, rank, U_in, V_in, n_iter_max=n_iter_max, tol=tol, update_rule=update_rule,
@@ -113,8 +126,11 @@ def compute_nmf(data, rank, U_in, V_in, n_iter_max=100, tol=1e-8,
 
 
 def one_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta,
-                 sparsity_coefficients, fixed_modes, normalize, deterministic, unstored="zero"):
+                 sparsity_coefficients, fixed_modes, normalize, deterministic, unstored="zero", weights=None):
     """One pass of updates on U then V, then the cost (nmf.py:387-458).  Returns (U, V, cost)."""
+    if weights is not None:
+        from . import weighted_nmf
+        return weighted_nmf.one_weighted_nmf_step(data, rank, U_in, V_in, weights, update_rule, beta, fixed_modes)
     if is_sparse(data):
         from . import sparse_nmf
         return sparse_nmf.one_sparse_nmf_step(data, rank, U_in, V_in, norm_data, update_rule, beta, sparsity_coefficients,

@@ -9,6 +9,10 @@
 //                        Answer, one line per case: the "[nnf plan] ..." line of that launch, followed on the same line by the
 //                        fields of the plan the report leaves out (slots, ncb, ws_max), or "status=<code>" for a refusal.
 //                        beta = 2 (the Gram form of the MU updates: X H^T / W^T X + a Gram) is not a plan of these launchers.
+//                        mu_left / mu_right with ldw= (the pitch of the weights, >= n) and optionally walign= (their offset from a
+//                        16-byte boundary, in floats): the weighted forms (nnf_mu_left_w_f32 / nnf_mu_right_w_f32, bm=WGEN) --
+//                        any beta, 2 included; the general-beta plans with the offset bounds taken at max(pitch of X, ldw), and
+//                        16-byte loads only if X and the weights both qualify.
 //                        mu_mode (the mode update on the tensor's own layout, any beta) reads the same eight fields as
 //                          mu_mode <CUs> <L> <I> <r> <K> <beta> <workspace bytes> [align=] [ldv=]
 //                        and adds kt= wgpc= ws_max= pieces= ldp= ws_bytes= (what the launcher carves for the plan).
@@ -427,6 +431,21 @@ int main(int argc, char** argv) {
             if ((status = p.status) == NNF_OK)
                 nnf_report_rows(stdout, m, n, key_of(rest, "nb", 1), (int)r, MT, vec,
                                 nnf_rows_kr_fast(key_of(rest, "nb", 1), MT, key_of(rest, "lda", 1), key_of(rest, "ldb", 1)), p, more);
+        } else if ((left || strcmp(name, "mu_right") == 0) && key_of(rest, "ldw", 0) != 0) {   // the weighted forms
+            const long long ldw = key_of(rest, "ldw", 0);
+            const bool wvec = vec && key_of(rest, "walign", 0) % 4 == 0 && ldw % 4 == 0;
+            const nnf_rank_tiles t{(int)(r + 15) / 16, 0};
+            if (ldw < n || !(beta >= 0.0)) {
+                status = NNF_ERR_ARG;
+            } else if (left) {
+                const mu_left_plan p = mu_plan_left_w(cur, (int)C, m, n, ld, ldw, n, (int)r, t.MT);
+                snprintf(more, sizeof more, " slots=%lld", (long long)p.slots);
+                if ((status = p.status) == NNF_OK) mu_report_left(stdout, m, n, (int)r, t, wvec, BM_WGEN, p, more);
+            } else {
+                const mu_right_plan p = mu_plan_right_w(cur, (int)C, m, n, ld, ldw, m, (int)r, t.MT);
+                snprintf(more, sizeof more, " ncb=%d ws_max=%lld", p.ncb, (long long)p.split.ws_max);
+                if ((status = p.split.status) == NNF_OK) mu_report_right(stdout, m, n, (int)r, t, wvec, BM_WGEN, p, more);
+            }
         } else if ((left || strcmp(name, "mu_right") == 0) && beta != 2.0) {
             const int BM = beta == 1.0 ? BM_KL : BM_GEN;
             const nnf_rank_tiles t = mu_tiles_of(left, (int)r, BM == BM_KL, vec);
