@@ -317,6 +317,17 @@ int nnf_mu_left_f32(nnf_ctx* ctx, const float* X, int64_t m, int64_t n, int64_t 
 int nnf_mu_mode_f32(nnf_ctx* ctx, const float* T, int64_t L, int64_t I, int64_t K, const float* Ft, int64_t ldf,
                     const float* V, int64_t ldv, int r, double beta, float* out, int64_t ldo, void* stream);
 
+/* The sums of nnf_mu_mode_f32 under a weight per entry: Wg (contiguous, seen as (L, I, K) like T) holds finite weights >= 0,
+ *   num[k,i] = sum_{l,j} Wg T P^(beta-2) V[k, l*K+j],  den[k,i] = sum_{l,j} Wg P^(beta-1) V[k, l*K+j]      (both r x I, fp32)
+ * for any beta >= 0 (beta = 1 and beta = 2 exact: x/p and w, x and p).  The call returns the raw sums, as nnf_mu_left_w_f32 does;
+ * nnf_mu_apply_f32 finishes.  An entry of weight zero is out of both sums whatever T holds there (NaN, Inf): a slice whose
+ * weights are all zero gets num = den = 0 exactly.  Under a positive weight a zero of T is an observed zero.  The partial sums
+ * of the column splits (two sets of r x I in the context workspace, nothing else) are added in split order in fp64: two calls
+ * are bitwise equal.  16-byte loads need T, Wg and V aligned.  r <= 64 (else NNF_ERR_UNSUPPORTED). */
+int nnf_mu_mode_w_f32(nnf_ctx* ctx, const float* T, const float* Wg, int64_t L, int64_t I, int64_t K, const float* Ft, int64_t ldf,
+                      const float* V, int64_t ldv, int r, double beta, float* num, int64_t ldn, float* den, int64_t ldd,
+                      void* stream);
+
 /* nnf_mu_left_f32 with beta = 1 that also returns *cost_f64 = beta_divergence(X, U V, 1) of the factors it STARTS from
  * (mu.py:84-88 + nmf.py:455): the update forms every entry of U V anyway, so the cost of outer iteration i is a by-product of
  * the left update of iteration i+1 and the separate pass over X (nnf_betadiv_f32) is only needed after the last one.

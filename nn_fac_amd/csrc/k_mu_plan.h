@@ -153,6 +153,12 @@ constexpr int MU_MODE_CHUNK = 4;            // units per staged chunk of V
 // 4-wave workgroups up to 128 VGPRs (beta = 1 up to MT = 3, and MT = 4 with 16-byte loads: 128; beta != 1 up to MT = 2: 108),
 // three beyond (beta = 1, MT = 4, scalar loads: 132; beta != 1, MT = 3 and 4: 136 .. 152).  LDS (4 KiB per rank tile) never binds.
 constexpr int mu_mode_wgpc(int MT, bool kl, bool vec) { return (kl ? (MT <= 3 || vec) : MT <= 2) ? 4 : 3; }
+// the weighted form (nnf_mu_mode_w_f32: one instantiation per MT and load width serves every beta; MU_MODE_CHUNK more f32x4 in
+// flight for the weights, and their copies of the chunk being worked on, next to both accumulators).  VGPRs of the instantiations
+// (build/k_mu_mode.s; none spills, none has scratch), 16-byte | scalar loads: MT = 1: 128 | 128, MT = 2: 148 | 156, MT = 3: 180 |
+// 184, MT = 4: 204 | 212 -- four 4-wave workgroups per CU up to 128 VGPRs, three up to 168, two up to 256: the load width never
+// changes the figure
+constexpr int mu_mode_w_wgpc(int MT, bool /*vec*/) { return MT <= 1 ? 4 : MT == 2 ? 3 : 2; }
 // a workgroup sums its columns in fp32 MFMA accumulators: at most 256 units = 4096 columns, a chain of 1024 MFMA steps (the
 // W^T X kernel's 2048-row cap is a chain of 512; its notes in k_stream_plan.h say what longer chains cost)
 constexpr int64_t MU_MODE_UNITS_CAP = 256;
@@ -171,22 +177,23 @@ struct mu_mode_plan {
     int64_t ldp;        // pitch of a slab row
 };
 // `cur`: a copy of the caller's cursor -- the update takes r doubles, the row sums' partials, then one (beta = 1) or two sets of
-// nsplit slabs of r x ldp floats
-inline mu_mode_plan mu_plan_mode(nnf_ws_cursor cur, int cus, int64_t L, int64_t I, int64_t K, int r, bool kl, bool vec) {
+// nsplit slabs of r x ldp floats.  `weighted` (nnf_mu_mode_w_f32, any beta): two sets of slabs and nothing in front of them
+inline mu_mode_plan mu_plan_mode(nnf_ws_cursor cur, int cus, int64_t L, int64_t I, int64_t K, int r, bool kl, bool vec,
+                                 bool weighted = false) {
     mu_mode_plan p{NNF_ERR_UNSUPPORTED, nnf_cdiv(I, MU_MODE_ROWS), nnf_cdiv(K, MU_MODE_UNIT), 0, 0, 0, "occupancy", 0, 0, nnf_rup(I, 4)};
     if (r > MU_MODE_MAX_RANK) return p;
     // element and column indices are 64-bit in the kernel; keep the products well inside them
     if ((double)L * (double)I * (double)K >= 4.0e18 || (double)L * (double)p.kt >= 4.0e18) return p;
     p.units = L * p.kt;
-    p.pieces = kl ? nnf_rowsum_pieces(L * K) : 0;
+    p.pieces = kl && !weighted ? nnf_rowsum_pieces(L * K) : 0;
     p.status = NNF_ERR_WORKSPACE;
-    if (!cur.reserve((size_t)r * 8) || (p.pieces > 1 && !cur.reserve((size_t)r * p.pieces * 8))) return p;
-    const int nsets = kl ? 1 : 2;
+    if (!weighted && (!cur.reserve((size_t)r * 8) || (p.pieces > 1 && !cur.reserve((size_t)r * p.pieces * 8)))) return p;
+    const int nsets = kl && !weighted ? 1 : 2;
     const int64_t slab_bytes = (int64_t)r * p.ldp * 4, free = (int64_t)cur.remaining();
     p.ws_max = free / (slab_bytes * nsets);
     while (nsets > 1 && p.ws_max >= 1 && nnf_rup(p.ws_max * slab_bytes, 256) + p.ws_max * slab_bytes > free) --p.ws_max;
     if (p.ws_max < 1) return p;
-    p.nsplit = (int64_t)mu_mode_wgpc((r + 15) / 16, kl, vec) * cus / p.nrb;
+    p.nsplit = (int64_t)(weighted ? mu_mode_w_wgpc((r + 15) / 16, vec) : mu_mode_wgpc((r + 15) / 16, kl, vec)) * cus / p.nrb;
     if (p.nsplit < 1) p.nsplit = 1;
     if (p.nsplit < nnf_cdiv(p.units, MU_MODE_UNITS_CAP)) { p.nsplit = nnf_cdiv(p.units, MU_MODE_UNITS_CAP); p.bound = "chain"; }
     if (p.nsplit > nnf_cdiv(p.units, MU_MODE_CHUNK)) { p.nsplit = nnf_cdiv(p.units, MU_MODE_CHUNK); p.bound = "min_cols"; }
@@ -199,16 +206,17 @@ inline mu_mode_plan mu_plan_mode(nnf_ws_cursor cur, int cus, int64_t L, int64_t 
     return p;
 }
 // bytes the launcher carves for a plan (tools/nnf_plan.cpp prints it; tests/test_mu_mode_plan.py checks it against a cursor)
-inline size_t mu_mode_ws_bytes(const mu_mode_plan& p, int r, bool kl) {
+inline size_t mu_mode_ws_bytes(const mu_mode_plan& p, int r, bool kl, bool weighted = false) {
     nnf_ws_cursor c(nullptr, ~size_t(0) >> 1);
-    c.reserve((size_t)r * 8);
+    if (!weighted) c.reserve((size_t)r * 8);
     if (p.pieces > 1) c.reserve((size_t)r * p.pieces * 8);
-    for (int s = 0; s < (kl ? 1 : 2); ++s) c.reserve((size_t)p.nsplit * r * p.ldp * 4);
+    for (int s = 0; s < (kl && !weighted ? 1 : 2); ++s) c.reserve((size_t)p.nsplit * r * p.ldp * 4);
     return c.off;
 }
 inline void mu_report_mode(FILE* f, int64_t L, int64_t I, int64_t K, int r, int MT, bool vec, bool kl, const mu_mode_plan& p,
-                           const char* more = "") {
-    fprintf(f, "[nnf plan] mu_mode L=%lld I=%lld K=%lld r=%d mt=%d vec=%d bm=%s nrb=%lld nsplit=%lld ups=%lld units=%lld bound=%s%s\n",
-            (long long)L, (long long)I, (long long)K, r, MT, (int)vec, kl ? "KL" : "GEN", (long long)p.nrb, (long long)p.nsplit,
+                           const char* more = "", bool weighted = false) {
+    fprintf(f, "[nnf plan] %s L=%lld I=%lld K=%lld r=%d mt=%d vec=%d bm=%s nrb=%lld nsplit=%lld ups=%lld units=%lld bound=%s%s\n",
+            weighted ? "mu_mode_w" : "mu_mode", (long long)L, (long long)I, (long long)K, r, MT, (int)vec,
+            weighted ? mu_bm_name(BM_WGEN) : kl ? "KL" : "GEN", (long long)p.nrb, (long long)p.nsplit,
             (long long)p.ups, (long long)p.units, p.bound, more);
 }

@@ -574,6 +574,26 @@ class WeightedOps:
         self._call("nnf_mu_right_w_f32", _ptr(X), m, n, _ld(X), *_mat(Wg), *_mat(Ut), *_mat(V), r, beta, *_mat(N), *_mat(D))
         return N, D
 
+    def mu_mode_w(self, T3, W3, Ft, V, beta, out_num=None, out_den=None):
+        """The sums of mu_mode under a weight per entry (nnf_mu_mode_w_f32): `T3` the contiguous tensor seen as (L, I_n, K), `W3`
+        its weights in the same shape, `Ft` (r x I_n), `V` (r x L*K).  num[k, i] = sum_{l,j} W3 T3 P^(beta-2) V[k, l*K+j],
+        den[k, i] = sum_{l,j} W3 P^(beta-1) V[k, l*K+j] (both r x I_n); r <= 64.  Returns (num, den); mu_apply finishes."""
+        L, I, K = _t3(T3, "mu_mode_w: T3, seen as (L, I, K),").shape
+        _t3(W3, "mu_mode_w: W3, the weights of T3,")
+        if W3.shape != T3.shape or W3.device != T3.device:
+            raise EngineError(f"mu_mode_w W3: {tuple(T3.shape)} on {T3.device} expected, got {tuple(W3.shape)} on {W3.device}")
+        r = _chk2d(Ft, "mu_mode_w Ft").shape[0]
+        if Ft.shape[1] != I:
+            raise EngineError(f"mu_mode_w Ft: shape mismatch, T3 is {tuple(T3.shape)}, Ft {tuple(Ft.shape)}")
+        _shaped(V, (r, L * K), "mu_mode_w V")
+        if r > self.MU_MODE_MAX_RANK:
+            raise EngineError("mu_mode_w Ft: built for r <= 64")
+        beta = _obs_beta(beta, "mu_mode_w")
+        N = _out(out_num, (r, I), Ft, "mu_mode_w out_num")
+        D = _out(out_den, (r, I), Ft, "mu_mode_w out_den")
+        self._call("nnf_mu_mode_w_f32", _ptr(T3), _ptr(W3), L, I, K, *_mat(Ft), *_mat(V), r, beta, *_mat(N), *_mat(D))
+        return N, D
+
     def betadiv_w(self, X, Wg, Ut, V, beta, out=None):
         """sum_ij Wg[i, j] d_beta(X[i, j] | (Ut^T V)[i, j]) into a 1-element float64 device tensor (nnf_betadiv_w_f32)."""
         m, n, r, beta = self._xwuv(X, Wg, Ut, V, beta, "betadiv_w")

@@ -41,9 +41,14 @@ from ._outer_loop import _IdentityUnreliable, _IdentityNearStop, _GuessMissed  #
 def ntf(tensor, rank, init="random", factors_0=[], n_iter_max=100, tol=1e-8,
         update_rule="hals", beta=2,
         sparsity_coefficients=[], fixed_modes=[], normalize=[],
-        verbose=False, return_costs=False, unstored="zero"):
+        verbose=False, return_costs=False, unstored="zero", weights=None):
     """Nonnegative PARAFAC of `tensor` (reference docstring: ntf.py:23-179).  ``unstored`` (extension, sparse tensors): "zero" reads
-    an unstored entry as a zero, "missing" as unknown -- the fit is over the stored entries only (sparse_ntf.py)."""
+    an unstored entry as a zero, "missing" as unknown -- the fit is over the stored entries only (sparse_ntf.py).
+    ``weights`` (extension, dense tensors, update_rule="mu"): an array of the tensor's shape, floats >= 0 or a boolean mask -- the fit
+    minimises sum w d_beta(t | model); an entry of weight zero is missing, whatever the tensor holds there (weighted_ntf.py)."""
+    if weights is not None:  # weighted_ntf.py: what that path refuses is said before the start values are drawn
+        from . import weighted_ntf
+        weighted_ntf.check_request(tensor.shape, is_sparse_tensor(tensor), weights, rank, update_rule, beta, init=init)
     if is_sparse_tensor(tensor):      # sparse_ntf.py: what that path refuses is said before the start values are drawn
         from . import sparse_ntf
         sparse_ntf.check_request(rank, update_rule, beta, len(tensor.shape), init=init, unstored=unstored)
@@ -66,7 +71,7 @@ def ntf(tensor, rank, init="random", factors_0=[], n_iter_max=100, tol=1e-8,
     return compute_ntf(tensor, rank, factors, n_iter_max=n_iter_max, tol=tol,
                        update_rule=update_rule, beta=beta,
                        sparsity_coefficients=sparsity_coefficients, fixed_modes=fixed_modes, normalize=normalize,
-                       verbose=verbose, return_costs=return_costs, unstored=unstored)
+                       verbose=verbose, return_costs=return_costs, unstored=unstored, weights=weights)
 
 
 class _NtfState(TensorState, _loop.AsyncStop):
@@ -386,10 +391,17 @@ def run_ntf_steps(st, rank, Ft, n_iter, update_rule, beta, sparsity_coefficients
 def compute_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8,
                 update_rule="hals", beta=2,
                 sparsity_coefficients=[], fixed_modes=[], normalize=[],
-                verbose=False, return_costs=False, alpha=0.5, delta=0.01, sweep_log=None, unstored="zero"):
+                verbose=False, return_costs=False, alpha=0.5, delta=0.01, sweep_log=None, unstored="zero", weights=None):
     """Outer loop of ntf.py:288-344.  Returns the list of factors (dim x R each) [, costs, toc].
     A sparse `tensor_in` (a torch sparse-COO tensor, a sparse_ntf.SparseCOO) runs in nn_fac_amd.sparse_ntf, over its stored entries;
-    ``unstored`` says what an unstored entry is, "zero" or "missing" (see there)."""
+    ``unstored`` says what an unstored entry is, "zero" or "missing" (see there).  ``weights`` (dense tensors, update_rule="mu"): a
+    weight per entry, floats >= 0 or a boolean mask; the run is nn_fac_amd.weighted_ntf's."""
+    if weights is not None:
+        from . import weighted_ntf
+        return weighted_ntf.compute_weighted_ntf(tensor_in, rank, factors_in, weights, n_iter_max=n_iter_max, tol=tol,
+                                                 update_rule=update_rule, beta=beta, sparsity_coefficients=sparsity_coefficients,
+                                                 fixed_modes=fixed_modes, verbose=verbose, return_costs=return_costs,
+                                                 sweep_log=sweep_log)
     if is_sparse_tensor(tensor_in):
         from . import sparse_ntf
         return sparse_ntf.compute_sparse_ntf(tensor_in, rank, factors_in, n_iter_max=n_iter_max, tol=tol, update_rule=update_rule,
@@ -425,10 +437,14 @@ def compute_ntf(tensor_in, rank, factors_in, n_iter_max=100, tol=1e-8,
 
 def one_ntf_step(unfolded_tensors, rank, in_factors, norm_tensor, update_rule, beta,
                  sparsity_coefficients, fixed_modes, normalize,
-                 alpha=0.5, delta=0.01, unstored="zero"):
+                 alpha=0.5, delta=0.01, unstored="zero", weights=None):
     """One pass over the modes (ntf.py:422-477).  `unfolded_tensors` is the reference's list of unfoldings; the tensor is
     rebuilt from the mode-0 unfolding (a plain reshape).  Returns (factors, cost).  A sparse tensor (sparse_ntf.py) is passed
-    as itself, where the unfoldings are."""
+    as itself, where the unfoldings are.  ``weights`` (weighted_ntf.py): in the tensor's shape or in the mode-0 unfolding's."""
+    if weights is not None:
+        from . import weighted_ntf
+        return weighted_ntf.one_weighted_ntf_step(unfolded_tensors, rank, in_factors, norm_tensor, weights, update_rule, beta,
+                                                  sparsity_coefficients, fixed_modes)
     if is_sparse_tensor(unfolded_tensors):
         from . import sparse_ntf
         return sparse_ntf.one_sparse_ntf_step(unfolded_tensors, rank, in_factors, norm_tensor, update_rule, beta,

@@ -25,8 +25,8 @@ there -- and the only one for weights other than 0 and 1.
 Refused before the device is touched, each with what to use instead: update_rule="hals" (one Gram per row, a different algorithm),
 sparse data (that is unstored="missing"), `group=` (sharded runs), init="nndsvd" (an SVD of data with holes in it), ranks above
 128, a weight array of another shape or dtype, beta < 0.  Negative or non-finite weights are refused after the upload, by one
-device reduction.  Not built: weights on ntf, ntd, PARAFAC2, the simplex, deep and multilayer drivers; one-byte masks in the
-kernels; a cost that rides in the left update.
+device reduction.  Not built: weights on ntd, PARAFAC2, the simplex, deep and multilayer drivers; one-byte masks in the
+kernels; a cost that rides in the left update.  (Weights on ntf: weighted_ntf.py.)
 
 The outer loop, its stopping test, `return_costs`, `toc` and `sweep_log` are those of compute_nmf, on `_outer_loop.Pipeline`.
 """

@@ -2,7 +2,7 @@
 // k_mu_plan.h, k_hals_plan.h, k_simplex_plan.h) for any CU count, printed as the library reports them under NNF_PLAN_DEBUG / NNF_HALS_DEBUG.
 //
 //   nnf_plan < cases     one case per line:  <launcher> <CUs> <m> <n> <r> <row pitch of X> <beta> <workspace bytes> [key=value ...]
-//                        launcher: xht | xty | mu_left | mu_right | mu_mode | mttkrp_rows | mttkrp_seg | partial_last |
+//                        launcher: xht | xty | mu_left | mu_right | mu_mode | mu_mode_w | mttkrp_rows | mttkrp_seg | partial_last |
 //                        partial_mid | gram | cost; the factors are contiguous (r x m, r x n);
 //                        optional keys: align= (offset of X from a 16-byte boundary, in floats; default 0) and, for mttkrp_rows
 //                        (m x n = the unfolded tensor, pitch n), nb= lda= ldb= (Khatri-Rao inner length, factor pitches).
@@ -16,6 +16,8 @@
 //                        mu_mode (the mode update on the tensor's own layout, any beta) reads the same eight fields as
 //                          mu_mode <CUs> <L> <I> <r> <K> <beta> <workspace bytes> [align=] [ldv=]
 //                        and adds kt= wgpc= ws_max= pieces= ldp= ws_bytes= (what the launcher carves for the plan).
+//                        mu_mode_w (its weighted form, nnf_mu_mode_w_f32, bm=WGEN) reads the same line plus walign= (the weights'
+//                        offset from a 16-byte boundary, in floats): any beta on two sets of slabs with nothing in front of them.
 //                        The tensor and Gram launchers read the eight fields as
 //                          mttkrp_seg <CUs> <rows> <segment length> <r> <row pitch> 0 <workspace bytes> [align=] [nseg=] [segstride=]
 //                                     [fsld=] [fkld=] [fkalign=]     (segments per row, their stride, the pitches of the segment-side
@@ -320,17 +322,20 @@ int main(int argc, char** argv) {
         const bool left = strcmp(name, "mu_left") == 0;
         int status = NNF_ERR_UNSUPPORTED;   // (ranks above 128 run in passes of 128: ask for one pass)
         more[0] = 0;
-        if (strcmp(name, "mu_mode") == 0) {   // m = L, n = I, ld = K
+        if (strcmp(name, "mu_mode") == 0 || strcmp(name, "mu_mode_w") == 0) {   // m = L, n = I, ld = K
             const long long ldv = key_of(rest, "ldv", m * ld);
-            const bool kl = beta == 1.0, mvec = key_of(rest, "align", 0) % 4 == 0 && ld % 4 == 0 && ldv % 4 == 0;
+            const bool wt = name[7] != 0;   // the weighted form: any beta on the two-accumulator plan, 16-byte loads need Wg aligned too
+            const bool kl = beta == 1.0 && !wt;
+            const bool mvec = key_of(rest, "align", 0) % 4 == 0 && ld % 4 == 0 && ldv % 4 == 0 && (!wt || key_of(rest, "walign", 0) % 4 == 0);
+            const int MT = (int)(r + 15) / 16;
             if (m < 1 || n < 1 || ld < 1 || r < 1 || !(beta >= 0.0) || ldv < m * ld) {
                 status = NNF_ERR_ARG;
             } else {
-                const mu_mode_plan p = mu_plan_mode(cur, (int)C, m, n, ld, (int)r, kl, mvec);
+                const mu_mode_plan p = mu_plan_mode(cur, (int)C, m, n, ld, (int)r, kl, mvec, wt);
                 snprintf(more, sizeof more, " kt=%lld wgpc=%d ws_max=%lld pieces=%d ldp=%lld ws_bytes=%zu", (long long)p.kt,
-                         mu_mode_wgpc((int)(r + 15) / 16, kl, mvec), (long long)p.ws_max,
-                         p.pieces, (long long)p.ldp, p.status == NNF_OK ? mu_mode_ws_bytes(p, (int)r, kl) : (size_t)0);
-                if ((status = p.status) == NNF_OK) mu_report_mode(stdout, m, n, ld, (int)r, (int)(r + 15) / 16, mvec, kl, p, more);
+                         wt ? mu_mode_w_wgpc(MT, mvec) : mu_mode_wgpc(MT, kl, mvec), (long long)p.ws_max,
+                         p.pieces, (long long)p.ldp, p.status == NNF_OK ? mu_mode_ws_bytes(p, (int)r, kl, wt) : (size_t)0);
+                if ((status = p.status) == NNF_OK) mu_report_mode(stdout, m, n, ld, (int)r, MT, mvec, kl, p, more, wt);
             }
         } else if (m < 1 || n < 1 || r < 1 || ld < n) {
             status = NNF_ERR_ARG;
